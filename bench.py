@@ -2,7 +2,17 @@
 """bench.py — Schnorr verifies/sec on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-batch B] [--config single|mixed]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps, checks their verdicts against the expected
+pattern and prints the headline line (`value`, `ms_per_step`).  Everything below that rides along —
+per-kernel and roofline figures, the secondary schemes and input forms, the small-batch latency, the
+CPU baseline and oracle samples, per-rank stage times — runs only with --full (implied by
+--dump-inputs and --cpu-baseline-file).
+--dump-outputs DIR writes what the last timed step computed (the verdict vector, as float32) to
+DIR/verdicts.npy (with N > 1 also DIR/gathered_verdicts.npy, the all-gathered vector); the inputs
+are seeded, so two builds can be compared output for output.
 
 One "step" = one pass of the verify hot path over one batch per GPU, inputs already resident in
 HBM, through the public device-pointer entry points of libdsv.so:
@@ -25,7 +35,7 @@ processes, started before this process touches the GPU; LOCAL_RANK -> device, re
 
 Batches are generated on the GPU by the engine's own sign kernels from the reference harness's
 StdRng streams; every 16th item is corrupted, so the expected verdict vector is non-trivial; it is
-checked after the timed region, and at N = 1 samples are re-verified by the CPU oracle.
+checked after the timed region, and with --full at N = 1 samples are re-verified by the CPU oracle.
 
 Prints ONE JSON line on rank 0.  `roofline` is SURVEY.md §8(d)'s figure for the dominant kernel
 k_verify_fixed_half: v_mad_u64_u32 lane-operations per verdict x verdicts / the kernel's launch
@@ -37,7 +47,8 @@ decompression on the device), `host_path` / `host_path_ext` / `wire.host` (PCIe-
 headline value), `verify_batch_e2e` (the named entry point over 2^20 typed objects holding the
 reference's in-memory representation, conversion included; tools/verify_batch_e2e.cpp),
 `small_batch` (measured first).  What is live and what is replayed from a committed PMC pass:
-`roofline.pmc_source`.  With N > 1: `ranks` (per-rank step / init / gather / stage times).
+`roofline.pmc_source`.  With N > 1: `ranks` (per-rank step and init times; with --full also the
+gather and stage times).  All of this paragraph but `ranks.ms_per_step` / `ranks.init_s` needs --full.
 """
 import argparse
 import json
@@ -353,6 +364,23 @@ def _verify_batch_e2e(E, hu, hR, hPK, hm, expected, cores):
     return res
 
 
+DUMP_BUDGET = 64 << 20   # bytes over all files --dump-outputs writes
+
+
+def _dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  An array past its share of the budget
+    is replaced by a fixed, seeded sample of its items, whose positions go to DIR/<name>_index.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32).reshape(-1)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(2321).choice(a.size, size=share // (4 + 8), replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -389,13 +417,21 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-double", action="store_true", help="skip the secondary figures")
     ap.add_argument("--dump-inputs", metavar="DIR",
-                    help="write the timed batches (single, double, var-generator) as the reference's wire records "
+                    help="(implies --full) write the timed batches (single, double, var-generator) as the reference's wire records "
                          "+ the GPU verdicts into DIR: the input of rust/dusk-schnorr-gpu/src/bin/bench_ref.rs, "
                          "which times the REAL crate's pk.verify(&sig, m) over them")
     ap.add_argument("--cpu-baseline-file", metavar="JSON",
-                    help="output of bench_ref (the real dusk-schnorr crate on this box's host cores): becomes "
+                    help="(implies --full) output of bench_ref (the real dusk-schnorr crate on this box's host cores): becomes "
                          "cpu_baseline with kind \"crate\"; the oracle's figures stay beside it as `port`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: small-batch latency, "
+                         "per-kernel / roofline figures, double / var-generator / fast accept / input forms / "
+                         "signing / mixed, CPU baseline and oracle samples, host paths, per-rank stage times")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the verdicts of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.dump_inputs or args.cpu_baseline_file:
+        args.full = True                         # both feed on the secondary legs / the CPU baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args.gpus))
@@ -484,14 +520,18 @@ def main():
         return sum(a.elapsed_time(b) for a, b in pairs) / max(1, len(pairs))
 
     # ------------------------------------------------------------------ configs[4]: mixed batch
-    def run_mixed(steps, warmup):
+    def run_mixed(steps, warmup, keep_outputs=False):
         mb = W.gen_mixed(n, seed=2321, device=dev, first_item=rank * n)
         gk = (torch.arange(world * n, device=dev) & 1).to(torch.uint8)   # the global kind vector
         ver = MixedShardedVerifier(n, mb["n_double"], world, rank, dev, collective=multi)
         if multi:
             ver(mb, gk)                          # communicator set-up is not a step
-        dtm = timed(lambda: ver(mb, gk), steps, warmup)
-        out_all = ver(mb, gk)
+        last = [None]
+
+        def step_m():
+            last[0] = ver(mb, gk)
+        dtm = timed(step_m, steps, warmup)
+        out_all = last[0]                        # the verdicts of the last timed step
         torch.cuda.synchronize()
         mine = out_all[rank * n:(rank + 1) * n]
         bad = int((mine != mb["expected"]).sum().item())
@@ -502,9 +542,15 @@ def main():
         if bad or ver.local_counts() != (n - mb["n_double"], mb["n_double"]):
             raise SystemExit("rank %d: mixed batch: %d verdicts differ / counts %r"
                              % (rank, bad, ver.local_counts()))
+        outputs = {}
+        if keep_outputs and rank == 0:
+            outputs["verdicts"] = mine.cpu().numpy()
+            if multi:
+                outputs["gathered_verdicts"] = out_all.cpu().numpy()
         ranks = None
         if multi:
             ranks = {"ms_per_step": last_ranks["ms_per_step"]}
+        if multi and args.full:
             prof = ver.profile(mb, gk, reps=3)   # HIP events around each stage, outside the timed region
             for k_, v_ in prof.items():
                 ranks[k_] = per_rank(v_)
@@ -518,7 +564,7 @@ def main():
                "n_gpus": world}
         if ranks:
             res["ranks"] = ranks
-        return res, mb
+        return res, mb, outputs
 
     base = {
         "metric": METRIC, "unit": "verifies/s", "n_gpus": world, "steps": args.steps,
@@ -531,7 +577,9 @@ def main():
     }
 
     if args.config == "mixed":
-        res, _ = run_mixed(args.steps, args.warmup)
+        res, _, outputs = run_mixed(args.steps, args.warmup, keep_outputs=bool(args.dump_outputs))
+        if args.dump_outputs and rank == 0:
+            _dump_outputs(args.dump_outputs, outputs)
         if multi:
             base["ranks"] = dict(res.pop("ranks"), init_s=per_rank(init_s))
         out = dict(base, value=res["value"], ms_per_step=res["ms_per_step"],
@@ -557,7 +605,7 @@ def main():
     # ---- BASELINE configs[0] size through the host entry point: latency of a 1024-item call,
     # measured FIRST (a fresh process, nothing else in flight): 200 calls after 10 warm ones
     small_batch = None
-    if rank == 0 and world == 1 and not args.no_double:
+    if args.full and rank == 0 and world == 1 and not args.no_double:
         sb = [batch[k][:1024].cpu().numpy() for k in ("u", "R", "PK", "m")]
         for _ in range(10):
             E.verify_single(*sb)
@@ -584,11 +632,17 @@ def main():
         dist.all_gather_into_tensor(gathered, ok)  # RCCL connects lazily: not a step
     dt = timed(step, args.steps, args.warmup)
     ok_api = ok.clone()
+    outputs = {}
+    if args.dump_outputs and rank == 0:          # what the last timed step handed its caller
+        outputs["verdicts"] = ok_api.cpu().numpy()
+        if multi:
+            outputs["gathered_verdicts"] = gathered.cpu().numpy()
     ranks = None
     if multi:
+        ranks = {"ms_per_step": last_ranks["ms_per_step"], "init_s": per_rank(init_s)}
+    if multi and args.full:
         # where each rank's step goes (outside the timed region: HIP events on the current stream around
         # the verify call and around the all_gather, which includes the wait for the slowest rank)
-        ranks = {"ms_per_step": last_ranks["ms_per_step"], "init_s": per_rank(init_s)}
         ev_v, ev_g = event_pairs(5), event_pairs(5)
         sync_all()
         for (a, b), (c_, d_) in zip(ev_v, ev_g):
@@ -615,8 +669,9 @@ def main():
         torch.cuda.synchronize()
         return sum(a.elapsed_time(b) for a, b in evs) / reps
 
-    hash_ms = event_ms(lambda: E.challenge_single_dev(batch["R"], batch["m"], c, valid))
-    core_ms = event_ms(lambda: E.verify_core_dev(batch["u"], c, valid, batch["PK"], batch["R"], ok, ws))
+    if args.full:
+        hash_ms = event_ms(lambda: E.challenge_single_dev(batch["R"], batch["m"], c, valid))
+        core_ms = event_ms(lambda: E.verify_core_dev(batch["u"], c, valid, batch["PK"], batch["R"], ok, ws))
 
     mism = int((ok != batch["expected"]).sum().item())
     mism_api = int((ok_api != batch["expected"]).sum().item())
@@ -626,13 +681,15 @@ def main():
     if mism or mism_api:
         raise SystemExit("rank %d: %d / %d verdicts differ from the expected pattern"
                          % (rank, mism, mism_api))
+    if outputs:
+        _dump_outputs(args.dump_outputs, outputs)
 
     value = n * world * args.steps / dt
     out = dict(base, value=value, ms_per_step=dt / args.steps * 1e3,
                data="synthetic: reference harness inputs (StdRng::seed_from_u64(2321): sk, m, nonce "
                     "per item, restated RNG), GPU-signed, every 16th item corrupted",
                config={"workload": "2^%d single-signature batch verify per GPU (BASELINE configs[1]); "
-                                   "`value` is this figure, `double` / `vargen` / `mixed` ride along"
+                                   "`value` is this figure, `double` / `vargen` / `mixed` ride along with --full"
                                    % args.log2_batch,
                        "batch_per_gpu": n, "parallelism": "dp%d" % world,
                        "collective": "all_gather of verdict bytes" if multi else "none"})
@@ -657,7 +714,7 @@ def main():
         kernels[name] = blk
         return blk
 
-    if rank == 0:
+    if rank == 0 and args.full:
         vm, vs = _verify_counts(1)
         dom = kernel_block("k_verify_fixed_half<1>", core_ms, n, vm, vs, other=VERIFY_OTHER,
                            algo_bytes=ALGO_BYTES["single"])
@@ -734,7 +791,7 @@ def main():
 
     # ---- secondary figures (N = 1): double (configs[2]), var-generator (configs[3]), signing
     sample_checks = {}
-    if not args.no_double and world == 1:
+    if args.full and not args.no_double and world == 1:
         reps = max(1, args.steps // 2)
         bd = W.gen_double(n, seed=4242, device=dev)
         okd = torch.zeros(n, dtype=torch.uint8, device=dev)
@@ -998,14 +1055,14 @@ def main():
         out["sign"] = {"value": n * reps / tss, "unit": "signatures/s",
                        "workload": "2^%d single signatures, nonces supplied" % args.log2_batch}
         del sk_, r_, su, sR
-        mres, mb = run_mixed(reps, 1)
+        mres, mb, _ = run_mixed(reps, 1)
         out["mixed"] = mres
         sample_checks["mixed"] = (mb, None)
         if rank == 0:
             out["roofline"]["kernels"] = kernels
-    elif world > 1 and not args.no_double:
+    elif args.full and world > 1 and not args.no_double:
         # the multi-GPU run also measures configs[4] (2^20 mixed items per GPU), same process group
-        mres, _ = run_mixed(max(1, args.steps // 2), 1)
+        mres, _, _ = run_mixed(max(1, args.steps // 2), 1)
         out["mixed"] = mres
 
     # ---- the timed batches as the reference's wire records, for the real crate's CPU loop (bench_ref.rs)
@@ -1035,7 +1092,7 @@ def main():
                                 "next": "DSV_NO_LINK=1 cargo run --release --bin bench_ref -- %s" % args.dump_inputs}
 
     # ---- CPU baseline: the oracle (port of the reference algorithm) on the host cores
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
 

@@ -396,7 +396,7 @@ def test_bench_spawns_its_own_ranks_and_runs_the_mixed_config():
         assert len(lines) == 1, r.stdout[-1500:]
         return json.loads(lines[0])
 
-    d = run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "15"])
+    d = run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "15", "--full"])
     assert d["n_gpus"] == 2 and d["world_size"] == 2 and d["launcher"] == "self-spawned"
     assert d["backend"] == "gloo" and d["value"] > 0 and d["scaling"] == "weak"
     assert d["mixed"]["n_gpus"] == 2 and d["mixed"]["value"] > 0
@@ -412,7 +412,7 @@ def test_bench_collectives_over_rccl_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in drop}
     env["DSV_BENCH_FORCE_DIST"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--log2-batch", "16", "--no-cpu-baseline"], cwd=ROOT, env=env,
+                        "--log2-batch", "16", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][0])

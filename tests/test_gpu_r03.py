@@ -262,15 +262,15 @@ def test_half_gcd_near_equal_remainders_do_not_spin(engine):
 @pytest.mark.parametrize("world,config", [(4, "single"), (5, "single"), (5, "mixed")])
 def test_bench_rehearses_larger_world_sizes_on_one_gpu(world, config):
     """`python bench.py --gpus N` spawns N fresh ranks (gloo, all on GPU 0): ports,
-    shard arithmetic, N contexts' memory, gathered verdicts of every other rank.  The default config
-    at N > 1 also runs configs[4] (mixed) in the same process group.  The GPU box admits six
+    shard arithmetic, N contexts' memory, gathered verdicts of every other rank.  With --full the
+    default config at N > 1 also runs configs[4] (mixed) in the same process group.  The GPU box admits six
     processes on its card and this test process is one of them, so N = 5 is the largest rehearsal
     that may run here; world size 8 is covered on the CPU (tests/test_distributed.py)."""
     drop = ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")
     env = {k: v for k, v in os.environ.items() if k not in drop}
     env.update({"DSV_BENCH_DEVICE": "0", "DSV_BENCH_BACKEND": "gloo"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1",
-           "--warmup", "1", "--log2-batch", "13", "--config", config, "--no-cpu-baseline"]
+           "--warmup", "1", "--log2-batch", "13", "--config", config, "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

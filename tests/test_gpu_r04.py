@@ -163,7 +163,7 @@ def test_bench_under_the_drivers_launcher(engine):
     env.update({"DSV_BENCH_DEVICE": "0", "DSV_BENCH_BACKEND": "gloo"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "14", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "14", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.strip()]

@@ -8,7 +8,7 @@ ROUNDS=${2:-3}
 for i in $(seq $ROUNDS); do
   for which in prev cur; do
     if [ $which = prev ]; then export DSV_LIB_PATH=$PWD/$PREV; else unset DSV_LIB_PATH; fi
-    python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['roofline'].get('model',{})

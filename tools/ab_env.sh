@@ -4,7 +4,7 @@
 ROUNDS=$1; VAR=$2; shift 2
 for i in $(seq $ROUNDS); do
   for v in "$@"; do
-    env $VAR=$v python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+    env $VAR=$v python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline']['kernels']

@@ -2,7 +2,7 @@
 # bench.py's verify_batch_e2e.fast_accept (typed objects -> verify_batch_fast) and the host wire form under several settings
 set -e
 for cfg in "DSV_RLC_STAGED=1" "DSV_RLC_STAGED=0" "DSV_RLC_STAGED=1" "DSV_RLC_STAGED=0"; do
-  env $cfg python bench.py 2>/dev/null | python -c "
+  env $cfg python bench.py --full 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 f=j['verify_batch_e2e']['fast_accept']

@@ -6,7 +6,7 @@ ROUNDS=$1; shift
 for i in $(seq $ROUNDS); do
   for which in "$@"; do
     if [ $which = cur ]; then unset DSV_LIB_PATH; else export DSV_LIB_PATH=$PWD/build/ab/libdsv_$which.so; fi
-    python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline']['kernels']

@@ -8,7 +8,7 @@ ROOT=$PWD
 for i in $(seq $ROUNDS); do
   for which in r02 cur; do
     if [ $which = r02 ]; then cd $ROOT/build/r02tree; else cd $ROOT; fi
-    python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline $([ $which = cur ] && echo --full) 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline']['kernels']

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Closing run of a round on the GPU box: full GPU test suite, rocprofv3 passes of the final build
 # (kernel trace + stats, then PMC passes on their own), summaries for profiles/<round>/, final bench
-# line.  Everything lands under gpurun_out/ (progress lines on stdout as it goes).
+# line.  Logs and profiles land in the run's output folder; progress lines and the final bench line
+# (`bench.py --full`, then its summary) go to stdout.
 #   tools/gpu_round_check.sh r03
 #   (a failing or timed-out step ends the run: no further GPU step is started after it)
 R=${1:-r03}
@@ -24,5 +25,6 @@ python3 tools/summarize_prof.py gpurun_out/prof_round gpurun_out/${R}_final > gp
 cp profiles/pmc_latest.json gpurun_out/${R}_pmc_latest.json
 find gpurun_out/prof_round -name "*.db" -delete 2>/dev/null
 echo "[final] bench"
-python3 bench.py --steps 20 --warmup 3 > gpurun_out/${R}_bench_final.json 2> gpurun_out/${R}_bench_final.err
-python3 tools/bench_summary.py gpurun_out/${R}_bench_final.json
+line=$(timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 3) || exit 1
+echo "$line"
+echo "$line" | python3 tools/bench_summary.py /dev/stdin

@@ -13,7 +13,7 @@ ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-double"
 mkdir -p $OUT
 step() { echo "[profile_bench] $1"; }
 step "rocprofv3 --kernel-trace --stats --output-format"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1   # incl. double / vargen / mixed kernels
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1   # incl. double / vargen / mixed kernels
 step "export DSV_SPLIT=0"
 export DSV_SPLIT=0
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_nosplit -- python3 $ARGS > $OUT/trace_nosplit.log 2>&1
@@ -33,7 +33,7 @@ rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_s
 step "rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"
 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv -d $OUT/pmc_tcc2 -- python3 $ARGS > $OUT/pmc_tcc2.log 2>&1 || true
 # the fused double kernel (roofline_double.traffic): the same two counters over a run that includes the double leg
-ARGS2="bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+ARGS2="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 step "rocprofv3 --pmc FETCH_SIZE (double leg)"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch2 -- python3 $ARGS2 > $OUT/pmc_fetch2.log 2>&1
 step "rocprofv3 --pmc WRITE_SIZE GRBM_GUI_ACTIVE (double leg)"

@@ -11,4 +11,4 @@ for a in "20 0 8 single" "22 0 5 single" "18 0 8 single" "16 0 8 single" "20 0 6
 done
 } > gpurun_out/rlc_probe_final.txt
 rocprofv3 --kernel-trace -d gpurun_out/rlc_prof -o rlc -- python3 tools/rlc_probe.py 20 0 4 > gpurun_out/rlc_prof.log 2>&1
-python bench.py > gpurun_out/r05_bench_final.json 2> gpurun_out/r05_bench_final.err
+python bench.py --full   # the closing bench line, on stdout
