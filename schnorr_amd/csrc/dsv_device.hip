@@ -1,8 +1,9 @@
 // dsv_device.hip — the device-pointer entry points of include/dsv.h: challenge hash, the three verify
 // schemes over affine inputs resident in HBM (`PublicKey::verify`, `PublicKeyDouble::verify`,
-// `PublicKeyVarGen::verify`, /root/reference/src/keys/public.rs:121-130, :222-244, :401-415), the second
-// stage alone, and mixed single + double batches (device-side split by kind).  The bodies
-// verify_*_on are what the host pipeline and the other units call per sub-batch.
+// `PublicKeyVarGen::verify`, /root/reference/src/keys/public.rs:121-130, :222-244, :401-415) over affine
+// points, projective points or Montgomery limbs, the second stage alone, and mixed single + double batches
+// (device-side split by kind).  The body verify_on is what the host pipeline and the other units call per
+// sub-batch.
 #include "dsv_host.h"
 
 namespace dsvh {
@@ -32,60 +33,51 @@ hipEvent_t prep_tables_beside_hash(Context& ctx, const void* PK_uv, const void* 
   }
   return lane->side_join;
 }
-// valid_in (may be null): per-item validity found by an earlier stage (normalisation, decompression);
-// the hash kernel folds it into the validity the verify kernel starts from
-int verify_single_on(Context& ctx, const void* u, const void* R_uv, const void* PK_uv, const void* m,
-                     size_t n, void* ok, void* workspace, hipStream_t stream, const uint8_t* valid_in) {
-  const uint8_t *pu = (const uint8_t*)u, *pR = (const uint8_t*)R_uv, *pPK = (const uint8_t*)PK_uv,
-                *pm = (const uint8_t*)m;
+void launch_hash(const Items& in, size_t n, uint8_t* c, uint8_t* valid, hipStream_t s, const uint8_t* valid_in) {
+  launch_challenge(in.Rp() != nullptr, in.R(), in.Rp(), in.m, n, c, valid, s, valid_in);
+}
+void launch_verify(const Context& ctx, const Items& in, const uint8_t* c, const uint8_t* valid, size_t n,
+                   uint8_t* ok, u32* tables, hipStream_t s, bool prebuilt, const u32* gate) {
+  if (in.scheme == 0)
+    launch_verify_fixed(ctx, false, in.u, c, in.PK(), in.R(), 0, valid, n, ok, tables, s, prebuilt, gate);
+  else if (in.scheme == 1)
+    launch_verify_fixed_double(ctx, in.u, c, in.PK(), in.R(), in.PKp(), in.Rp(), valid, n, ok, tables, s, prebuilt,
+                               gate);
+  else  // (no tables to prebuild: k_vargen builds its own)
+    launch_verify_var(in.u, c, in.PK(), in.Gen(), in.R(), valid, n, ok, tables, s, gate);
+}
+int verify_on(Context& ctx, const Items& in, size_t n, void* ok, void* workspace, hipStream_t stream,
+              const uint8_t* valid_in) {
   uint8_t* pok = (uint8_t*)ok;
   Context* cp = &ctx;
-  return run_split(ctx, n, workspace, stream,
-                   [=](size_t off, size_t cnt, const Workspace& w, hipStream_t s) {
+  return run_split(ctx, n, workspace, stream, [=](size_t off, size_t cnt, const Workspace& w, hipStream_t s) {
+    const Items at = in.at(off);
     // (only for an unsplit call: inside run_split's loop the lane lock is held and cnt > 2^14 anyway,
     //  except for a short last part, which simply builds its tables in the kernel)
-    hipEvent_t ready = cnt == n ? prep_tables_beside_hash(*cp, pPK + 64 * off, pR + 64 * off, cnt, w.tables, s)
-                                : nullptr;
-    launch_challenge(false, pR + 64 * off, (const uint8_t*)nullptr, pm + 32 * off, cnt, w.c, w.valid, s,
-                     valid_in ? valid_in + off : nullptr);
+    hipEvent_t ready = layout(in.scheme).fixed && cnt == n
+                           ? prep_tables_beside_hash(*cp, at.PK(), at.R(), cnt, w.tables, s)
+                           : nullptr;
+    launch_hash(at, cnt, w.c, w.valid, s, valid_in ? valid_in + off : nullptr);
     if (ready && hipStreamWaitEvent(s, ready, 0) != hipSuccess) return;  // (surfaces through hipGetLastError)
-    launch_verify_fixed(*cp, false, pu + 32 * off, w.c, pPK + 64 * off, pR + 64 * off, 0, w.valid,
-                        cnt, pok + off, w.tables, s, ready != nullptr);
+    launch_verify(*cp, at, w.c, w.valid, cnt, pok + off, w.tables, s, ready != nullptr);
   });
 }
-int verify_double_on(Context& ctx, const void* u, const void* R_uv, const void* Rp_uv,
-                     const void* PK_uv, const void* PKp_uv, const void* m, size_t n, void* ok,
-                     void* workspace, hipStream_t stream, const uint8_t* valid_in) {
-  const uint8_t *pu = (const uint8_t*)u, *pR = (const uint8_t*)R_uv, *pRp = (const uint8_t*)Rp_uv,
-                *pPK = (const uint8_t*)PK_uv, *pPKp = (const uint8_t*)PKp_uv, *pm = (const uint8_t*)m;
-  uint8_t* pok = (uint8_t*)ok;
-  Context* cp = &ctx;
-  return run_split(ctx, n, workspace, stream,
-                   [=](size_t off, size_t cnt, const Workspace& w, hipStream_t s) {
-    // (only for an unsplit call: inside run_split's loop the lane lock is held and cnt > 2^14 anyway,
-    //  except for a short last part, which simply builds its tables in the kernel)
-    hipEvent_t ready = cnt == n ? prep_tables_beside_hash(*cp, pPK + 64 * off, pR + 64 * off, cnt, w.tables, s)
-                                : nullptr;
-    launch_challenge(true, pR + 64 * off, pRp + 64 * off, pm + 32 * off, cnt, w.c, w.valid, s,
-                     valid_in ? valid_in + off : nullptr);
-    if (ready && hipStreamWaitEvent(s, ready, 0) != hipSuccess) return;
-    launch_verify_fixed_double(*cp, pu + 32 * off, w.c, pPK + 64 * off, pR + 64 * off,
-                               pPKp + 64 * off, pRp + 64 * off, w.valid, cnt, pok + off, w.tables, s,
-                               ready != nullptr);
-  });
-}
-int verify_vargen_on(Context& ctx, const void* u, const void* R_uv, const void* PK_uv,
-                     const void* Gen_uv, const void* m, size_t n, void* ok, void* workspace,
-                     hipStream_t stream, const uint8_t* valid_in) {
-  const uint8_t *pu = (const uint8_t*)u, *pR = (const uint8_t*)R_uv, *pPK = (const uint8_t*)PK_uv,
-                *pG = (const uint8_t*)Gen_uv, *pm = (const uint8_t*)m;
-  uint8_t* pok = (uint8_t*)ok;
-  return run_split(ctx, n, workspace, stream,
-                   [=](size_t off, size_t cnt, const Workspace& w, hipStream_t s) {
-    launch_challenge(false, pR + 64 * off, (const uint8_t*)nullptr, pm + 32 * off, cnt, w.c, w.valid, s,
-                     valid_in ? valid_in + off : nullptr);
-    launch_verify_var(pu + 32 * off, (const uint8_t*)w.c, pPK + 64 * off, pG + 64 * off, pR + 64 * off, (const uint8_t*)w.valid, cnt, pok + off, w.tables, s);
-  });
+void normalize_on(int scheme, const uint8_t* const* in, uint8_t* const* out, size_t n, uint8_t* valid, u32* prefix,
+                  hipStream_t s, const uint8_t* u_mont, const uint8_t* m_mont, uint8_t* u_out, uint8_t* m_out,
+                  int per_lane, int block) {
+  const int np = layout(scheme).points;
+  NormalizeArgs a = {};
+  for (int k = 0; k < np; k++) {
+    a.in[k] = in[k];
+    a.out[k] = out[k];
+  }
+  if (u_mont) {
+    a.u_mont = u_mont;
+    a.m_mont = m_mont;
+    a.u_out = u_out;
+    a.m_out = m_out;
+  }
+  launch_normalize_uvz(a, np, n, valid, prefix, s, per_lane, block);
 }
 int decompress_on(Context& ctx, const void* in, size_t in_stride, size_t n, void* out_uv, void* ok,
                   int accumulate, hipStream_t stream) {
@@ -95,6 +87,54 @@ int decompress_on(Context& ctx, const void* in, size_t in_stride, size_t n, void
   HIP_TRY(hipGetLastError());
   return DSV_OK;
 }
+
+// ---- projective inputs / Montgomery limbs resident in HBM (dsv_host.hip: what they are) ----------
+namespace {
+struct ExtWs {
+  uint8_t* pts[4];
+  uint8_t* valid;
+  u32* prefix;
+  void* vws;
+};
+size_t ext_workspace_bytes(size_t n) {
+  return 4 * align_up(n * 64, 256) + align_up(n, 256) + align_up(normalize_prefix_bytes(n, 4), 256) +
+         align_up(dsv_workspace_bytes(n), 256) + 256;
+}
+size_t mont_workspace_bytes(size_t n) { return 2 * align_up(n * 32, 256) + ext_workspace_bytes(n); }
+ExtWs carve_ext(void* ws, size_t n) {
+  Stager st(static_cast<uint8_t*>(ws));
+  ExtWs w;
+  for (int k = 0; k < 4; k++) w.pts[k] = st.take(n * 64);
+  w.valid = st.take(n);
+  w.prefix = reinterpret_cast<u32*>(st.take(normalize_prefix_bytes(n, 4)));
+  w.vws = st.take(dsv_workspace_bytes(n));
+  return w;
+}
+// in.pt: the scheme's points, each n x 96 B (u || v || z).  kMont: in.u / in.m are Montgomery limbs,
+// converted by the normalisation kernel into two arrays carved in front of the ext workspace
+int verify_ext_on(Context& ctx, int form, const Items& in, size_t n, void* ok, void* workspace, hipStream_t s) {
+  Stager st(static_cast<uint8_t*>(workspace));
+  Items aff = in;
+  uint8_t *cu = nullptr, *cm = nullptr;
+  if (form == kMont) {
+    cu = st.take(n * 32), cm = st.take(n * 32);
+    aff.u = cu, aff.m = cm;
+  }
+  const ExtWs w = carve_ext(st.take(0), n);
+  normalize_on(in.scheme, in.pt, w.pts, n, w.valid, w.prefix, s, cu ? in.u : nullptr, in.m, cu, cm);
+  for (int k = 0; k < 4; k++) aff.pt[k] = in.pt[k] ? w.pts[k] : nullptr;
+  if (int rc = verify_on(ctx, aff, n, ok, w.vws, s, w.valid)) return rc;
+  HIP_TRY(hipGetLastError());
+  return DSV_OK;
+}
+// the verify entry points over device pointers: affine (u, points, m), projective or Montgomery limbs
+int verify_dev(int form, const Items& in, size_t n, void* ok, void* workspace, void* stream) {
+  if (n && (in.any_null() || !ok || !workspace)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  DSV_DEV_PROLOGUE(n, ok);
+  if (form == kAffine) return verify_on(ctx, in, n, ok, workspace, (hipStream_t)stream);
+  return verify_ext_on(ctx, form, in, n, ok, workspace, (hipStream_t)stream);
+}
+}  // namespace
 }  // namespace dsvh
 
 using namespace dsvh;
@@ -121,10 +161,48 @@ int dsv_challenge_double_dev(const void* R_uv, const void* Rp_uv, const void* m,
 
 int dsv_verify_single_dev(const void* u, const void* R_uv, const void* PK_uv, const void* m,
                           size_t n, void* ok, void* workspace, void* stream) {
-  if (n && (!u || !R_uv || !PK_uv || !m || !ok || !workspace))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_DEV_PROLOGUE(n, ok);
-  return verify_single_on(ctx, u, R_uv, PK_uv, m, n, ok, workspace, (hipStream_t)stream);
+  return verify_dev(kAffine, make_items(0, u, {R_uv, PK_uv}, m), n, ok, workspace, stream);
+}
+int dsv_verify_double_dev(const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
+                          const void* PKp_uv, const void* m, size_t n, void* ok, void* workspace,
+                          void* stream) {
+  return verify_dev(kAffine, make_items(1, u, {R_uv, Rp_uv, PK_uv, PKp_uv}, m), n, ok, workspace, stream);
+}
+int dsv_verify_vargen_dev(const void* u, const void* R_uv, const void* PK_uv, const void* Gen_uv,
+                          const void* m, size_t n, void* ok, void* workspace, void* stream) {
+  return verify_dev(kAffine, make_items(2, u, {R_uv, PK_uv, Gen_uv}, m), n, ok, workspace, stream);
+}
+
+// projective points (u || v || z, 96 B): the device does to_hash_inputs first
+size_t dsv_ext_workspace_bytes(size_t n) { return ext_workspace_bytes(n); }
+int dsv_verify_single_ext_dev(const void* u, const void* R_uvz, const void* PK_uvz, const void* m,
+                              size_t n, void* ok, void* workspace, void* stream) {
+  return verify_dev(kExt, make_items(0, u, {R_uvz, PK_uvz}, m), n, ok, workspace, stream);
+}
+int dsv_verify_double_ext_dev(const void* u, const void* R_uvz, const void* Rp_uvz, const void* PK_uvz,
+                              const void* PKp_uvz, const void* m, size_t n, void* ok, void* workspace,
+                              void* stream) {
+  return verify_dev(kExt, make_items(1, u, {R_uvz, Rp_uvz, PK_uvz, PKp_uvz}, m), n, ok, workspace, stream);
+}
+int dsv_verify_vargen_ext_dev(const void* u, const void* R_uvz, const void* PK_uvz, const void* Gen_uvz,
+                              const void* m, size_t n, void* ok, void* workspace, void* stream) {
+  return verify_dev(kExt, make_items(2, u, {R_uvz, PK_uvz, Gen_uvz}, m), n, ok, workspace, stream);
+}
+
+// Montgomery limbs (the Rust types' in-memory form) resident in HBM
+size_t dsv_mont_workspace_bytes(size_t n) { return mont_workspace_bytes(n); }
+int dsv_verify_single_mont_dev(const void* u, const void* R_uvz, const void* PK_uvz, const void* m,
+                               size_t n, void* ok, void* workspace, void* stream) {
+  return verify_dev(kMont, make_items(0, u, {R_uvz, PK_uvz}, m), n, ok, workspace, stream);
+}
+int dsv_verify_double_mont_dev(const void* u, const void* R_uvz, const void* Rp_uvz, const void* PK_uvz,
+                               const void* PKp_uvz, const void* m, size_t n, void* ok, void* workspace,
+                               void* stream) {
+  return verify_dev(kMont, make_items(1, u, {R_uvz, Rp_uvz, PK_uvz, PKp_uvz}, m), n, ok, workspace, stream);
+}
+int dsv_verify_vargen_mont_dev(const void* u, const void* R_uvz, const void* PK_uvz, const void* Gen_uvz,
+                               const void* m, size_t n, void* ok, void* workspace, void* stream) {
+  return verify_dev(kMont, make_items(2, u, {R_uvz, PK_uvz, Gen_uvz}, m), n, ok, workspace, stream);
 }
 
 // second stage alone (c and valid already computed): lets callers time / profile the dominant
@@ -153,23 +231,6 @@ int dsv_verify_core_double_dev(const void* u, const void* c, const void* valid, 
                              (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return DSV_OK;
-}
-
-int dsv_verify_double_dev(const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
-                          const void* PKp_uv, const void* m, size_t n, void* ok, void* workspace,
-                          void* stream) {
-  if (n && (!u || !R_uv || !Rp_uv || !PK_uv || !PKp_uv || !m || !ok || !workspace))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_DEV_PROLOGUE(n, ok);
-  return verify_double_on(ctx, u, R_uv, Rp_uv, PK_uv, PKp_uv, m, n, ok, workspace, (hipStream_t)stream);
-}
-
-int dsv_verify_vargen_dev(const void* u, const void* R_uv, const void* PK_uv, const void* Gen_uv,
-                          const void* m, size_t n, void* ok, void* workspace, void* stream) {
-  if (n && (!u || !R_uv || !PK_uv || !Gen_uv || !m || !ok || !workspace))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_DEV_PROLOGUE(n, ok);
-  return verify_vargen_on(ctx, u, R_uv, PK_uv, Gen_uv, m, n, ok, workspace, (hipStream_t)stream);
 }
 
 // ---- mixed batches: device-side split by kind ---------------------------------------------
@@ -291,16 +352,14 @@ int verify_mixed_dev(const void* kinds, const void* u, const void* R_uv, const v
   for (const Col& c : double_cols)
     if (int r = gather_on(c.src, n, c.bytes, idx_d, nd, totals + 1, c.dst, s)) return r;
   if (ns) {
-    if (int r = fast ? verify_rlc_on(ctx, 0, cu, cR, nullptr, cPK, nullptr, nullptr, cm, ns, oks, vws, s, 0, vt.dev)
-                     : verify_single_on(ctx, cu, cR, cPK, cm, ns, oks, vws, s))
-      return r;
+    const Items in = make_items(0, cu, {cR, cPK}, cm);
+    if (int r = fast ? verify_rlc_on(ctx, in, ns, oks, vws, s, 0, vt.dev) : verify_on(ctx, in, ns, oks, vws, s)) return r;
     launch_scatter_bytes(oks, idx_s, ns, totals, (uint8_t*)ok, n, s);
   }
   if (nd) {
-    if (int r = fast ? verify_rlc_on(ctx, 1, cu + ns * 32, cR + ns * 64, cRp, cPK + ns * 64, cPKp, nullptr,
-                                     cm + ns * 32, nd, okd, vws, s, 0, vt.dev, /*and_into*/ ns != 0)
-                     : verify_double_on(ctx, cu + ns * 32, cR + ns * 64, cRp, cPK + ns * 64, cPKp, cm + ns * 32, nd,
-                                        okd, vws, s))
+    const Items in = make_items(1, cu + ns * 32, {cR + ns * 64, cRp, cPK + ns * 64, cPKp}, cm + ns * 32);
+    if (int r = fast ? verify_rlc_on(ctx, in, nd, okd, vws, s, 0, vt.dev, /*and_into*/ ns != 0)
+                     : verify_on(ctx, in, nd, okd, vws, s))
       return r;
     launch_scatter_bytes(okd, idx_d, nd, totals + 1, (uint8_t*)ok, n, s);
   }

@@ -2,7 +2,8 @@
 // error channel, workspace carving, the sub-batch scheduler of the device-pointer entry points and the
 // bodies that more than one unit calls.  The units (one hipcc job each, build.py: UNITS):
 //   dsv_context.hip   contexts, dsv_init / dsv_shutdown, streams and staging of a device
-//   dsv_device.hip    device-pointer entry points: challenge, verify (affine), core, mixed batches
+//   dsv_device.hip    device-pointer entry points: challenge, verify (affine, projective, Montgomery
+//                     limbs), core, mixed batches
 //   dsv_host.hip      host-pointer entry points: affine / projective / Montgomery-limb / typed-object
 //                     columns, *_multi, submit / wait
 //   dsv_wire.hip      serialized records (decode + verify), compress / decompress
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -306,20 +308,79 @@ int run_split(Context& ctx, size_t n, void* workspace, hipStream_t user, Part pa
   DSV_ON_DEVICE(ctx)
 
 
+// ---- the layout of one scheme's inputs: the only host code that knows the point order -------------
+// Canonical order (every entry point's argument order, every arena and workspace):
+//   scheme 0 single (R, PK), 1 double (R, R', PK, PK'), 2 var-generator (R, PK, Gen).
+// Wire records: the signature is u then its nonce points, the key record its key points (32 B each,
+// compressed), so the canonical order is the signature's points followed by the key record's.
+struct SchemeLayout {
+  int points;                  // points per item
+  size_t sig_bytes, pk_bytes;  // wire records
+  int R, Rp, PK, PKp, Gen;     // slot in the canonical order, -1: the scheme has no such point
+  bool fixed;                  // the fixed-generator kernels (k_verify / k_quad), else k_vargen
+};
+constexpr SchemeLayout kSchemes[3] = {
+    {2, 64, 32, 0, -1, 1, -1, -1, true},
+    {4, 96, 64, 0, 1, 2, 3, -1, true},
+    {3, 64, 64, 0, -1, 1, -1, 2, false},
+};
+inline const SchemeLayout& layout(int scheme) { return kSchemes[scheme]; }
+// One call's items: u (32 B), the points in canonical order, m (32 B) per item; pt_bytes apart per
+// item (64: affine, 96: projective / Montgomery limbs).  Unused slots are null and stay null.
+struct Items {
+  int scheme = 0;
+  const uint8_t* u = nullptr;
+  const uint8_t* pt[4] = {};
+  const uint8_t* m = nullptr;
+  Items at(size_t off, size_t pt_bytes = 64) const {
+    Items r = *this;
+    r.u = u + 32 * off;
+    for (int k = 0; k < layout(scheme).points; k++) r.pt[k] = pt[k] + pt_bytes * off;
+    r.m = m ? m + 32 * off : nullptr;
+    return r;
+  }
+  const uint8_t* slot(int k) const { return k < 0 ? nullptr : pt[k]; }
+  const uint8_t* R() const { return slot(layout(scheme).R); }
+  const uint8_t* Rp() const { return slot(layout(scheme).Rp); }
+  const uint8_t* PK() const { return slot(layout(scheme).PK); }
+  const uint8_t* PKp() const { return slot(layout(scheme).PKp); }
+  const uint8_t* Gen() const { return slot(layout(scheme).Gen); }
+  bool any_null() const {
+    bool r = !u || !m;
+    for (int k = 0; k < layout(scheme).points; k++) r = r || !pt[k];
+    return r;
+  }
+};
+// the items of an entry point's arguments (points in canonical order)
+inline Items make_items(int scheme, const void* u, std::initializer_list<const void*> pts, const void* m) {
+  Items in{scheme, static_cast<const uint8_t*>(u)};
+  int k = 0;
+  for (const void* p : pts) in.pt[k++] = static_cast<const uint8_t*>(p);
+  in.m = static_cast<const uint8_t*>(m);
+  return in;
+}
+
 // bodies shared by the device-pointer entry points and the host pipeline (context resolved); dsv_device.hip
 extern thread_local bool t_pipeline_part;  // run_pipelined, several chunks: its four streams are all there is
 extern thread_local size_t t_chunk_first;  // run_pipelined: first item of the chunk being enqueued (prep / part
                                            // callbacks that place their output by item number: the fast accept)
-// valid_in (may be null): per-item validity found by an earlier stage (normalisation, decompression);
-// the hash kernel folds it into the validity the verify kernel starts from
-int verify_single_on(Context& ctx, const void* u, const void* R_uv, const void* PK_uv, const void* m,
-                     size_t n, void* ok, void* workspace, hipStream_t stream, const uint8_t* valid_in = nullptr);
-int verify_double_on(Context& ctx, const void* u, const void* R_uv, const void* Rp_uv,
-                     const void* PK_uv, const void* PKp_uv, const void* m, size_t n, void* ok,
-                     void* workspace, hipStream_t stream, const uint8_t* valid_in = nullptr);
-int verify_vargen_on(Context& ctx, const void* u, const void* R_uv, const void* PK_uv,
-                     const void* Gen_uv, const void* m, size_t n, void* ok, void* workspace,
-                     hipStream_t stream, const uint8_t* valid_in = nullptr);
+// the challenge hash of the items (R, R' and m): c, valid; valid_in (may be null) is AND-ed into valid
+void launch_hash(const Items& in, size_t n, uint8_t* c, uint8_t* valid, hipStream_t s, const uint8_t* valid_in = nullptr);
+// the per-signature kernel of the scheme from the challenges c / valid: launch_verify_fixed,
+// launch_verify_fixed_double or launch_verify_var (prebuilt: the window tables of (PK, R) are built already)
+void launch_verify(const Context& ctx, const Items& in, const uint8_t* c, const uint8_t* valid, size_t n,
+                   uint8_t* ok, u32* tables, hipStream_t s, bool prebuilt = false, const u32* gate = nullptr);
+// hash + verify of affine items, sub-batched by run_split.  valid_in (may be null): per-item validity found
+// by an earlier stage (normalisation, decompression); the hash kernel folds it into the validity the verify
+// kernel starts from
+int verify_on(Context& ctx, const Items& in, size_t n, void* ok, void* workspace, hipStream_t stream,
+              const uint8_t* valid_in = nullptr);
+// to_hash_inputs of the scheme's points: in[k] (u, v, z: 96 B per item) -> out[k] (u, v: 64 B), canonical
+// order; with u_mont / m_mont (Montgomery limbs) the same launch converts the scalars into u_out / m_out.
+// per_lane / block: the launch shape (0: the kernel's defaults)
+void normalize_on(int scheme, const uint8_t* const* in, uint8_t* const* out, size_t n, uint8_t* valid, u32* prefix,
+                  hipStream_t s, const uint8_t* u_mont = nullptr, const uint8_t* m_mont = nullptr,
+                  uint8_t* u_out = nullptr, uint8_t* m_out = nullptr, int per_lane = 0, int block = 0);
 int decompress_on(Context& ctx, const void* in, size_t in_stride, size_t n, void* out_uv, void* ok,
                   int accumulate, hipStream_t stream);
 
@@ -328,11 +389,9 @@ struct RlcStaged {  // a host call whose bucket pass over items [0, boundary) wa
   ChaChaKey key;
   size_t boundary;
 };
-// scheme 0 single (R, PK), 1 double (R, R', PK, PK'), 2 var-generator (R, PK, Gen): unused pointers null
 // Enqueue-only; *accepted_dev (device-accessible memory, may be null) is written by a kernel at the end.
-int verify_rlc_on(Context& ctx, int scheme, const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
-                  const void* PKp_uv, const void* Gen_uv, const void* m, size_t n, void* ok, void* workspace,
-                  hipStream_t s, int window_bits, u32* accepted_dev, bool and_into = false, bool have_challenges = false,
+int verify_rlc_on(Context& ctx, const Items& in, size_t n, void* ok, void* workspace, hipStream_t s, int window_bits,
+                  u32* accepted_dev, bool and_into = false, bool have_challenges = false,
                   const uint8_t* valid_in = nullptr, const RlcStaged* staged = nullptr);
 // where a call's verdict goes: `dev` is what the verdict kernel writes; a caller's pageable `int* accepted`
 // gets a pinned slot of the context and the call waits for the stream at its end (rlc_verdict_wait)
@@ -365,15 +424,34 @@ int rlc_history(Context& ctx);  // the device's history counter (-1: no pinned m
 // per-item scratch of the host pipeline's whole-chunk preprocessing: projective inputs / Montgomery limbs
 constexpr size_t kExtItemBytes = 4 * 64 + 1 + 4 * kLimbs * 4 + 1;
 constexpr size_t kMontItemBytes = kExtItemBytes + 64;
-// columns of typed objects (dsv_host.hip)
-int check_cols(int kind, const dsv_column* cols, size_t n, const uint8_t* ok);
-int verify_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, bool multi);
+// host batches (dsv_host.hip): affine arrays, projective points, Montgomery limbs
+enum Form { kAffine, kExt, kMont };
+inline size_t form_pt_bytes(int form) { return form == kAffine ? 64 : 96; }
+// argument checks of a column batch (typed objects; the dense forms): n, then every column's pointer and stride
+int check_cols(int scheme, const dsv_column* cols, size_t n, const uint8_t* ok, int form);
+// cols: u, the scheme's points, m; multi: sharded over every initialised device
+int verify_host_cols(int scheme, int form, const dsv_column* cols, size_t n, uint8_t* ok, bool multi);
 
-// serialized records (dsv_wire.hip)
+// serialized records (dsv_wire.hip): the decoder's outputs u, R, R', the key record's points P0, P1, valid
+// (this order: dsv_wire_workspace_bytes)
 struct WireWs {
   uint8_t *u, *R, *Rp, *P0, *P1, *valid;
+  Items items(int scheme, const void* m) const {  // the signature's points, then the key record's
+    const uint8_t* sig_pts[2] = {R, Rp};
+    const uint8_t* pk_pts[2] = {P0, P1};
+    const int ns = (int)(layout(scheme).sig_bytes / 32) - 1;
+    Items in{scheme, u};
+    for (int k = 0; k < layout(scheme).points; k++) in.pt[k] = k < ns ? sig_pts[k] : pk_pts[k - ns];
+    in.m = static_cast<const uint8_t*>(m);
+    return in;
+  }
 };
-int verify_wire(Context& ctx, int kind, const uint8_t* sig, const uint8_t* pk, const uint8_t* m,
+WireWs carve_wire(Stager& x, size_t n);
+// n records -> out.u, out.pt[] (device memory the decoder writes) and valid; the decompress verdicts
+// accumulate from the second point on
+int decode_wire(Context& ctx, int scheme, const uint8_t* sig, const uint8_t* pk, size_t n, const Items& out,
+                uint8_t* valid, hipStream_t st);
+int verify_wire(Context& ctx, int scheme, const uint8_t* sig, const uint8_t* pk, const uint8_t* m,
                 size_t n, uint8_t* ok);
 
 }  // namespace dsvh

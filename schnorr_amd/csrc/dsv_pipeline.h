@@ -37,6 +37,9 @@ struct HostIn {
   size_t bytes;       // per item
   size_t stride = 0;  // distance between items in the caller's memory; 0 = `bytes` (a dense array)
 };
+constexpr size_t kMaxHostIn = 6;  // inputs of one call: u, four points, m
+// the pipeline's inputs for items [off, ..) of a column batch (u, the scheme's points, m); returns their count
+size_t column_inputs(int scheme, int form, const dsv_column* cols, size_t off, HostIn* ins);
 // Chunk sizes double from 2^15 up to 2^18 items: the GPU starts after ~0.3 ms of staging, every
 // gather runs under the previous (half as long) chunk's kernels, and from the fourth chunk on the
 // transfers are long enough to run near the link rate (r03, same box, 2^20 items: chunks
@@ -66,6 +69,15 @@ struct Staged {
   const uint8_t* p[8] = {};
   size_t bytes[8] = {};
   const uint8_t* valid = nullptr;
+  // sub-batch `off` of a chunk staged as u, the scheme's points (affine), m
+  Items items(int scheme, size_t off) const {
+    Items in{scheme};
+    in.u = p[0] + off * bytes[0];
+    const int np = layout(scheme).points;
+    for (int k = 0; k < np; k++) in.pt[k] = p[1 + k] + off * bytes[1 + k];
+    in.m = p[1 + np] + off * bytes[1 + np];
+    return in;
+  }
 };
 struct NoPrep {};
 //   prep(dev_ptrs, count, scratch, stream, staged)  [or NoPrep{}: the chunk is used as transferred]:
@@ -81,9 +93,10 @@ struct NoPrep {};
 //   part(staged, offset, count, dok, ws, extra, stream): one sub-batch; `extra`: scratch of
 //     extra_item_bytes per item behind the lane's verify workspace (the wire path decompresses per
 //     sub-batch: full-occupancy kernels, no reason to serialise a chunk's worth on one lane).
-template <size_t NIN, class Prep, class Part>
-int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n, size_t prep_item_bytes,
+template <class Prep, class Part>
+int run_pipelined(Context& ctx, const HostIn* ins, size_t nin, uint8_t* ok, size_t n, size_t prep_item_bytes,
                   size_t extra_item_bytes, Prep prep, Part part, unsigned flags = 0) {
+  if (nin == 0 || nin > kMaxHostIn) return fail(DSV_ERR_INVALID_ARGUMENT, "host pipeline: %zu inputs", nin);
   const bool heavy = (flags & kPipeHeavy) != 0, no_verdicts = (flags & kPipeNoVerdicts) != 0;
   constexpr bool has_prep = !std::is_same<Prep, NoPrep>::value;
   const bool small = n <= kPipeSmallCall;  // transfer, kernels and verdicts on ONE stream, a work area of its own
@@ -102,7 +115,7 @@ int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n,
   for (size_t c : chunks) chunk = c > chunk ? c : chunk;
   // slot capacity: offsets of the LARGEST chunk (a shorter chunk packs its arrays tighter, see below)
   size_t cap_off = 0;
-  for (size_t k = 0; k < NIN; k++) cap_off += align_up(chunk * ins[k].bytes, 256);
+  for (size_t k = 0; k < nin; k++) cap_off += align_up(chunk * ins[k].bytes, 256);
   const size_t host_need = cap_off + align_up(chunk, 256);
   // chunks in flight: three (r05, one-shot calls of 2^16-item chunks: six slots are ~1 ms per 2^20
   // SLOWER than three — with the host far ahead every chunk's preprocessing kernel is resident at the
@@ -145,7 +158,7 @@ int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n,
   // enqueued (its kernels and verdict copy are in the streams), then drained (verdicts delivered)
   struct Held {
     size_t first = 0, cnt = 0, ok_off = 0;
-    size_t in_off[NIN + 1] = {};
+    size_t in_off[kMaxHostIn + 1] = {};
     bool enqueued = false;
     int parts_on[2] = {0, 0};  // its sub-batches per compute lane
   } held[kPipeSlots];
@@ -238,13 +251,13 @@ int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n,
     t_drain += t1 - t0;
     uint8_t* host = slot.host;
     h.in_off[0] = 0;  // offsets inside the slot for THIS chunk, the same on both sides
-    for (size_t k = 0; k < NIN; k++) h.in_off[k + 1] = h.in_off[k] + align_up(cnt * ins[k].bytes, 256);
-    h.ok_off = h.in_off[NIN];
+    for (size_t k = 0; k < nin; k++) h.in_off[k + 1] = h.in_off[k] + align_up(cnt * ins[k].bytes, 256);
+    h.ok_off = h.in_off[nin];
     size_t bytes = 0;
-    for (size_t k = 0; k < NIN; k++) bytes += cnt * ins[k].bytes;
+    for (size_t k = 0; k < nin; k++) bytes += cnt * ins[k].bytes;
     const int T = bytes >= ((size_t)1 << 20) ? host_copy_threads() : 1;
     pipe.copiers.run(T, [&](int t, int nt) {
-      for (size_t k = 0; k < NIN; k++) {
+      for (size_t k = 0; k < nin; k++) {
         if (ins[k].stride && ins[k].stride != ins[k].bytes) {  // one field out of every object
           const size_t lo = cnt * (size_t)t / (size_t)nt, hi = cnt * (size_t)(t + 1) / (size_t)nt;
           copy_strided(host + h.in_off[k] + lo * ins[k].bytes, ins[k].p + (first + lo) * ins[k].stride,
@@ -266,7 +279,7 @@ int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n,
     // 1024-signature call), everything else on the shared transfer stream
     hipStream_t s_in = small ? ctx.pipe_small : ctx.pipe_in;
     std::lock_guard<std::mutex> enq(ctx.enq_mu);  // (record + later waits on ev_in stay paired)
-    if (hipMemcpyAsync(slot.stage, host, h.in_off[NIN - 1] + cnt * ins[NIN - 1].bytes, hipMemcpyHostToDevice, s_in) != hipSuccess ||
+    if (hipMemcpyAsync(slot.stage, host, h.in_off[nin - 1] + cnt * ins[nin - 1].bytes, hipMemcpyHostToDevice, s_in) != hipSuccess ||
         (!small && hipEventRecord(slot.ev_in, s_in) != hipSuccess))
       return fail(DSV_ERR_HIP, "transfer to the device failed: %s", hipGetErrorString(hipGetLastError()));
     return DSV_OK;
@@ -315,15 +328,15 @@ int run_pipelined(Context& ctx, const HostIn (&ins)[NIN], uint8_t* ok, size_t n,
         sp = pre_stream ? ctx.pipe_pre : ctx.pipe_lane[prep_lane];
         if (hipStreamWaitEvent(sp, slot.ev_in, 0) != hipSuccess) return fail(DSV_ERR_HIP, "hipStreamWaitEvent failed");
       }
-      const void* dptr[NIN];
-      for (size_t j = 0; j < NIN; j++) dptr[j] = dev + h.in_off[j];
+      const void* dptr[kMaxHostIn];
+      for (size_t j = 0; j < nin; j++) dptr[j] = dev + h.in_off[j];
       Stager scratch(slot.prep);
       if (int r = prep(dptr, cnt, scratch, sp, sg)) return r;
       if (!small && hipEventRecord(slot.ev_pre, sp) != hipSuccess) return fail(DSV_ERR_HIP, "hipEventRecord failed");
       if (prep_lane >= 0) used[prep_lane] = true;  // (in order behind the transfer already)
     } else {
       (void)prep;
-      for (size_t j = 0; j < NIN; j++) {
+      for (size_t j = 0; j < nin; j++) {
         sg.p[j] = dev + h.in_off[j];
         sg.bytes[j] = ins[j].bytes;
       }

@@ -128,6 +128,11 @@ RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups) {
   RlcPlan probe = rlc_plan(scheme, cnt, window_bits ? window_bits : 8, groups, align);
   return rlc_plan(scheme, cnt, window_bits ? window_bits : rlc_default_bits(probe.sub), groups, align);
 }
+int check_rlc_bits(int window_bits) {
+  if (window_bits && !rlc_bits_ok(window_bits))
+    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16");
+  return DSV_OK;
+}
 int rlc_random_key(ChaChaKey& key) {
   uint8_t* p = reinterpret_cast<uint8_t*>(key.w);
   size_t have = 0;
@@ -203,11 +208,19 @@ int rlc_verdict_wait(const RlcVerdictTarget& t, hipStream_t s) {
 }
 }  // namespace dsvh
 namespace {
+// the aggregate's view of a group's items and their challenges
+RlcInputs rlc_inputs(const Items& in, const uint8_t* c, const uint8_t* valid) {
+  RlcInputs r = {};
+  r.u = in.u, r.c = c, r.valid = valid;
+  r.pk[0] = in.PK(), r.r[0] = in.R();
+  r.pk[1] = in.PKp(), r.r[1] = in.Rp();  // (double)
+  r.gen = in.Gen();                       // (var-generator)
+  return r;
+}
 // one call's arguments, as the pieces below need them
 struct RlcCall {
   Context& ctx;
-  int scheme;  // 0 single (R, PK), 1 double (R, R', PK, PK'), 2 var-generator (R, PK, Gen): unused pointers null
-  const uint8_t *u, *R, *Rp, *PK, *PKp, *G, *m;
+  Items in;
   uint8_t* ok;
   void* workspace;
   hipStream_t s;
@@ -226,20 +239,13 @@ void rlc_enqueue_sample(const RlcCall& c, const RlcCarve& cv, const ChaChaKey& k
   const size_t at = off + (size_t)(key.w[7] % (u32)((cnt - sn) / 64 + 1)) * 64;  // (the key's last word: no weight uses it)
   const size_t rel = at - off;
   u32* tables = carve(cv.sample_ws, sn).tables;
-  if (c.scheme == 0)
-    launch_verify_fixed(c.ctx, false, c.u + 32 * at, cv.w.c + 32 * rel, c.PK + 64 * at, c.R + 64 * at, 0, cv.w.valid + rel, sn,
-                        cv.sample_ok, tables, c.s);
-  else if (c.scheme == 1)
-    launch_verify_fixed_double(c.ctx, c.u + 32 * at, cv.w.c + 32 * rel, c.PK + 64 * at, c.R + 64 * at, c.PKp + 64 * at,
-                               c.Rp + 64 * at, cv.w.valid + rel, sn, cv.sample_ok, tables, c.s);
-  else  // (one lane per signature beyond 2^13 items, sixteen below: ~0.4 ms for the sample)
-    launch_verify_var(c.u + 32 * at, cv.w.c + 32 * rel, c.PK + 64 * at, c.G + 64 * at, c.R + 64 * at, cv.w.valid + rel, sn,
-                      cv.sample_ok, tables, c.s);
+  const Items in = c.in.at(at);
+  // (var-generator: one lane per signature beyond 2^13 items, sixteen below: ~0.4 ms for the sample)
+  launch_verify(c.ctx, in, cv.w.c + 32 * rel, cv.w.valid + rel, sn, cv.sample_ok, tables, c.s);
   // a WRONG item counts, a malformed one does not (`valid` covers what the hash reads — R, R', m; u and
   // the keys are range-checked here as the verify kernel does)
-  launch_rlc_sample_decide(cv.sample_ok, cv.w.valid + rel, c.u + 32 * at, c.PK + 64 * at,
-                           c.scheme == 0 ? (const uint8_t*)nullptr : (c.scheme == 1 ? c.PKp : c.G) + 64 * at, 0, sn, cv.b.flags,
-                           c.s);
+  launch_rlc_sample_decide(cv.sample_ok, cv.w.valid + rel, in.u, in.PK(), in.PKp() ? in.PKp() : in.Gen(), 0, sn,
+                           cv.b.flags, c.s);
 }
 // The per-signature kernels of the group at `off`, from the challenges already in the workspace (run_split
 // carves it the same way), each launch gated by its sub-group's flag words in `gflags`: no work where the
@@ -257,16 +263,7 @@ int rlc_enqueue_fallback(const RlcCall& c, const Workspace& w0, const u32* gflag
       size_t take = (g + 1) * sub - (o + done);
       if (take > part - done) take = part - done;
       const u32* gate = gflags + 4 + 4 * g;
-      if (call.scheme == 0)
-        launch_verify_fixed(*cp, false, call.u + 32 * at, w.c + 32 * done, call.PK + 64 * at, call.R + 64 * at, 0, w.valid + done,
-                            take, call.ok + at, w.tables, ps, false, gate);
-      else if (call.scheme == 1)
-        launch_verify_fixed_double(*cp, call.u + 32 * at, w.c + 32 * done, call.PK + 64 * at, call.R + 64 * at,
-                                   call.PKp + 64 * at, call.Rp + 64 * at, w.valid + done, take, call.ok + at, w.tables, ps, false,
-                                   gate);
-      else
-        launch_verify_var(call.u + 32 * at, (const uint8_t*)w.c + 32 * done, call.PK + 64 * at, call.G + 64 * at,
-                          call.R + 64 * at, (const uint8_t*)w.valid + done, take, call.ok + at, w.tables, ps, gate);
+      launch_verify(*cp, call.in.at(at), w.c + 32 * done, w.valid + done, take, call.ok + at, w.tables, ps, false, gate);
       done += take;
     }
   };
@@ -284,7 +281,7 @@ int rlc_trace(const RlcCall& c, const u32* flags_area, const RlcVerdictArgs& va,
   for (u32 k = 0; k < va.ngroups; k++) {
     const RlcTraced& t = traced[k];
     if (!va.subs[k]) {
-      std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: too small for an aggregate, per-signature path\n", c.scheme,
+      std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: too small for an aggregate, per-signature path\n", c.in.scheme,
                    t.off, t.off + t.cnt);
       continue;
     }
@@ -292,14 +289,14 @@ int rlc_trace(const RlcCall& c, const u32* flags_area, const RlcVerdictArgs& va,
       const RlcPlan& pl = stage ? t.plan2 : t.plan;
       const u32* gf = f.data() + ((size_t)2 * k + stage) * kRlcGroupFlagWords;
       if (gf[0] && !stage)
-        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: a wrong item in the sample, no aggregate\n", c.scheme, t.off,
+        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: a wrong item in the sample, no aggregate\n", c.in.scheme, t.off,
                      t.off + t.cnt);
       if (gf[0] && stage)
-        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: second stage not needed\n", c.scheme, t.off, t.off + t.cnt);
+        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu: second stage not needed\n", c.in.scheme, t.off, t.off + t.cnt);
       for (u32 g = 0; g < pl.groups && !gf[0]; g++) {
         const u32* fl = gf + 4 + 4 * g;
         const size_t lo = t.off + (size_t)g * pl.sub, hi = lo + pl.sub < t.off + t.cnt ? lo + pl.sub : t.off + t.cnt;
-        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu c=%d %ssub-group %u/%u%s (history %u / %u): %s%s%s%s%s\n", c.scheme,
+        std::fprintf(stderr, "[dsv rlc] scheme %d items %zu..%zu c=%d %ssub-group %u/%u%s (history %u / %u): %s%s%s%s%s\n", c.in.scheme,
                      lo, hi, pl.c, t.plan2.groups ? (stage ? "second stage, " : "first stage, ") : "", g + 1, pl.groups,
                      t.sampled ? " sampled" : "", history, history_long,
                      fl[1] == 1 ? "" : "chain incomplete ", fl[0] & kRlcOffCurve ? "off-curve " : "",
@@ -314,12 +311,10 @@ int rlc_trace(const RlcCall& c, const u32* flags_area, const RlcVerdictArgs& va,
 namespace dsvh {
 // Enqueues everything on `s` and returns; *accepted_dev (device-accessible, may be null) = every group was
 // decided by its aggregates (and_into: ... AND what the word held: the second kind of a mixed batch).
-int verify_rlc_on(Context& ctx, int scheme, const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
-                  const void* PKp_uv, const void* Gen_uv, const void* m, size_t n, void* ok, void* workspace,
-                  hipStream_t s, int window_bits, u32* accepted_dev, bool and_into, bool have_challenges,
-                  const uint8_t* valid_in, const RlcStaged* staged) {
-  const RlcCall c{ctx, scheme, (const uint8_t*)u, (const uint8_t*)R_uv, (const uint8_t*)Rp_uv, (const uint8_t*)PK_uv,
-                  (const uint8_t*)PKp_uv, (const uint8_t*)Gen_uv, (const uint8_t*)m, (uint8_t*)ok, workspace, s};
+int verify_rlc_on(Context& ctx, const Items& items, size_t n, void* ok, void* workspace, hipStream_t s, int window_bits,
+                  u32* accepted_dev, bool and_into, bool have_challenges, const uint8_t* valid_in, const RlcStaged* staged) {
+  const int scheme = items.scheme;
+  const RlcCall c{ctx, items, (uint8_t*)ok, workspace, s};
   if (int r = ensure_rlc_pinned(ctx)) return r;
   const size_t group = rlc_group_items(n);
   static const bool trace = getenv("DSV_RLC_TRACE") != nullptr;  // why a group was (not) accepted: makes the call synchronous
@@ -340,17 +335,7 @@ int verify_rlc_on(Context& ctx, int scheme, const void* u, const void* R_uv, con
       // too small for an aggregate to pay: the per-signature entry point as it is
       va.subs[k] = 0;
       traced[k] = RlcTraced{off, cnt, RlcPlan{}, RlcPlan{}, false};
-      int r;
-      const uint8_t* vin = valid_in ? valid_in + off : nullptr;
-      if (scheme == 0)
-        r = verify_single_on(ctx, c.u + 32 * off, c.R + 64 * off, c.PK + 64 * off, c.m + 32 * off, cnt, c.ok + off, workspace, s, vin);
-      else if (scheme == 1)
-        r = verify_double_on(ctx, c.u + 32 * off, c.R + 64 * off, c.Rp + 64 * off, c.PK + 64 * off, c.PKp + 64 * off,
-                             c.m + 32 * off, cnt, c.ok + off, workspace, s, vin);
-      else
-        r = verify_vargen_on(ctx, c.u + 32 * off, c.R + 64 * off, c.PK + 64 * off, c.G + 64 * off, c.m + 32 * off, cnt,
-                             c.ok + off, workspace, s, vin);
-      if (r) return r;
+      if (int r = verify_on(ctx, items.at(off), cnt, c.ok + off, workspace, s, valid_in ? valid_in + off : nullptr)) return r;
       continue;
     }
     // how this group runs (file header): plain, split (sub-groups + sample) or guarded (two stages)
@@ -375,20 +360,14 @@ int verify_rlc_on(Context& ctx, int scheme, const void* u, const void* R_uv, con
     ChaChaKey key;
     if (staged) key = staged->key;  // (one group: the bucket pass of its first items is on the stream already)
     else if (int r = rlc_random_key(key)) return r;
-    const bool do_sample = !window_bits && sample_on && (ctx.quad || scheme == 2) && history > 0 && !G2;
+    const bool do_sample = !window_bits && sample_on && (ctx.quad || !layout(scheme).fixed) && history > 0 && !G2;
     traced[k] = RlcTraced{off, cnt, plan, RlcPlan{}, do_sample};
     if (!staged) HIP_TRY(launch_rlc_begin(cv.b, s));  // (staged: the hook did, before the first range)
     // (have_challenges: one group whose c / valid are in the workspace already — the host form hashes
     //  chunk by chunk while the transfers run)
-    if (!have_challenges)
-      launch_challenge(scheme == 1, c.R + 64 * off, scheme == 1 ? c.Rp + 64 * off : (const uint8_t*)nullptr, c.m + 32 * off, cnt,
-                       cv.w.c, cv.w.valid, s, valid_in ? valid_in + off : nullptr);
+    if (!have_challenges) launch_hash(items.at(off), cnt, cv.w.c, cv.w.valid, s, valid_in ? valid_in + off : nullptr);
     if (do_sample) rlc_enqueue_sample(c, cv, key, off, cnt);
-    RlcInputs in = {};
-    in.u = c.u + 32 * off, in.c = cv.w.c, in.valid = cv.w.valid;
-    in.pk[0] = c.PK + 64 * off, in.r[0] = c.R + 64 * off;
-    if (scheme == 1) in.pk[1] = c.PKp + 64 * off, in.r[1] = c.Rp + 64 * off;
-    if (scheme == 2) in.gen = c.G + 64 * off;
+    const RlcInputs in = rlc_inputs(items.at(off), cv.w.c, cv.w.valid);
     if (staged) {
       HIP_TRY(launch_rlc_buckets(scheme, rlc_range(plan, staged->boundary, cnt - staged->boundary), cv.b, in, key,
                                  c.ok + off, true, s));
@@ -460,8 +439,7 @@ size_t dsv_rlc_workspace_bytes(size_t n, int window_bits) {
 int dsv_rlc_plan_info(int scheme, size_t n, int window_bits, int groups, uint64_t* out) {
   if (!out || scheme < 0 || scheme > 2 || n == 0 || n > kRlcMaxGroup || groups < 0 || groups > kRlcMaxSub)
     return fail(DSV_ERR_INVALID_ARGUMENT, "bad argument");
-  if (window_bits && !rlc_bits_ok(window_bits))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16");
+  if (int r = check_rlc_bits(window_bits)) return r;
   const RlcPlan p = rlc_group_plan(scheme, n, window_bits, groups);
   const uint64_t v[24] = {(uint64_t)p.c, (uint64_t)p.half, (uint64_t)p.wpk, (uint64_t)p.wr, (uint64_t)p.windows,
                           (uint64_t)p.nseg, (uint64_t)p.nseg2, (uint64_t)p.fine_bits, p.kmul, (uint64_t)p.lpts,
@@ -498,43 +476,39 @@ int dsv_debug_rlc_subgroups(int groups) {
   if (groups >= 0) g_rlc_force_groups.store(groups > kRlcMaxSub ? kRlcMaxSub : groups);
   return before;
 }
-#define DSV_RLC_PROLOGUE(nullcheck)                                                              \
-  if (n == 0) return rlc_clear_accepted(accepted);                                               \
-  if (nullcheck) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");                          \
-  if (window_bits && !rlc_bits_ok(window_bits))                                                  \
-    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16"); \
-  DSV_DEV_PROLOGUE(n, ok);                                                                       \
-  RlcVerdictTarget vt;                                                                           \
-  if (int r_ = rlc_verdict_target(ctx, accepted, vt)) return r_
+extern "C++" {
+namespace {
+// the fast accept over affine items resident in HBM
+int verify_rlc_dev(const Items& in, size_t n, void* ok, void* workspace, void* stream, int window_bits, int* accepted) {
+  if (n == 0) return rlc_clear_accepted(accepted);
+  if (in.any_null() || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int r = check_rlc_bits(window_bits)) return r;
+  DSV_DEV_PROLOGUE(n, ok);
+  RlcVerdictTarget vt;
+  if (int r = rlc_verdict_target(ctx, accepted, vt)) return r;
+  if (int r = verify_rlc_on(ctx, in, n, ok, workspace, (hipStream_t)stream, window_bits, vt.dev)) return r;
+  return rlc_verdict_wait(vt, (hipStream_t)stream);
+}
+}  // namespace
+}  // extern "C++"
 int dsv_verify_single_rlc_dev(const void* u, const void* R_uv, const void* PK_uv, const void* m, size_t n,
                               void* ok, void* workspace, void* stream, int window_bits, int* accepted) {
-  DSV_RLC_PROLOGUE(!u || !R_uv || !PK_uv || !m || !ok || !workspace);
-  if (int r = verify_rlc_on(ctx, 0, u, R_uv, nullptr, PK_uv, nullptr, nullptr, m, n, ok, workspace, (hipStream_t)stream,
-                            window_bits, vt.dev))
-    return r;
-  return rlc_verdict_wait(vt, (hipStream_t)stream);
+  return verify_rlc_dev(make_items(0, u, {R_uv, PK_uv}, m), n, ok, workspace, stream, window_bits, accepted);
 }
 int dsv_verify_double_rlc_dev(const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
                               const void* PKp_uv, const void* m, size_t n, void* ok, void* workspace, void* stream,
                               int window_bits, int* accepted) {
-  DSV_RLC_PROLOGUE(!u || !R_uv || !Rp_uv || !PK_uv || !PKp_uv || !m || !ok || !workspace);
-  if (int r = verify_rlc_on(ctx, 1, u, R_uv, Rp_uv, PK_uv, PKp_uv, nullptr, m, n, ok, workspace, (hipStream_t)stream,
-                            window_bits, vt.dev))
-    return r;
-  return rlc_verdict_wait(vt, (hipStream_t)stream);
+  return verify_rlc_dev(make_items(1, u, {R_uv, Rp_uv, PK_uv, PKp_uv}, m), n, ok, workspace, stream, window_bits,
+                        accepted);
 }
 int dsv_verify_vargen_rlc_dev(const void* u, const void* R_uv, const void* PK_uv, const void* Gen_uv, const void* m,
                               size_t n, void* ok, void* workspace, void* stream, int window_bits, int* accepted) {
-  DSV_RLC_PROLOGUE(!u || !R_uv || !PK_uv || !Gen_uv || !m || !ok || !workspace);
-  if (int r = verify_rlc_on(ctx, 2, u, R_uv, nullptr, PK_uv, nullptr, Gen_uv, m, n, ok, workspace, (hipStream_t)stream,
-                            window_bits, vt.dev))
-    return r;
-  return rlc_verdict_wait(vt, (hipStream_t)stream);
+  return verify_rlc_dev(make_items(2, u, {R_uv, PK_uv, Gen_uv}, m), n, ok, workspace, stream, window_bits, accepted);
 }
 
 // ---- batch fast accept over typed objects in host memory (SURVEY §8(f)-4 at the named entry point) ----
 // The aggregate needs its whole group resident, so this form splits the work differently from
-// verify_mont_host: the pipeline (gather, transfer, normalisation — and the challenge hash, chunk by
+// the column path (verify_host_shard): the pipeline (gather, transfer, normalisation — and the challenge hash, chunk by
 // chunk, in the shadow of the transfers) only FILLS a per-device arena; one aggregate over the arena
 // follows, and only if it fails, the per-signature kernels on what is resident already.  One group
 // (n <= 2^22) on the calling thread's device; anything else takes the ordinary column path.
@@ -546,13 +520,19 @@ struct RlcArena {
   uint8_t* ok;
   uint8_t* ws;
   size_t bytes;
+  // the resident items (points in canonical order); m: what the hash reads, if anything still does
+  Items items(int scheme, const uint8_t* m) const {
+    Items in{scheme, u};
+    for (int k = 0; k < 4; k++) in.pt[k] = pts[k];
+    in.m = m;
+    return in;
+  }
 };
 RlcArena carve_arena(uint8_t* base, int kind, size_t n) {
   Stager st(base);
   RlcArena a = {};
   a.u = st.take(n * 32);
-  const int np = kind == 0 ? 2 : (kind == 1 ? 4 : 3);
-  for (int k = 0; k < np; k++) a.pts[k] = st.take(n * 64);
+  for (int k = 0; k < layout(kind).points; k++) a.pts[k] = st.take(n * 64);
   a.ok = st.take(n);
   a.ws = st.take(dsv_rlc_workspace_bytes(n, 0));
   a.bytes = st.off;
@@ -595,32 +575,29 @@ struct RlcHook {
     return DSV_OK;
   }
 };
-template <size_t NIN>
-int fill_arena(Context& ctx, int kind, const HostIn (&ins)[NIN], size_t n, uint8_t* ok, const RlcArena& a,
+int fill_arena(Context& ctx, int kind, const HostIn* ins, size_t nin, size_t n, uint8_t* ok, const RlcArena& a,
                const Workspace& w, RlcHook* hook) {
   Context* cp = &ctx;
-  const int np = kind == 0 ? 2 : (kind == 1 ? 4 : 3);
+  const int np = layout(kind).points;
   return run_pipelined(
-      ctx, ins, ok, n, kMontItemBytes, 0,
+      ctx, ins, nin, ok, n, kMontItemBytes, 0,
       [=](const void* const* d, size_t cnt, Stager& x, hipStream_t st, Staged& g) {
         const size_t first = t_chunk_first;
-        NormalizeArgs na = {};
+        const uint8_t* in[4] = {};
+        uint8_t* out[4] = {};
         for (int k = 0; k < np; k++) {
-          na.in[k] = (const uint8_t*)d[1 + k];
-          na.out[k] = a.pts[k] + first * 64;
-          g.p[1 + k] = na.out[k];
+          in[k] = (const uint8_t*)d[1 + k];
+          out[k] = a.pts[k] + first * 64;
+          g.p[1 + k] = out[k];
           g.bytes[1 + k] = 64;
         }
         uint8_t* valid = x.take(cnt);
         uint8_t* cm = x.take(cnt * 32);  // the canonical message: only the hash reads it
         u32* prefix = reinterpret_cast<u32*>(x.take(normalize_prefix_bytes(cnt, np)));
-        na.u_mont = (const uint8_t*)d[0];
-        na.m_mont = (const uint8_t*)d[1 + np];
-        na.u_out = a.u + first * 32;
-        na.m_out = cm;
-        launch_normalize_uvz(na, np, cnt, valid, prefix, st, cp->norm_per_lane, cp->norm_block);
+        normalize_on(kind, in, out, cnt, valid, prefix, st, (const uint8_t*)d[0], (const uint8_t*)d[1 + np],
+                     a.u + first * 32, cm, cp->norm_per_lane, cp->norm_block);
         HIP_TRY(hipGetLastError());
-        g.p[0] = na.u_out;
+        g.p[0] = a.u + first * 32;
         g.p[1 + np] = cm;
         g.bytes[0] = g.bytes[1 + np] = 32;
         g.valid = valid;
@@ -629,8 +606,7 @@ int fill_arena(Context& ctx, int kind, const HostIn (&ins)[NIN], size_t n, uint8
       [=](const Staged& g, size_t off, size_t cnt, void*, void*, Stager&, hipStream_t st) {
         const size_t at = t_chunk_first + off;
         if (int r = hook->at_part(at)) return r;
-        launch_challenge(kind == 1, g.p[1] + 64 * off, kind == 1 ? g.p[2] + 64 * off : (const uint8_t*)nullptr,
-                         g.p[1 + np] + 32 * off, cnt, w.c + 32 * at, w.valid + at, st, g.valid + off);
+        launch_hash(g.items(kind, off), cnt, w.c + 32 * at, w.valid + at, st, g.valid + off);
         HIP_TRY(hipGetLastError());
         return (int)DSV_OK;
       },
@@ -666,9 +642,7 @@ int rlc_host_shard(Context& ctx, int kind, size_t n, uint8_t* ok, int* accepted,
   if (!ar.stream) HIP_TRY(hipStreamCreateWithFlags(&ar.stream, hipStreamNonBlocking));
   const RlcArena a = carve_arena(ar.dev, kind, n);
   const Workspace w = carve(a.ws, n);  // where the aggregate (and the per-signature kernels) expect c / valid
-  // Points in the arena: single R PK, double R R' PK PK', var-generator R PK Gen
-  const uint8_t *R = a.pts[0], *Rp = kind == 1 ? a.pts[1] : nullptr, *PK = a.pts[kind == 1 ? 2 : 1],
-                *PKp = kind == 1 ? a.pts[3] : nullptr, *Gen = kind == 2 ? a.pts[2] : nullptr;
+  const Items items = a.items(kind, /*m: hashed already*/ a.u);
   static const bool staged_on = !(getenv("DSV_RLC_STAGED") && atoi(getenv("DSV_RLC_STAGED")) == 0);
   // (two ranges only in the steady state: while the history says "batches fail" the group runs in sub-groups,
   //  all of them after the fill)
@@ -682,11 +656,7 @@ int rlc_host_shard(Context& ctx, int kind, size_t n, uint8_t* ok, int* accepted,
     hook.ev[0] = ar.ev[0], hook.ev[1] = ar.ev[1];
     hook.plan = rlc_group_plan(kind, n, 0, 1);  // (what verify_rlc_on plans for a staged group)
     hook.cv = carve_rlc(a.ws, n, n, hook.plan);
-    hook.in = RlcInputs{};
-    hook.in.u = a.u, hook.in.c = hook.cv.w.c, hook.in.valid = hook.cv.w.valid;
-    hook.in.pk[0] = PK, hook.in.r[0] = R;
-    if (kind == 1) hook.in.pk[1] = PKp, hook.in.r[1] = Rp;
-    if (kind == 2) hook.in.gen = Gen;
+    hook.in = rlc_inputs(items, hook.cv.w.c, hook.cv.w.valid);
     if (int r = rlc_random_key(hook.key)) return r;
   }
   if (int rc = fill(a, w, &hook)) {
@@ -699,8 +669,8 @@ int rlc_host_shard(Context& ctx, int kind, size_t n, uint8_t* ok, int* accepted,
   staged.boundary = hook.boundary;
   RlcVerdictTarget vt;
   if (int r = rlc_verdict_target(ctx, accepted, vt)) return r;
-  if (int r = verify_rlc_on(ctx, kind, a.u, R, Rp, PK, PKp, Gen, /*m: hashed already*/ a.u, n, a.ok, a.ws,
-                            ar.stream, 0, vt.dev, false, true, nullptr, hook.fired ? &staged : nullptr))
+  if (int r = verify_rlc_on(ctx, items, n, a.ok, a.ws, ar.stream, 0, vt.dev, false, true, nullptr,
+                            hook.fired ? &staged : nullptr))
     return r;
   HIP_TRY(hipMemcpyAsync(ok, a.ok, n, hipMemcpyDeviceToHost, ar.stream));
   HIP_TRY(hipStreamSynchronize(ar.stream));
@@ -711,19 +681,9 @@ int verify_mont_cols_rlc_shard(Context& ctx, int kind, const dsv_column* cols, s
                                int* accepted) {
   Context* cp = &ctx;
   return rlc_host_shard(ctx, kind, n, ok + off, accepted, [=](const RlcArena& a, const Workspace& w, RlcHook* hook) {
-    auto in = [&](int k, size_t width) {
-      return HostIn{static_cast<const uint8_t*>(cols[k].base) + off * cols[k].stride, width, cols[k].stride};
-    };
-    if (kind == 0) {
-      const HostIn ins[4] = {in(0, 32), in(1, 96), in(2, 96), in(3, 32)};
-      return fill_arena(*cp, 0, ins, n, ok + off, a, w, hook);
-    }
-    if (kind == 1) {
-      const HostIn ins[6] = {in(0, 32), in(1, 96), in(2, 96), in(3, 96), in(4, 96), in(5, 32)};
-      return fill_arena(*cp, 1, ins, n, ok + off, a, w, hook);
-    }
-    const HostIn ins[5] = {in(0, 32), in(1, 96), in(2, 96), in(3, 96), in(4, 32)};
-    return fill_arena(*cp, 2, ins, n, ok + off, a, w, hook);
+    HostIn ins[kMaxHostIn];
+    const size_t nin = column_inputs(kind, kMont, cols, off, ins);
+    return fill_arena(*cp, kind, ins, nin, n, ok + off, a, w, hook);
   });
 }
 // Shards like the *_multi forms: one group per initialised device (each with its own aggregate; all of
@@ -731,7 +691,7 @@ int verify_mont_cols_rlc_shard(Context& ctx, int kind, const dsv_column* cols, s
 // thread's device, or — beyond 2^22 items — the ordinary column path.
 int verify_mont_cols_rlc(int kind, const dsv_column* cols, size_t n, uint8_t* ok, int* accepted) {
   if (accepted) *accepted = 0;
-  if (int r = check_cols(kind, cols, n, ok)) return r;
+  if (int r = check_cols(kind, cols, n, ok, kMont)) return r;
   if (n == 0) return DSV_OK;
   int nd = 0;
   for (int d = 0; d < kMaxDevices; d++) nd += g_ctx[d].ready.load(std::memory_order_acquire) ? 1 : 0;
@@ -747,7 +707,7 @@ int verify_mont_cols_rlc(int kind, const dsv_column* cols, size_t n, uint8_t* ok
     if (rc == DSV_OK && accepted) *accepted = rejected.load() == 0 ? 1 : 0;
     return rc;
   }
-  if (n > kRlcMaxGroup || n < kRlcMinAuto) return verify_mont_cols(kind, cols, n, ok, true);
+  if (n > kRlcMaxGroup || n < kRlcMinAuto) return verify_host_cols(kind, kMont, cols, n, ok, true);
   Context* ctxp = nullptr;
   if (int r = host_context(ctxp)) return r;
   return verify_mont_cols_rlc_shard(*ctxp, kind, cols, 0, n, ok, accepted);
@@ -770,33 +730,17 @@ int verify_wire_rlc_dev(int kind, const void* sig, const void* pk, const void* m
   if (n == 0) return rlc_clear_accepted(accepted);
   if (!sig || !pk || !m || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   if (((uintptr_t)sig | (uintptr_t)pk) & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");
-  if (window_bits && !rlc_bits_ok(window_bits))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16");
+  if (int r = check_rlc_bits(window_bits)) return r;
   DSV_DEV_PROLOGUE(n, ok);
   const hipStream_t st = (hipStream_t)stream;
   Stager x(static_cast<uint8_t*>(workspace));
-  WireWs w;
-  w.u = x.take(n * 32);
-  w.R = x.take(n * 64);
-  w.Rp = x.take(n * 64);
-  w.P0 = x.take(n * 64);
-  w.P1 = x.take(n * 64);
-  w.valid = x.take(n);
+  const WireWs w = carve_wire(x, n);
   void* rws = x.take(0);
-  const uint8_t *dsig = (const uint8_t*)sig, *dpk = (const uint8_t*)pk;
-  const size_t sig_bytes = kind == 1 ? 96 : 64, pk_bytes = kind == 0 ? 32 : 64;
-  launch_gather32(dsig, sig_bytes, n, w.u, st);
-  if (int r = decompress_on(ctx, dsig + 32, sig_bytes, n, w.R, w.valid, 0, st)) return r;
-  if (kind == 1)
-    if (int r = decompress_on(ctx, dsig + 64, sig_bytes, n, w.Rp, w.valid, 1, st)) return r;
-  if (int r = decompress_on(ctx, dpk, pk_bytes, n, w.P0, w.valid, 1, st)) return r;
-  if (kind != 0)
-    if (int r = decompress_on(ctx, dpk + 32, pk_bytes, n, w.P1, w.valid, 1, st)) return r;
+  const Items items = w.items(kind, m);
+  if (int r = decode_wire(ctx, kind, (const uint8_t*)sig, (const uint8_t*)pk, n, items, w.valid, st)) return r;
   RlcVerdictTarget vt;
   if (int r = rlc_verdict_target(ctx, accepted, vt)) return r;
-  if (int r = verify_rlc_on(ctx, kind, w.u, w.R, kind == 1 ? w.Rp : nullptr, w.P0, kind == 1 ? w.P1 : nullptr,
-                            kind == 2 ? w.P1 : nullptr, m, n, ok, rws, st, window_bits, vt.dev, false, false, w.valid))
-    return r;
+  if (int r = verify_rlc_on(ctx, items, n, ok, rws, st, window_bits, vt.dev, false, false, w.valid)) return r;
   return rlc_verdict_wait(vt, st);
 }
 }  // namespace
@@ -833,27 +777,19 @@ int verify_wire_rlc_host(int kind, const uint8_t* sig, const uint8_t* pk, const 
   if (int r = host_context(ctxp)) return r;
   Context& ctx = *ctxp;
   if (n > kRlcMaxGroup || n < kRlcMinAuto) return verify_wire(ctx, kind, sig, pk, m, n, ok);
-  const size_t sig_bytes = kind == 1 ? 96 : 64, pk_bytes = kind == 0 ? 32 : 64;
   Context* cp = &ctx;
   return rlc_host_shard(ctx, kind, n, ok, accepted, [=](const RlcArena& a, const Workspace& w, RlcHook* hook) {
-    const HostIn ins[3] = {{sig, sig_bytes}, {pk, pk_bytes}, {m, 32}};
-    return run_pipelined(*cp, ins, ok, n, 0, /*per item: the decoder's verdict byte*/ 1, NoPrep{},
+    const HostIn ins[3] = {{sig, layout(kind).sig_bytes}, {pk, layout(kind).pk_bytes}, {m, 32}};
+    return run_pipelined(*cp, ins, 3, ok, n, 0, /*per item: the decoder's verdict byte*/ 1, NoPrep{},
                          [=](const Staged& g, size_t off, size_t cnt, void*, void*, Stager& x, hipStream_t st) {
       const size_t at = t_chunk_first + off;
       if (int r = hook->at_part(at)) return r;
-      const uint8_t *dsig = g.p[0] + off * sig_bytes, *dpk = g.p[1] + off * pk_bytes;
       uint8_t* valid = x.take(cnt);
-      launch_gather32(dsig, sig_bytes, cnt, a.u + 32 * at, st);
-      // arena order: single R PK, double R R' PK PK', var-generator R PK Gen
-      int slot = 0;
-      if (int r = decompress_on(*cp, dsig + 32, sig_bytes, cnt, a.pts[slot++] + 64 * at, valid, 0, st)) return r;
-      if (kind == 1)
-        if (int r = decompress_on(*cp, dsig + 64, sig_bytes, cnt, a.pts[slot++] + 64 * at, valid, 1, st)) return r;
-      if (int r = decompress_on(*cp, dpk, pk_bytes, cnt, a.pts[slot++] + 64 * at, valid, 1, st)) return r;
-      if (kind != 0)
-        if (int r = decompress_on(*cp, dpk + 32, pk_bytes, cnt, a.pts[slot++] + 64 * at, valid, 1, st)) return r;
-      launch_challenge(kind == 1, a.pts[0] + 64 * at, kind == 1 ? a.pts[1] + 64 * at : (const uint8_t*)nullptr,
-                       g.p[2] + 32 * off, cnt, w.c + 32 * at, w.valid + at, st, valid);
+      Items items = a.items(kind, nullptr).at(at);
+      items.m = g.p[2] + 32 * off;  // (the sub-batch's messages, in the staging)
+      if (int r = decode_wire(*cp, kind, g.p[0] + off * g.bytes[0], g.p[1] + off * g.bytes[1], cnt, items, valid, st))
+        return r;
+      launch_hash(items, cnt, w.c + 32 * at, w.valid + at, st, valid);
       HIP_TRY(hipGetLastError());
       return (int)DSV_OK;
     }, kPipeNoVerdicts);

@@ -41,35 +41,9 @@ int dsv_decompress_points(const uint8_t* in32, size_t n, uint8_t* out_uv, uint8_
   return DSV_OK;
 }
 
-namespace {
-// shared body of the *_wire entry points.  sig: n records of sig_bytes = 32 (u) + 32*n_sig_points;
-// pk: n records of 32*n_pk_points compressed points.  kind: 0 single, 1 double, 2 vargen.
-constexpr size_t kWireItemBytes = 32 + 4 * 64 + 1;
-int verify_wire_on(Context& ctx, int kind, const uint8_t* dsig, const uint8_t* dpk, const void* dm,
-                   size_t cnt, void* dok, const WireWs& x, void* vws, hipStream_t st) {
-  const size_t sig_bytes = kind == 1 ? 96 : 64, pk_bytes = kind == 0 ? 32 : 64;
-  launch_gather32(dsig, sig_bytes, cnt, x.u, st);
-  if (int r = decompress_on(ctx, dsig + 32, sig_bytes, cnt, x.R, x.valid, 0, st)) return r;
-  if (kind == 1)
-    if (int r = decompress_on(ctx, dsig + 64, sig_bytes, cnt, x.Rp, x.valid, 1, st)) return r;
-  if (int r = decompress_on(ctx, dpk, pk_bytes, cnt, x.P0, x.valid, 1, st)) return r;
-  if (kind != 0)
-    if (int r = decompress_on(ctx, dpk + 32, pk_bytes, cnt, x.P1, x.valid, 1, st)) return r;
-  int rc;
-  if (kind == 0) rc = verify_single_on(ctx, x.u, x.R, x.P0, dm, cnt, dok, vws, st, x.valid);
-  else if (kind == 1) rc = verify_double_on(ctx, x.u, x.R, x.Rp, x.P0, x.P1, dm, cnt, dok, vws, st, x.valid);
-  else rc = verify_vargen_on(ctx, x.u, x.R, x.P0, x.P1, dm, cnt, dok, vws, st, x.valid);
-  if (rc) return rc;
-  HIP_TRY(hipGetLastError());
-  return DSV_OK;
-}
-// device-pointer form: serialized records already resident in HBM
-int verify_wire_dev(int kind, const void* sig, const void* pk, const void* m, size_t n, void* ok,
-                    void* workspace, void* stream) {
-  if (n && (!sig || !pk || !m || !ok || !workspace)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)sig | (uintptr_t)pk) & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");
-  DSV_DEV_PROLOGUE(n, ok);
-  Stager x(static_cast<uint8_t*>(workspace));
+extern "C++" {
+namespace dsvh {
+WireWs carve_wire(Stager& x, size_t n) {
   WireWs w;
   w.u = x.take(n * 32);
   w.R = x.take(n * 64);
@@ -77,33 +51,68 @@ int verify_wire_dev(int kind, const void* sig, const void* pk, const void* m, si
   w.P0 = x.take(n * 64);
   w.P1 = x.take(n * 64);
   w.valid = x.take(n);
+  return w;
+}
+// sig: n records of sig_bytes = 32 (u) + 32 per nonce point; pk: n records of pk_bytes = 32 per key point
+int decode_wire(Context& ctx, int scheme, const uint8_t* sig, const uint8_t* pk, size_t n, const Items& out,
+                uint8_t* valid, hipStream_t st) {
+  const SchemeLayout& L = layout(scheme);
+  const int ns = (int)(L.sig_bytes / 32) - 1;
+  launch_gather32(sig, L.sig_bytes, n, const_cast<uint8_t*>(out.u), st);
+  for (int k = 0; k < L.points; k++) {
+    const uint8_t* in = k < ns ? sig + 32 * (1 + k) : pk + 32 * (k - ns);
+    if (int r = decompress_on(ctx, in, k < ns ? L.sig_bytes : L.pk_bytes, n, const_cast<uint8_t*>(out.pt[k]), valid,
+                              k > 0, st))
+      return r;
+  }
+  return DSV_OK;
+}
+}  // namespace dsvh
+namespace {
+// shared body of the *_wire entry points
+constexpr size_t kWireItemBytes = 32 + 4 * 64 + 1;
+int verify_wire_on(Context& ctx, int scheme, const uint8_t* dsig, const uint8_t* dpk, const void* dm,
+                   size_t cnt, void* dok, const WireWs& x, void* vws, hipStream_t st) {
+  const Items in = x.items(scheme, dm);
+  if (int r = decode_wire(ctx, scheme, dsig, dpk, cnt, in, x.valid, st)) return r;
+  if (int rc = verify_on(ctx, in, cnt, dok, vws, st, x.valid)) return rc;
+  HIP_TRY(hipGetLastError());
+  return DSV_OK;
+}
+// device-pointer form: serialized records already resident in HBM
+int verify_wire_dev(int scheme, const void* sig, const void* pk, const void* m, size_t n, void* ok,
+                    void* workspace, void* stream) {
+  if (n && (!sig || !pk || !m || !ok || !workspace)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)sig | (uintptr_t)pk) & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");
+  DSV_DEV_PROLOGUE(n, ok);
+  Stager x(static_cast<uint8_t*>(workspace));
+  const WireWs w = carve_wire(x, n);
   void* vws = x.take(dsv_workspace_bytes(n));
-  return verify_wire_on(ctx, kind, (const uint8_t*)sig, (const uint8_t*)pk, m, n, ok, w, vws,
+  return verify_wire_on(ctx, scheme, (const uint8_t*)sig, (const uint8_t*)pk, m, n, ok, w, vws,
                         (hipStream_t)stream);
 }
 }  // namespace
 
-extern "C++" {
 namespace dsvh {
-int verify_wire(Context& ctx, int kind, const uint8_t* sig, const uint8_t* pk, const uint8_t* m,
+int verify_wire(Context& ctx, int scheme, const uint8_t* sig, const uint8_t* pk, const uint8_t* m,
                 size_t n, uint8_t* ok) {
-  const size_t sig_bytes = kind == 1 ? 96 : 64, pk_bytes = kind == 0 ? 32 : 64;
+  const size_t sig_bytes = layout(scheme).sig_bytes, pk_bytes = layout(scheme).pk_bytes;
   const HostIn ins[3] = {{sig, sig_bytes}, {pk, pk_bytes}, {m, 32}};
   Context* cp = &ctx;
-  return run_pipelined(ctx, ins, ok, n, 0, kWireItemBytes, NoPrep{},
+  return run_pipelined(ctx, ins, 3, ok, n, 0, kWireItemBytes, NoPrep{},
                        [=](const Staged& g, size_t off, size_t cnt, void* dok, void* ws, Stager& x, hipStream_t st) {
-    WireWs w;
-    w.u = x.take(cnt * 32);
-    w.R = x.take(cnt * 64);
-    w.Rp = x.take(cnt * 64);
-    w.P0 = x.take(cnt * 64);
-    w.P1 = x.take(cnt * 64);
-    w.valid = x.take(cnt);
-    return verify_wire_on(*cp, kind, g.p[0] + off * g.bytes[0], g.p[1] + off * g.bytes[1],
-                          g.p[2] + off * g.bytes[2], cnt, dok, w, ws, st);
+    return verify_wire_on(*cp, scheme, g.p[0] + off * g.bytes[0], g.p[1] + off * g.bytes[1],
+                          g.p[2] + off * g.bytes[2], cnt, dok, carve_wire(x, cnt), ws, st);
   });
 }
 }  // namespace dsvh
+namespace {
+int verify_wire_host(int scheme, const uint8_t* sig, const uint8_t* pk, const uint8_t* m, size_t n, uint8_t* ok) {
+  if (n && (!sig || !pk || !m || !ok)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  DSV_HOST_PROLOGUE(n);
+  return verify_wire(ctx, scheme, sig, pk, m, n, ok);
+}
+}  // namespace
 }  // extern "C++"
 
 size_t dsv_wire_workspace_bytes(size_t n) {
@@ -125,22 +134,15 @@ int dsv_verify_vargen_wire_dev(const void* sig64, const void* pk64, const void* 
 
 int dsv_verify_single_wire(const uint8_t* sig64, const uint8_t* pk32, const uint8_t* m, size_t n,
                            uint8_t* ok) {
-  if (n && (!sig64 || !pk32 || !m || !ok)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_HOST_PROLOGUE(n);
-  return verify_wire(ctx, 0, sig64, pk32, m, n, ok);
+  return verify_wire_host(0, sig64, pk32, m, n, ok);
 }
 int dsv_verify_double_wire(const uint8_t* sig96, const uint8_t* pk64, const uint8_t* m, size_t n,
                            uint8_t* ok) {
-  if (n && (!sig96 || !pk64 || !m || !ok)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_HOST_PROLOGUE(n);
-  return verify_wire(ctx, 1, sig96, pk64, m, n, ok);
+  return verify_wire_host(1, sig96, pk64, m, n, ok);
 }
 int dsv_verify_vargen_wire(const uint8_t* sig64, const uint8_t* pk64, const uint8_t* m, size_t n,
                            uint8_t* ok) {
-  if (n && (!sig64 || !pk64 || !m || !ok)) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  DSV_HOST_PROLOGUE(n);
-  return verify_wire(ctx, 2, sig64, pk64, m, n, ok);
+  return verify_wire_host(2, sig64, pk64, m, n, ok);
 }
-
 
 }  // extern "C"

@@ -110,61 +110,62 @@ def _same_n(*arrs):
     return n
 
 
+# Per scheme: the fields of an item (u, the points in the canonical order, m) and the wire record widths
+# (signature, public key).  Point widths by form: affine 64 B, projective / Montgomery limbs 96 B.
+_SCHEMES = {"single": (("u", "R", "PK", "m"), (64, 32)),
+            "double": (("u", "R", "Rp", "PK", "PKp", "m"), (96, 64)),
+            "vargen": (("u", "R", "PK", "Gen", "m"), (64, 64))}
+_POINT_WIDTH = {"": 64, "_ext": 96, "_mont": 96}
+
+
+def _layout(scheme, form):
+    """(names, widths) of one call's arrays: form "", "_ext", "_mont" (an item's fields) or "_wire" (records)"""
+    if form == "_wire":
+        sw, pw = _SCHEMES[scheme][1]
+        return ("sig", "pk", "m"), (sw, pw, 32)
+    fields = _SCHEMES[scheme][0]
+    pw = _POINT_WIDTH[form]
+    names = tuple(f if f in ("u", "m") or not form else f + "_uvz" for f in fields)
+    return names, tuple(32 if f in ("u", "m") else pw for f in fields)
+
+
 # ------------------------------------------------------------------ host-buffer path
-def verify_single(u, R, PK, m):
-    u, R, PK, m = _arr(u, 32), _arr(R, 64), _arr(PK, 64), _arr(m, 32)
-    n = _same_n(u, R, PK, m)
+def _host(scheme, form, arrays, multi=False, rlc=False):
+    """dsv_verify_<scheme><form>[_multi | _rlc] over host arrays -> verdicts (rlc: (verdicts, accepted))"""
+    _, widths = _layout(scheme, form)
+    arrs = [_arr(a, w) for a, w in zip(arrays, widths)]
+    n = _same_n(*arrs)
     ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_single(_p(u), _p(R), _p(PK), _p(m), ctypes.c_size_t(n), _p(ok)))
-    return ok
+    name = "dsv_verify_%s%s%s" % (scheme, form, "_multi" if multi else "_rlc" if rlc else "")
+    accepted = ctypes.c_int(0)
+    tail = [ctypes.byref(accepted)] if rlc else []
+    _lib.check(getattr(_lib.load(), name)(*([_p(a) for a in arrs] + [ctypes.c_size_t(n), _p(ok)] + tail)))
+    return (ok, bool(accepted.value)) if rlc else ok
+
+
+def verify_single(u, R, PK, m):
+    return _host("single", "", (u, R, PK, m))
 
 
 def verify_double(u, R, Rp, PK, PKp, m):
-    u, R, Rp, PK, PKp, m = (_arr(u, 32), _arr(R, 64), _arr(Rp, 64), _arr(PK, 64), _arr(PKp, 64),
-                            _arr(m, 32))
-    n = _same_n(u, R, Rp, PK, PKp, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_double(_p(u), _p(R), _p(Rp), _p(PK), _p(PKp), _p(m),
-                                             ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("double", "", (u, R, Rp, PK, PKp, m))
 
 
 def verify_vargen(u, R, PK, Gen, m):
-    u, R, PK, Gen, m = _arr(u, 32), _arr(R, 64), _arr(PK, 64), _arr(Gen, 64), _arr(m, 32)
-    n = _same_n(u, R, PK, Gen, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_vargen(_p(u), _p(R), _p(PK), _p(Gen), _p(m),
-                                             ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("vargen", "", (u, R, PK, Gen, m))
 
 
 def verify_single_multi(u, R, PK, m):
     """dsv_verify_single_multi: one host batch sharded over every initialised device."""
-    u, R, PK, m = _arr(u, 32), _arr(R, 64), _arr(PK, 64), _arr(m, 32)
-    n = _same_n(u, R, PK, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_single_multi(_p(u), _p(R), _p(PK), _p(m), ctypes.c_size_t(n),
-                                                   _p(ok)))
-    return ok
+    return _host("single", "", (u, R, PK, m), multi=True)
 
 
 def verify_double_multi(u, R, Rp, PK, PKp, m):
-    u, R, Rp, PK, PKp, m = (_arr(u, 32), _arr(R, 64), _arr(Rp, 64), _arr(PK, 64), _arr(PKp, 64),
-                            _arr(m, 32))
-    n = _same_n(u, R, Rp, PK, PKp, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_double_multi(_p(u), _p(R), _p(Rp), _p(PK), _p(PKp), _p(m),
-                                                   ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("double", "", (u, R, Rp, PK, PKp, m), multi=True)
 
 
 def verify_vargen_multi(u, R, PK, Gen, m):
-    u, R, PK, Gen, m = _arr(u, 32), _arr(R, 64), _arr(PK, 64), _arr(Gen, 64), _arr(m, 32)
-    n = _same_n(u, R, PK, Gen, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_vargen_multi(_p(u), _p(R), _p(PK), _p(Gen), _p(m),
-                                                   ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("vargen", "", (u, R, PK, Gen, m), multi=True)
 
 
 def to_hash_inputs(uvz):
@@ -177,49 +178,48 @@ def to_hash_inputs(uvz):
     return out, ok
 
 
-def _ext_call(name, widths, arrays):
-    arrs = [_arr(a, w) for a, w in zip(arrays, widths)]
-    n = _same_n(*arrs)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(getattr(_lib.load(), name)(*([_p(a) for a in arrs] + [ctypes.c_size_t(n), _p(ok)])))
-    return ok
-
-
 def verify_single_ext(u, R_uvz, PK_uvz, m, multi=False):
     """Projective points (u || v || z, 96 B): the device does to_hash_inputs."""
-    return _ext_call("dsv_verify_single_ext" + ("_multi" if multi else ""), (32, 96, 96, 32),
-                     (u, R_uvz, PK_uvz, m))
+    return _host("single", "_ext", (u, R_uvz, PK_uvz, m), multi)
 
 
 def verify_double_ext(u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m, multi=False):
-    return _ext_call("dsv_verify_double_ext" + ("_multi" if multi else ""), (32, 96, 96, 96, 96, 32),
-                     (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m))
+    return _host("double", "_ext", (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m), multi)
 
 
 def verify_vargen_ext(u, R_uvz, PK_uvz, Gen_uvz, m, multi=False):
-    return _ext_call("dsv_verify_vargen_ext" + ("_multi" if multi else ""), (32, 96, 96, 96, 32),
-                     (u, R_uvz, PK_uvz, Gen_uvz, m))
+    return _host("vargen", "_ext", (u, R_uvz, PK_uvz, Gen_uvz, m), multi)
 
 
 # ---- the reference's in-memory representation: every element = four u64 Montgomery limbs (R = 2^256)
 def verify_single_mont(u, R_uvz, PK_uvz, m, multi=False):
-    return _ext_call("dsv_verify_single_mont" + ("_multi" if multi else ""), (32, 96, 96, 32),
-                     (u, R_uvz, PK_uvz, m))
+    return _host("single", "_mont", (u, R_uvz, PK_uvz, m), multi)
 
 
 def verify_double_mont(u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m, multi=False):
-    return _ext_call("dsv_verify_double_mont" + ("_multi" if multi else ""), (32, 96, 96, 96, 96, 32),
-                     (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m))
+    return _host("double", "_mont", (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m), multi)
 
 
 def verify_vargen_mont(u, R_uvz, PK_uvz, Gen_uvz, m, multi=False):
-    return _ext_call("dsv_verify_vargen_mont" + ("_multi" if multi else ""), (32, 96, 96, 96, 32),
-                     (u, R_uvz, PK_uvz, Gen_uvz, m))
+    return _host("vargen", "_mont", (u, R_uvz, PK_uvz, Gen_uvz, m), multi)
 
 
-_MONT_COLS = {"single": ("dsv_verify_single_mont_cols", (32, 96, 96, 32)),
-              "double": ("dsv_verify_double_mont_cols", (32, 96, 96, 96, 96, 32)),
-              "vargen": ("dsv_verify_vargen_mont_cols", (32, 96, 96, 96, 32))}
+def _columns(scheme, cols):
+    """(n, dsv_column array) of typed-object columns: one uint8 [n, width] array per field, rows strided,
+    bytes of a row contiguous"""
+    _, widths = _layout(scheme, "_mont")
+    if len(cols) != len(widths):
+        raise ValueError("dsv_verify_%s_mont_cols takes %d columns" % (scheme, len(widths)))
+    n = cols[0].shape[0]
+    arr = (_lib.Column * len(cols))()
+    for k, (c, w) in enumerate(zip(cols, widths)):
+        if c.dtype != np.uint8 or c.ndim != 2 or c.shape != (n, w) or (w > 1 and c.strides[1] != 1) \
+                or c.strides[0] < w:
+            raise ValueError("column %d: expected uint8 [n, %d] rows with contiguous bytes, got %r / strides %r"
+                             % (k, w, c.shape, c.strides))
+        arr[k].base = c.ctypes.data
+        arr[k].stride = c.strides[0]
+    return n, arr
 
 
 def verify_mont_cols(scheme, cols):
@@ -227,40 +227,19 @@ def verify_mont_cols(scheme, cols):
     [n, width] per field in the scheme's column order (single: u, R, PK, m; double: u, R, R', PK, PK',
     m; vargen: u, R, PK, Gen, m) — typically VIEWS into arrays of records (numpy structured arrays,
     `records["R"][:, :96]`): only the last axis has to be contiguous, the row stride is passed on."""
-    name, widths = _MONT_COLS[scheme]
-    if len(cols) != len(widths):
-        raise ValueError("%s takes %d columns" % (name, len(widths)))
-    n = cols[0].shape[0]
-    arr = (_lib.Column * len(cols))()
-    for k, (c, w) in enumerate(zip(cols, widths)):
-        if c.dtype != np.uint8 or c.ndim != 2 or c.shape != (n, w) or (w > 1 and c.strides[1] != 1) \
-                or c.strides[0] < w:
-            raise ValueError("column %d: expected uint8 [n, %d] rows with contiguous bytes, got %r / strides %r"
-                             % (k, w, c.shape, c.strides))
-        arr[k].base = c.ctypes.data
-        arr[k].stride = c.strides[0]
+    n, arr = _columns(scheme, cols)
     ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(getattr(_lib.load(), name)(arr, ctypes.c_size_t(n), _p(ok)))
+    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols" % scheme)(arr, ctypes.c_size_t(n), _p(ok)))
     return ok
 
 
 def verify_mont_cols_rlc(scheme, cols):
     """dsv_verify_*_mont_cols_rlc: the same columns through the batch fast accept -> (verdicts, accepted)"""
-    name, widths = _MONT_COLS[scheme]
-    if len(cols) != len(widths):
-        raise ValueError("%s takes %d columns" % (name, len(widths)))
-    n = cols[0].shape[0]
-    arr = (_lib.Column * len(cols))()
-    for k, (c, w) in enumerate(zip(cols, widths)):
-        if c.dtype != np.uint8 or c.ndim != 2 or c.shape != (n, w) or (w > 1 and c.strides[1] != 1) \
-                or c.strides[0] < w:
-            raise ValueError("column %d: expected uint8 [n, %d] rows with contiguous bytes, got %r / strides %r"
-                             % (k, w, c.shape, c.strides))
-        arr[k].base = c.ctypes.data
-        arr[k].stride = c.strides[0]
+    n, arr = _columns(scheme, cols)
     ok = np.zeros(n, dtype=np.uint8)
     accepted = ctypes.c_int(0)
-    _lib.check(getattr(_lib.load(), name + "_rlc")(arr, ctypes.c_size_t(n), _p(ok), ctypes.byref(accepted)))
+    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols_rlc" % scheme)(arr, ctypes.c_size_t(n), _p(ok),
+                                                                          ctypes.byref(accepted)))
     return ok, bool(accepted.value)
 
 
@@ -269,22 +248,12 @@ class MontColsJob:
     there and returns them.  Keeps the column arrays alive until then."""
 
     def __init__(self, scheme, cols):
-        name, widths = _MONT_COLS[scheme]
-        if len(cols) != len(widths):
-            raise ValueError("%s takes %d columns" % (name, len(widths)))
-        n = cols[0].shape[0]
-        arr = (_lib.Column * len(cols))()
-        for k, (c, w) in enumerate(zip(cols, widths)):
-            if c.dtype != np.uint8 or c.ndim != 2 or c.shape != (n, w) or (w > 1 and c.strides[1] != 1) \
-                    or c.strides[0] < w:
-                raise ValueError("column %d: expected uint8 [n, %d] rows with contiguous bytes" % (k, w))
-            arr[k].base = c.ctypes.data
-            arr[k].stride = c.strides[0]
+        n, arr = _columns(scheme, cols)
         self._cols = cols
         self._ok = np.zeros(n, dtype=np.uint8)
         self._job = ctypes.c_void_p()
-        _lib.check(getattr(_lib.load(), name + "_submit")(arr, ctypes.c_size_t(n), _p(self._ok),
-                                                          ctypes.byref(self._job)))
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols_submit" % scheme)(
+            arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
 
     def __del__(self):
         # a job dropped unwaited still reads the columns and writes the verdicts: wait before they go
@@ -394,40 +363,21 @@ def compress_points(uv):
 
 
 def verify_single_wire(sig64, pk32, m):
-    sig, pk, m = _arr(sig64, 64), _arr(pk32, 32), _arr(m, 32)
-    n = _same_n(sig, pk, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_single_wire(_p(sig), _p(pk), _p(m), ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("single", "_wire", (sig64, pk32, m))
 
 
 def verify_wire_rlc(scheme, sig, pk, m):
     """dsv_verify_*_wire_rlc: serialized records in host memory through the batch fast accept ->
     (verdicts, accepted)"""
-    sw, pw = {"single": (64, 32), "double": (96, 64), "vargen": (64, 64)}[scheme]
-    sig, pk, m = _arr(sig, sw), _arr(pk, pw), _arr(m, 32)
-    n = _same_n(sig, pk, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    accepted = ctypes.c_int(0)
-    _lib.check(getattr(_lib.load(), "dsv_verify_%s_wire_rlc" % scheme)(
-        _p(sig), _p(pk), _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(accepted)))
-    return ok, bool(accepted.value)
+    return _host(scheme, "_wire", (sig, pk, m), rlc=True)
 
 
 def verify_double_wire(sig96, pk64, m):
-    sig, pk, m = _arr(sig96, 96), _arr(pk64, 64), _arr(m, 32)
-    n = _same_n(sig, pk, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_double_wire(_p(sig), _p(pk), _p(m), ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("double", "_wire", (sig96, pk64, m))
 
 
 def verify_vargen_wire(sig64, pk64, m):
-    sig, pk, m = _arr(sig64, 64), _arr(pk64, 64), _arr(m, 32)
-    n = _same_n(sig, pk, m)
-    ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_verify_vargen_wire(_p(sig), _p(pk), _p(m), ctypes.c_size_t(n), _p(ok)))
-    return ok
+    return _host("vargen", "_wire", (sig64, pk64, m))
 
 
 def stdrng_sign_inputs(seed, n, first_item=0):
@@ -563,14 +513,31 @@ def _stream_ptr(stream, dev=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _dev(scheme, form, arrays, ok, workspace, stream, rlc=None):
+    """dsv_verify_<scheme><form>_dev (rlc = (window_bits, accepted_out): ..._rlc_dev) over CUDA tensors.
+    Returns what the fast accept decided when the call waits for it (see _accepted_arg), else None."""
+    names, widths = _layout(scheme, form)
+    n, dev = _rows(*zip(arrays, widths, names))
+    if rlc is not None:
+        window_bits, accepted_out = rlc
+        arg, box = _accepted_arg(accepted_out, dev)
+        ws_need = (wire_rlc_workspace_bytes if form == "_wire" else rlc_workspace_bytes)(n, window_bits)
+        tail, name = [ctypes.c_int(window_bits), arg], "dsv_verify_%s%s_rlc_dev" % (scheme, form)
+    else:
+        box = None
+        ws_need = {"": workspace_bytes, "_ext": ext_workspace_bytes, "_mont": mont_workspace_bytes,
+                   "_wire": wire_workspace_bytes}[form](n)
+        tail, name = [], "dsv_verify_%s%s_dev" % (scheme, form)
+    _lib.check(getattr(_lib.load(), name)(
+        *[_tp(t, w) for t, w in zip(arrays, widths)], ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
+        _bytes_out(workspace, ws_need, dev, "workspace"), _stream_ptr(stream, dev), *tail))
+    return bool(box.value) if box is not None else None
+
+
 def verify_single_dev(u, R, PK, m, ok, workspace, stream=None):
     """Enqueue on `stream` (default: torch's current stream of the batch's device); does not
     synchronise."""
-    n, dev = _rows((u, 32, "u"), (R, 64, "R"), (PK, 64, "PK"), (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_single_dev(
-        _tp(u, 32), _tp(R, 64), _tp(PK, 64), _tp(m, 32), ctypes.c_size_t(n),
-        _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, workspace_bytes(n), dev, "workspace"),
-        _stream_ptr(stream, dev)))
+    _dev("single", "", (u, R, PK, m), ok, workspace, stream)
 
 
 def rlc_workspace_bytes(n, window_bits=0):
@@ -628,125 +595,70 @@ def _accepted_arg(accepted_out, dev):
     return ctypes.c_void_p(t.data_ptr()), None
 
 
-def _rlc(name, cols, ok, workspace, stream, window_bits, accepted_out=None):
-    n, dev = _rows(*cols)
-    arg, box = _accepted_arg(accepted_out, dev)
-    _lib.check(getattr(_lib.load(), name)(
-        *[_tp(t, w) for t, w, _ in cols], ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-        _bytes_out(workspace, rlc_workspace_bytes(n, window_bits), dev, "workspace"),
-        _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
-    return bool(box.value) if box is not None else None
-
-
 def verify_single_rlc_dev(u, R, PK, m, ok, workspace, stream=None, window_bits=0, accepted_out=None):
     """dsv_verify_single_rlc_dev: the verdict vector of verify_single_dev, through one aggregate test
     per group (or sub-group) when it is valid.  Enqueue-only when `accepted_out` (an int32 tensor on the
     device or in pinned host memory) is given: it receives 1 if every group was accepted by its aggregates
     once the stream gets there.  Without it the call waits for `stream` and returns that as a bool."""
-    return _rlc("dsv_verify_single_rlc_dev", ((u, 32, "u"), (R, 64, "R"), (PK, 64, "PK"), (m, 32, "m")),
-                ok, workspace, stream, window_bits, accepted_out)
+    return _dev("single", "", (u, R, PK, m), ok, workspace, stream, (window_bits, accepted_out))
 
 
 def verify_double_rlc_dev(u, R, Rp, PK, PKp, m, ok, workspace, stream=None, window_bits=0, accepted_out=None):
-    return _rlc("dsv_verify_double_rlc_dev", ((u, 32, "u"), (R, 64, "R"), (Rp, 64, "Rp"), (PK, 64, "PK"),
-                                               (PKp, 64, "PKp"), (m, 32, "m")), ok, workspace, stream, window_bits,
-                accepted_out)
+    return _dev("double", "", (u, R, Rp, PK, PKp, m), ok, workspace, stream, (window_bits, accepted_out))
 
 
 def verify_vargen_rlc_dev(u, R, PK, Gen, m, ok, workspace, stream=None, window_bits=0, accepted_out=None):
-    return _rlc("dsv_verify_vargen_rlc_dev", ((u, 32, "u"), (R, 64, "R"), (PK, 64, "PK"), (Gen, 64, "Gen"),
-                                               (m, 32, "m")), ok, workspace, stream, window_bits, accepted_out)
+    return _dev("vargen", "", (u, R, PK, Gen, m), ok, workspace, stream, (window_bits, accepted_out))
 
 
 def verify_double_dev(u, R, Rp, PK, PKp, m, ok, workspace, stream=None):
-    n, dev = _rows((u, 32, "u"), (R, 64, "R"), (Rp, 64, "Rp"), (PK, 64, "PK"), (PKp, 64, "PKp"),
-                   (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_double_dev(
-        _tp(u, 32), _tp(R, 64), _tp(Rp, 64), _tp(PK, 64), _tp(PKp, 64), _tp(m, 32),
-        ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-        _bytes_out(workspace, workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)))
+    _dev("double", "", (u, R, Rp, PK, PKp, m), ok, workspace, stream)
 
 
 def verify_vargen_dev(u, R, PK, Gen, m, ok, workspace, stream=None):
-    n, dev = _rows((u, 32, "u"), (R, 64, "R"), (PK, 64, "PK"), (Gen, 64, "Gen"), (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_vargen_dev(
-        _tp(u, 32), _tp(R, 64), _tp(PK, 64), _tp(Gen, 64), _tp(m, 32), ctypes.c_size_t(n),
-        _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, workspace_bytes(n), dev, "workspace"),
-        _stream_ptr(stream, dev)))
+    _dev("vargen", "", (u, R, PK, Gen, m), ok, workspace, stream)
 
 
 def verify_single_ext_dev(u, R_uvz, PK_uvz, m, ok, workspace, stream=None):
-    n, dev = _rows((u, 32, "u"), (R_uvz, 96, "R_uvz"), (PK_uvz, 96, "PK_uvz"), (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_single_ext_dev(
-        _tp(u, 32), _tp(R_uvz, 96), _tp(PK_uvz, 96), _tp(m, 32), ctypes.c_size_t(n),
-        _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, ext_workspace_bytes(n), dev, "workspace"),
-        _stream_ptr(stream, dev)))
+    _dev("single", "_ext", (u, R_uvz, PK_uvz, m), ok, workspace, stream)
 
 
 def verify_double_ext_dev(u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m, ok, workspace, stream=None):
-    n, dev = _rows((u, 32, "u"), (R_uvz, 96, "R_uvz"), (Rp_uvz, 96, "Rp_uvz"), (PK_uvz, 96, "PK_uvz"),
-                   (PKp_uvz, 96, "PKp_uvz"), (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_double_ext_dev(
-        _tp(u, 32), _tp(R_uvz, 96), _tp(Rp_uvz, 96), _tp(PK_uvz, 96), _tp(PKp_uvz, 96), _tp(m, 32),
-        ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-        _bytes_out(workspace, ext_workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)))
+    _dev("double", "_ext", (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m), ok, workspace, stream)
 
 
 def verify_vargen_ext_dev(u, R_uvz, PK_uvz, Gen_uvz, m, ok, workspace, stream=None):
-    n, dev = _rows((u, 32, "u"), (R_uvz, 96, "R_uvz"), (PK_uvz, 96, "PK_uvz"), (Gen_uvz, 96, "Gen_uvz"),
-                   (m, 32, "m"))
-    _lib.check(_lib.load().dsv_verify_vargen_ext_dev(
-        _tp(u, 32), _tp(R_uvz, 96), _tp(PK_uvz, 96), _tp(Gen_uvz, 96), _tp(m, 32), ctypes.c_size_t(n),
-        _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, ext_workspace_bytes(n), dev, "workspace"),
-        _stream_ptr(stream, dev)))
+    _dev("vargen", "_ext", (u, R_uvz, PK_uvz, Gen_uvz, m), ok, workspace, stream)
 
 
 def mont_workspace_bytes(n):
     return int(_lib.load().dsv_mont_workspace_bytes(ctypes.c_size_t(n)))
 
 
-def _mont_dev(name, widths, arrays, ok, workspace, stream):
-    names = ["col%d" % k for k in range(len(arrays))]
-    n, dev = _rows(*[(a, w, nm) for a, w, nm in zip(arrays, widths, names)])
-    _lib.check(getattr(_lib.load(), name)(
-        *([_tp(a, w) for a, w in zip(arrays, widths)] +
-          [ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-           _bytes_out(workspace, mont_workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)])))
-
-
 def verify_single_mont_dev(u, R_uvz, PK_uvz, m, ok, workspace, stream=None):
     """Montgomery limbs (the Rust types' in-memory form) resident in HBM."""
-    _mont_dev("dsv_verify_single_mont_dev", (32, 96, 96, 32), (u, R_uvz, PK_uvz, m), ok, workspace, stream)
+    _dev("single", "_mont", (u, R_uvz, PK_uvz, m), ok, workspace, stream)
 
 
 def verify_double_mont_dev(u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m, ok, workspace, stream=None):
-    _mont_dev("dsv_verify_double_mont_dev", (32, 96, 96, 96, 96, 32),
-              (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m), ok, workspace, stream)
+    _dev("double", "_mont", (u, R_uvz, Rp_uvz, PK_uvz, PKp_uvz, m), ok, workspace, stream)
 
 
 def verify_vargen_mont_dev(u, R_uvz, PK_uvz, Gen_uvz, m, ok, workspace, stream=None):
-    _mont_dev("dsv_verify_vargen_mont_dev", (32, 96, 96, 96, 32), (u, R_uvz, PK_uvz, Gen_uvz, m), ok,
-              workspace, stream)
-
-
-def _wire_dev(name, sig, sig_w, pk, pk_w, m, ok, workspace, stream):
-    n, dev = _rows((sig, sig_w, "sig"), (pk, pk_w, "pk"), (m, 32, "m"))
-    _lib.check(getattr(_lib.load(), name)(
-        _tp(sig, sig_w), _tp(pk, pk_w), _tp(m, 32), ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-        _bytes_out(workspace, wire_workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)))
+    _dev("vargen", "_mont", (u, R_uvz, PK_uvz, Gen_uvz, m), ok, workspace, stream)
 
 
 def verify_single_wire_dev(sig64, pk32, m, ok, workspace, stream=None):
     """Serialized records resident in HBM: Signature (64 B) / PublicKey (32 B) per item."""
-    _wire_dev("dsv_verify_single_wire_dev", sig64, 64, pk32, 32, m, ok, workspace, stream)
+    _dev("single", "_wire", (sig64, pk32, m), ok, workspace, stream)
 
 
 def verify_double_wire_dev(sig96, pk64, m, ok, workspace, stream=None):
-    _wire_dev("dsv_verify_double_wire_dev", sig96, 96, pk64, 64, m, ok, workspace, stream)
+    _dev("double", "_wire", (sig96, pk64, m), ok, workspace, stream)
 
 
 def verify_vargen_wire_dev(sig64, pk64, m, ok, workspace, stream=None):
-    _wire_dev("dsv_verify_vargen_wire_dev", sig64, 64, pk64, 64, m, ok, workspace, stream)
+    _dev("vargen", "_wire", (sig64, pk64, m), ok, workspace, stream)
 
 
 def wire_rlc_workspace_bytes(n, window_bits=0):
@@ -756,20 +668,10 @@ def wire_rlc_workspace_bytes(n, window_bits=0):
     return b
 
 
-_WIRE_WIDTHS = {"single": (64, 32), "double": (96, 64), "vargen": (64, 64)}
-
-
 def verify_wire_rlc_dev(scheme, sig, pk, m, ok, workspace, stream=None, window_bits=0):
     """dsv_verify_*_wire_rlc_dev: serialized records resident in HBM through the batch fast accept.
     Blocks on `stream`; returns True if the aggregate decided every group."""
-    sw, pw = _WIRE_WIDTHS[scheme]
-    n, dev = _rows((sig, sw, "sig"), (pk, pw, "pk"), (m, 32, "m"))
-    accepted = ctypes.c_int(0)
-    _lib.check(getattr(_lib.load(), "dsv_verify_%s_wire_rlc_dev" % scheme)(
-        _tp(sig, sw), _tp(pk, pw), _tp(m, 32), ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
-        _bytes_out(workspace, wire_rlc_workspace_bytes(n, window_bits), dev, "workspace"),
-        _stream_ptr(stream, dev), ctypes.c_int(window_bits), ctypes.byref(accepted)))
-    return bool(accepted.value)
+    return _dev(scheme, "_wire", (sig, pk, m), ok, workspace, stream, (window_bits, None))
 
 
 def verify_core_dev(u, c, valid, PK, R, ok, workspace, which=0, accumulate=False, stream=None):
