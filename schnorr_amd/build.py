@@ -121,6 +121,31 @@ def build_variant(name, force=False, verbose=False):
     return build(force=force, verbose=verbose, out=out, unit_flags=VARIANTS[name])
 
 
+PROBE_SRC = os.path.join(ROOT, "tests", "gpu_probe", "limb_probe.hip")
+
+
+def probe_path():
+    return os.path.join(HERE, "libdsv_probe.so")
+
+
+def build_probe(force=False, verbose=False):
+    """schnorr_amd/libdsv_probe.so: the test-only limb probe (tests/gpu_probe/limb_probe.hip) — the
+    device functions of csrc/*.h in kernels of its own, compiled with the engine's FLAGS / ARCH; not
+    part of libdsv.so (git-ignored, travels to the GPU box like it)"""
+    out = probe_path()
+    deps = _deps() + [PROBE_SRC]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps if os.path.exists(d)):
+        return out
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise RuntimeError("hipcc not found: cannot build the limb probe")
+    cmd = [hipcc] + FLAGS + ["-shared", "-I", CSRC, PROBE_SRC, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def _includes(path, seen):
     """the translation unit and every local header it includes, transitively"""
     import re

@@ -26,14 +26,6 @@ DSV_DEV QExt qext_mul16(QExt p, int q) {
   qext_double<true>(p, q);
   return p;
 }
-// value held by the lane four lanes up (quad 1 of an octet -> quad 0), for every limb
-DSV_DEV Fe from_upper_quad(const Fe& x) {
-  Fe r;
-#pragma unroll
-  for (int i = 0; i < NL; i++)
-    r.l[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)x.l[i], 0x104 /* row_shl:4 */, 0xf, 0xf, true);
-  return r;
-}
 
 template <int NCHAIN>
 __global__ void __launch_bounds__(kQuadBlock)
@@ -121,14 +113,8 @@ k_verify_fixed_half_oct(const uint8_t* __restrict__ u, const uint8_t* __restrict
         qext_add_aniels(acc, q, load_aniels(op.table, j + (upper ? 8 : 0), d));
       }
     }
-    {  // quad 0 += quad 1: the upper half as an extended niels operand, moved four lanes down
-      Niels nb;
-      nb.vpu = from_upper_quad(fe_carry(fe_add(acc.v, acc.u)));
-      nb.vmu = from_upper_quad(fe_sub2(acc.v, acc.u));
-      nb.z = from_upper_quad(acc.z);
-      nb.t2d = from_upper_quad(fe_mul(acc.t, fe_const(kD2)));
-      qext_add_niels(acc, q, nb);  // (meaningful in quad 0 only)
-    }
+    // quad 0 += quad 1: the upper half as an extended niels operand, moved four lanes down
+    qext_add_niels(acc, q, qext_upper_niels(acc));  // (meaningful in quad 0 only)
     good &= (bool)((int)fe_is_zero_canon(fe_canon(acc.u)) & (int)fe_equal(acc.v, acc.z));
     if (NCHAIN > 1) __builtin_amdgcn_wave_barrier();  // table slots are rebuilt next round
   }

@@ -111,4 +111,23 @@ DSV_DEV void qext_add_aniels(QExt& p, int q, const ANiels& n) {
   qext_add_tail(p, q, a, b, c, d);
 }
 
+// value held by the lane four lanes up (quad 1 of an octet -> quad 0), for every limb
+DSV_DEV Fe from_upper_quad(const Fe& x) {
+  Fe r;
+#pragma unroll
+  for (int i = 0; i < NL; i++)
+    r.l[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)x.l[i], 0x104 /* row_shl:4 */, 0xf, 0xf, true);
+  return r;
+}
+// octet combine of k_quad.hip: the accumulator of quad 1 as an extended niels operand of quad 0
+// (z as the accumulator holds it, 2d*t from the single product t)
+DSV_DEV Niels qext_upper_niels(const QExt& acc) {
+  Niels nb;
+  nb.vpu = from_upper_quad(fe_carry(fe_add(acc.v, acc.u)));
+  nb.vmu = from_upper_quad(fe_sub2(acc.v, acc.u));
+  nb.z = from_upper_quad(acc.z);
+  nb.t2d = from_upper_quad(fe_mul(acc.t, fe_const(kD2)));
+  return nb;
+}
+
 }  // namespace dsv

@@ -342,18 +342,32 @@ def mfma_operand_ok(x, what):
     _check(x.v < (1 << 256), what + ": value exceeds 2^256")
 
 
-def hades_full_round(s, rc):
+def _stage(stages, name, x):
+    """per-stage bounds of prove_hades (joined over every round and word)"""
+    if stages is not None:
+        stages[name] = join(stages[name], x) if name in stages else x
+
+
+def hades_full_round(s, rc, stages=None):
+    for x in s:
+        _stage(stages, "round_in", x)
     s = [add(s[k], rc[k]) for k in range(5)]
+    for x in s:
+        _stage(stages, "sbox_in", x)
     s = [sbox(x) for x in s]
     for x in s:
         mfma_operand_ok(x, "S-box output")
-    return [mfma_row() for _ in range(5)]
+        _stage(stages, "mds_operand", x)
+    out = [mfma_row() for _ in range(5)]
+    _stage(stages, "row", out[0])
+    return out
 
 
-def hades_partial_rounds(s):
+def hades_partial_rounds(s, stages=None):
     """hades29.h: hades_partial_rounds — every a_r after a_0 is a row, every z_r an S-box output"""
     for x in s:
         mfma_operand_ok(x, "state entering the partial rounds")
+        _stage(stages, "partial_in", x)
     k0 = _load_row("DSV_HADES_K0_HOST")
     a = add(s[4], k0)
     # fe_cond_sub(fe_ripple(.), q): ripple needs limbs < 2^31; the result is < max(q, sum - q)
@@ -362,40 +376,52 @@ def hades_partial_rounds(s):
     a0 = B([M29] * (NL - 1) + [a.v >> (LB * (NL - 1))], max(Q, a.v - Q))
     mfma_operand_ok(a0, "a_0")
     mfma_operand_ok(sbox(a0), "z_0")
+    _stage(stages, "sbox_in", a0)
     z = sbox(mfma_row())          # rounds 1..58: a_r is a row
     mfma_operand_ok(z, "z_r")
-    return [mfma_row() for _ in range(5)]
+    _stage(stages, "sbox_in", mfma_row())
+    _stage(stages, "mds_operand", join(sbox(a0), z))
+    out = [mfma_row() for _ in range(5)]
+    _stage(stages, "row", out[0])
+    return out
 
 
-def hades_permute(s):
+def hades_permute(s, stages=None):
     """hades29.h: hades_permute with the ACTUAL round constants (exact limbs) and worst-case state"""
     rc = _load_table("DSV_HADES_RC_HOST")
     s = list(s)
+    for x in s:
+        _stage(stages, "permute_in", x)
     for r in range(4):
-        s = hades_full_round(s, rc[5 * r:5 * r + 5])
-    s = hades_partial_rounds(s)
+        s = hades_full_round(s, rc[5 * r:5 * r + 5], stages)
+    s = hades_partial_rounds(s, stages)
     for r in range(4):
-        s = hades_full_round(s, rc[5 * (4 + 59 + r):5 * (4 + 59 + r) + 5])
+        s = hades_full_round(s, rc[5 * (4 + 59 + r):5 * (4 + 59 + r) + 5], stages)
     return s
 
 
 def prove_hades():
     """k_challenge (k_hash.hip): the 3-input and the 5-input sponge on worst-case inputs (fe_to_mont of
     any canonical word; the generic first round is the worst case of the constant-folded one), then
-    the truncation's fe_from_mont (fe_canon needs < 16 q and limbs < 2^31)."""
+    the truncation's fe_from_mont (fe_canon needs < 16 q and limbs < 2^31).  Besides the two hash
+    outputs it returns the per-stage bounds it established, each joined over all rounds and words:
+    permute_in (states entering a permutation), round_in (entering a full round), sbox_in (S-box
+    inputs), mds_operand (S-box outputs = operands of the matrix-core layers), row (a row back from
+    the matrix cores) and partial_in (the state entering the partial rounds)."""
     m = mul(canonical(), canonical())
     zero, one = B([0] * NL), canonical()
-    out3 = hades_permute([zero, m, m, m, one])
-    s = hades_permute([zero, m, m, m, m])
+    stages = {}
+    out3 = hades_permute([zero, m, m, m, one], stages)
+    s = hades_permute([zero, m, m, m, m], stages)
     s[1] = add(s[1], m)
     s[2] = add(s[2], one)
-    out5 = hades_permute(s)
+    out5 = hades_permute(s, stages)
     for o in (out3[1], out5[1]):
         h = mul(o, B([1] + [0] * (NL - 1)))
         for x in h.l:
             _check(x < (1 << 31), "fe_ripple input limb exceeds 2^31")
         _check(h.v < 16 * Q, "fe_canon input exceeds 16 q")
-    return {"hash3": out3[1], "hash5": out5[1]}
+    return dict(stages, hash3=out3[1], hash5=out5[1])
 
 
 # ---- decode29.h / k_decompress (k_misc.hip) ------------------------------------------------------
@@ -515,3 +541,78 @@ def prove_fast_accept():
             return {"acc": acc, "rounds": rnd}
         acc = nxt
     raise OverflowError_("xp bounds keep growing")
+
+
+# ---- quad29.h / k_quad.hip: four lanes per point, r02-r03 ----------------------------------------
+def qext_double(p, want_t):
+    """quad29.h: the four products are general multiplications (lanes 0..2: u*u, v*v, z*z; lane 3:
+    u*v), 2uv is the doubled product (not ext_two_uv); t = cu * vpu only when asked for"""
+    uu, vv, zz, uv = mul(p["u"], p["u"]), mul(p["v"], p["v"]), mul(p["z"], p["z"]), mul(p["u"], p["v"])
+    zz2 = dbl(zz)
+    cu = dbl(uv)
+    vpu = add(vv, uu)
+    vmu = sub_raw(vv, uu, 2)
+    ct = sub(zz2, vmu, "4w")
+    return {"u": mul(cu, ct), "v": mul(vpu, vmu), "z": mul(vmu, ct), "t": mul(cu, vpu) if want_t else p["t"]}
+
+
+def qext_add_tail(a, b, c, d):
+    cu = sub_raw(b, a, 2)
+    cv = add(b, a)
+    cz = add(d, c)
+    ct = sub(d, c, 2)
+    return {"u": mul(cu, ct), "v": mul(cv, cz), "z": mul(cz, ct), "t": mul(cu, cv)}
+
+
+def qext_add_niels(p, n):
+    a = mul(sub_raw(p["v"], p["u"], 2), n["vmu"])
+    b = mul(add(p["v"], p["u"]), n["vpu"])
+    c = mul(p["t"], n["t2d"])                         # the single product t straight into t2d
+    d = dbl(mul(p["z"], n["z"]))
+    return qext_add_tail(a, b, c, d)
+
+
+def qext_add_aniels(p, n):
+    a = mul(sub_raw(p["v"], p["u"], 2), n["vmu"])
+    b = mul(add(p["v"], p["u"]), n["vpu"])
+    c = mul(p["t"], n["t2d"])
+    d = dbl(p["z"])
+    return qext_add_tail(a, b, c, d)
+
+
+def octet_niels(acc, d2):
+    """k_verify_fixed_half_oct: the upper quad's accumulator as an extended niels operand (moved four
+    lanes down by from_upper_quad: a register move, bounds unchanged); z is the accumulator's own"""
+    return {"vpu": carry(add(acc["v"], acc["u"])), "vmu": sub(acc["v"], acc["u"], 2), "z": acc["z"],
+            "t2d": mul(acc["t"], d2)}
+
+
+def prove_quad_group_law(max_rounds=40, octet_niels=octet_niels):
+    """k_verify_fixed_half_oct (k_quad.hip) on quad29.h: from the identity, variable-base niels entries
+    (the tables are built by jubjub29.h code: the niels invariant of prove_group_law), then any
+    sequence of qext_double<false / true> (qext_mul16) and qext_add_niels, any number of
+    qext_add_aniels of fixed-base entries (the group-law proof's fixed-table bounds), the octet
+    combine (quad 1's accumulator as an extended niels operand into quad 0's) and the final
+    fe_canon(acc.u) / fe_equal(acc.v, acc.z).  Built like prove_fast_accept's xp_* fixpoint."""
+    inv = prove_group_law()
+    niels = inv["niels"]
+    d2 = canonical()
+    fixed = {"vpu": canonical(), "vmu": canonical(), "t2d": canonical()}
+    one = const(_load("DSV_ONE"))
+    zero = B([0] * NL)
+    acc = {"u": zero, "v": one, "z": one, "t": zero}
+    for rnd in range(max_rounds):
+        nxt = join_pt(acc, qext_double(acc, False))
+        nxt = join_pt(nxt, qext_double(acc, True))
+        nxt = join_pt(nxt, qext_add_niels(acc, niels))
+        nxt = join_pt(nxt, qext_add_aniels(acc, fixed))
+        if rnd >= 2:
+            nxt = {k: widen(x) for k, x in nxt.items()}
+        if leq_pt(nxt, acc):
+            nb = octet_niels(acc, d2)
+            out = qext_add_niels(acc, nb)
+            canon_ok(out["u"])                         # fe_is_zero_canon(fe_canon(acc.u))
+            equal_ok(out["v"], out["z"])
+            return {"acc": acc, "octet_niels": nb, "out": out, "rounds": rnd}
+        acc = nxt
+    raise OverflowError_("quad bounds keep growing: no fixpoint after %d rounds" % max_rounds)

@@ -185,7 +185,44 @@ def to_mont(plain):
 
 
 def equal(a, b):
-    return val(canon(sub(a, b, 8))) == 0
+    return is_zero_canon(canon(sub(a, b, 8)))
+
+
+def neg2(b):
+    return sub([0] * NL, b, 2)
+
+
+def is_zero_canon(a):
+    return all(x == 0 for x in a)
+
+
+def from_words_plain(w):
+    """fe_from_words_plain: 8 little-endian u32 words -> limbs (bit-exact, no range check)"""
+    r = []
+    for i in range(NL):
+        bit = LB * i
+        wi, sh = bit >> 5, bit & 31
+        lo = w[wi] >> sh
+        if sh > 3 and wi + 1 < 8:
+            lo |= (w[wi + 1] << (32 - sh)) & (U32 - 1)
+        r.append(lo & M29)
+    return r
+
+
+def to_words_plain(a):
+    """fe_to_words_plain: limbs -> 8 words by OR of shifted limbs (bit-exact also for limbs >= 2^29)"""
+    w = []
+    for k in range(8):
+        lo_limb, off = (32 * k) // LB, (32 * k) % LB
+        v = a[lo_limb] >> off
+        have = LB - off
+        if lo_limb + 1 < NL:
+            v |= (a[lo_limb + 1] << have) & (U32 - 1)
+        have += LB
+        if have < 32 and lo_limb + 2 < NL:
+            v |= (a[lo_limb + 2] << have) & (U32 - 1)
+        w.append(v)
+    return w
 
 
 # ---- points ------------------------------------------------------------------------------
@@ -221,6 +258,12 @@ def ext_double_affine(u, v):
     return {"u": mul(cu, ct), "v": mul(vpu, vmu), "z": mul(vmu, ct), "t1": cu, "t2": vpu}
 
 
+def ext_double_uvz(u, v, z):
+    """jubjub29.h: the doubling that keeps only (u, v, z)"""
+    r = ext_double({"u": u, "v": v, "z": z})
+    return r["u"], r["v"], r["z"]
+
+
 def _add_tail(a, b, c, d):
     cu = sub_raw(b, a, 2)
     cv = add(b, a)
@@ -245,12 +288,21 @@ def ext_add_aniels(p, n):
     return _add_tail(a, b, c, d)
 
 
-def ext_add_sub_aniels(p, n):
+def ext_add_aniels_t(p, tt, n):
+    """jubjub29.h: ext_add_aniels with the product tt = t1 * t2 handed in"""
+    a = mul(sub_raw(p["v"], p["u"], 2), n["vmu"])
+    b = mul(add(p["v"], p["u"]), n["vpu"])
+    c = mul(tt, n["t2d"])
+    d = dbl(p["z"])
+    return _add_tail(a, b, c, d)
+
+
+def ext_add_sub_aniels(p, n, tt=None):
     """jubjub29.h: ext_add_sub_aniels_t — (p + n, p - n) sharing c, d and z"""
     pm, pp = sub_raw(p["v"], p["u"], 2), add(p["v"], p["u"])
     a, b = mul(pm, n["vmu"]), mul(pp, n["vpu"])
     a2, b2 = mul(pm, n["vpu"]), mul(pp, n["vmu"])
-    c = mul(mul(p["t1"], p["t2"]), n["t2d"])
+    c = mul(mul(p["t1"], p["t2"]) if tt is None else tt, n["t2d"])
     d = dbl(p["z"])
     cu, cv, cz, ct = sub_raw(b, a, 2), add(b, a), add(d, c), sub(d, c, 2)
     z = mul(cz, ct)
@@ -279,6 +331,75 @@ def ext_from_niels(n):
 def ext_to_niels(p):
     return {"vpu": carry(add(p["v"], p["u"])), "vmu": sub(p["v"], p["u"], 2), "z": p["z"],
             "t2d": mul(mul(p["t1"], p["t2"]), D2)}
+
+
+def ext_to_niels_t(p, tt):
+    return {"vpu": carry(add(p["v"], p["u"])), "vmu": sub(p["v"], p["u"], 2), "z": p["z"],
+            "t2d": mul(tt, D2)}
+
+
+def ext_eq_affine(p, ru, rv):
+    """jubjub29.h: u1 == ru * z1 and v1 == rv * z1"""
+    return equal(p["u"], mul(ru, p["z"])) and equal(p["v"], mul(rv, p["z"]))
+
+
+# ---- quad29.h / k_quad.hip: four lanes per point, the single product t = t1 * t2 ------------
+# Every lane of a quad holds the whole record {u, v, z, t}; the four products of a step are one
+# fe_mul per lane (never fe_sqr), broadcast through the quad.  The functions below are the record
+# every lane holds afterwards.
+def qext_identity():
+    return {"u": [0] * NL, "v": list(ONE), "z": list(ONE), "t": [0] * NL}
+
+
+def qext_double(p, want_t):
+    uu, vv, zz, uv = mul(p["u"], p["u"]), mul(p["v"], p["v"]), mul(p["z"], p["z"]), mul(p["u"], p["v"])
+    zz2 = dbl(zz)
+    cu = dbl(uv)
+    vpu = add(vv, uu)
+    vmu = sub_raw(vv, uu, 2)
+    ct = sub(zz2, vmu, "4w")
+    return {"u": mul(cu, ct), "v": mul(vpu, vmu), "z": mul(vmu, ct),
+            "t": mul(cu, vpu) if want_t else p["t"]}
+
+
+def qext_mul16(p):
+    for _ in range(3):
+        p = qext_double(p, False)
+    return qext_double(p, True)
+
+
+def qext_add_tail(a, b, c, d):
+    cu = sub_raw(b, a, 2)
+    cv = add(b, a)
+    cz = add(d, c)
+    ct = sub(d, c, 2)
+    return {"u": mul(cu, ct), "v": mul(cv, cz), "z": mul(cz, ct), "t": mul(cu, cv)}
+
+
+def qext_add_niels(p, n):
+    a = mul(sub_raw(p["v"], p["u"], 2), n["vmu"])
+    b = mul(add(p["v"], p["u"]), n["vpu"])
+    c = mul(p["t"], n["t2d"])
+    d = dbl(mul(p["z"], n["z"]))
+    return qext_add_tail(a, b, c, d)
+
+
+def qext_add_aniels(p, n):
+    a = mul(sub_raw(p["v"], p["u"], 2), n["vmu"])
+    b = mul(add(p["v"], p["u"]), n["vpu"])
+    c = mul(p["t"], n["t2d"])
+    d = dbl(p["z"])
+    return qext_add_tail(a, b, c, d)
+
+
+def octet_niels(acc):
+    """k_quad.hip, k_verify_fixed_half_oct: the upper quad's accumulator as an extended niels operand"""
+    return {"vpu": carry(add(acc["v"], acc["u"])), "vmu": sub(acc["v"], acc["u"], 2), "z": acc["z"],
+            "t2d": mul(acc["t"], D2)}
+
+
+def octet_combine(lower, upper):
+    return qext_add_niels(lower, octet_niels(upper))
 
 
 def affine_of(p):

@@ -53,3 +53,45 @@ def test_batch_fast_accept_field_code_cannot_overflow():
     operations (running point with tt = t1 * t2) stay inside the group law's proven invariants"""
     out = FB.prove_fast_accept()
     assert out["rounds"] < 12 and out["acc"]["u"].v < 2 * FB.Q
+
+
+def test_hades_stage_bounds_are_returned_and_self_consistent():
+    """prove_hades() also hands out the per-stage bounds the device limb tests draw ceilings from: the
+    S-box proves on the joined S-box input bound, and its output is a valid matrix-core operand"""
+    out = FB.prove_hades()
+    for k in ("permute_in", "round_in", "sbox_in", "mds_operand", "row", "partial_in"):
+        assert isinstance(out[k], FB.B)
+    FB.mfma_operand_ok(FB.sbox(out["sbox_in"]), "S-box of the joined input bound")
+    assert FB.leq(out["row"], FB.mfma_row())
+
+
+def test_quad_group_law_bounds_reach_a_fixpoint_without_overflow():
+    """quad29.h / k_quad.hip: the four-lanes-per-point chain of k_verify_fixed_half_oct (qext_mul16,
+    qext_add_niels of variable-base entries, qext_add_aniels of fixed-base entries, the octet combine
+    and the final comparisons) cannot overflow for any input inside the group law's invariants"""
+    out = FB.prove_quad_group_law()
+    for k in ("u", "v", "z", "t"):
+        assert out["acc"][k].l[0] <= FB.M29 + 1
+        assert all(x <= FB.M29 for x in out["acc"][k].l[1:8])
+        assert out["acc"][k].v < 2 * FB.Q
+        assert out["out"][k].v < 2 * FB.Q
+    assert out["rounds"] < 12
+
+
+def test_quad_prover_rejects_a_broken_variant():
+    """Sanity of the quad proof: an octet combine whose v - u operand skips its carry pass (fe_sub2_raw
+    for fe_sub2) multiplies two un-carried operands and must be refused"""
+    def bad_octet_niels(acc, d2):
+        n = FB.octet_niels(acc, d2)
+        n["vmu"] = FB.sub_raw(acc["v"], acc["u"], 2)
+        return n
+
+    with pytest.raises(FB.OverflowError_):
+        FB.prove_quad_group_law(octet_niels=bad_octet_niels)
+    # and a quad doubling whose ct = 2 z^2 - (v^2 - u^2) skips fe_sub4w's carry pass
+    n = FB.mul(FB.canonical(), FB.canonical())
+    p = {"u": n, "v": n, "z": n, "t": n}
+    uu, vv = FB.mul(p["u"], p["u"]), FB.mul(p["v"], p["v"])
+    vmu = FB.sub_raw(vv, uu, 2)
+    with pytest.raises(FB.OverflowError_):
+        FB.mul(vmu, FB.sub_raw(FB.dbl(FB.mul(p["z"], p["z"])), vmu, "4w"))

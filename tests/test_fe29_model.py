@@ -140,3 +140,63 @@ def test_identity_and_torsion_through_the_formulas():
     assert F.affine_of(s) == (0, 1)
     s = F.ext_add_niels(ident, F.ext_to_niels(ident))
     assert F.affine_of(s) == (0, 1)
+
+
+def _qext_of(P):
+    """a projective representative of the affine point P as a quad29.h record {u, v, z, t = u v / z}"""
+    z = rnd.randrange(1, F.Q)
+    u, v = P[0] * z % F.Q, P[1] * z % F.Q
+    return {"u": F.to_mont_int(u), "v": F.to_mont_int(v), "z": F.to_mont_int(z),
+            "t": F.to_mont_int(P[0] * P[1] % F.Q * z % F.Q)}
+
+
+def _qaffine(p):
+    return F.affine_of({"u": p["u"], "v": p["v"], "z": p["z"]})
+
+
+def test_quad_group_law_matches_the_affine_model():
+    """quad29.h (qext_double<true/false>, qext_add_niels, qext_add_aniels) and the octet combine of
+    k_quad.hip against pymodel's point arithmetic, including the identity, the point of order 2 and a
+    point with an order-8 component; t must stay u v / z wherever it is produced"""
+    import test_halfgcd as TH
+    t8 = TH.order8_point()
+    pts = [M.IDENTITY, (0, F.Q - 1), t8, M.padd(M.pmul(M.GEN, 77), t8)]
+    pts += [M.pmul(M.GEN, rnd.randrange(1, M.R_ORDER)) for _ in range(3)]
+    for P in pts:
+        p = _qext_of(P)
+        d = F.qext_double(p, True)
+        assert _qaffine(d) == M.pmul(P, 2)
+        assert F.equal(F.mul(d["t"], d["z"]), F.mul(d["u"], d["v"]))
+        assert F.qext_double(p, False)["t"] == p["t"]
+        m16 = F.qext_mul16(p)
+        assert _qaffine(m16) == M.pmul(P, 16)
+        assert F.equal(F.mul(m16["t"], m16["z"]), F.mul(m16["u"], m16["v"]))
+        for R in (P, M.pneg(P), M.pmul(M.GEN, rnd.randrange(1, M.R_ORDER)), t8, M.IDENTITY):
+            r = F.ext_from_affine(F.to_mont_int(R[0]), F.to_mont_int(R[1]))
+            n = F.ext_to_niels(F.ext_double(r))            # a projective niels entry, 2R
+            s = F.qext_add_niels(p, n)
+            assert _qaffine(s) == M.padd(P, M.pmul(R, 2))
+            assert F.equal(F.mul(s["t"], s["z"]), F.mul(s["u"], s["v"]))
+            an = {k: F.ext_to_niels(r)[k] for k in ("vpu", "vmu", "t2d")}
+            assert _qaffine(F.qext_add_aniels(p, an)) == M.padd(P, R)
+            # octet combine: quad 0's accumulator += quad 1's, both projective
+            assert _qaffine(F.octet_combine(s, _qext_of(R))) == M.padd(M.padd(P, M.pmul(R, 2)), R)
+    # a whole k_verify_fixed_half_oct-shaped chain from the identity
+    P = M.pmul(M.GEN, rnd.randrange(1, M.R_ORDER))
+    e = F.ext_from_affine(F.to_mont_int(P[0]), F.to_mont_int(P[1]))
+    tbl = [None, F.ext_to_niels(e)]
+    cur = e
+    for _ in range(2, 9):
+        cur = F.ext_add_niels(cur, tbl[1])
+        tbl.append(F.ext_to_niels(cur))
+    k = rnd.randrange(1 << 40)
+    acc = F.qext_add_niels(F.qext_identity(), tbl[(k >> 36) & 7 or 1])
+    want = M.pmul(P, (k >> 36) & 7 or 1)
+    for j in range(8, -1, -1):
+        dgt = (k >> (4 * j)) & 7 or 1
+        acc = F.qext_add_niels(F.qext_mul16(acc), tbl[dgt])
+        want = M.padd(M.pmul(want, 16), M.pmul(P, dgt))
+    assert _qaffine(acc) == want
+    fin = F.octet_combine(acc, F.qext_add_niels(F.qext_identity(), F.ext_to_niels(F.ext_from_affine(
+        F.to_mont_int(M.pneg(want)[0]), F.to_mont_int(M.pneg(want)[1])))))
+    assert F.is_zero_canon(F.canon(fin["u"])) and F.equal(fin["v"], fin["z"])
