@@ -515,6 +515,62 @@ int dsv_stdrng_sign_inputs_dev(uint64_t seed, size_t first_item, size_t n, void 
 int dsv_stdrng_vargen_inputs_dev(uint64_t seed, size_t first_item, size_t n, void *sk, void *g,
                                  void *m, void *r, void *stream);
 
+/* ---- registered key sets: verify by key index ------------------------------------------------
+ * Many messages signed under few keys (validators, committees, busy accounts): each registered key gets
+ * fixed-base window tables of its points, so c*PK (and, var-generator scheme, u*Gen) become table
+ * additions with no doubling: u*Gen + c*PK == R is evaluated as written.
+ * scheme: 0 single (key = PK), 1 double (PK, PK'), 2 var-generator (PK, Gen); dsv_keyset_bytes(scheme, k)
+ * device bytes per set (594 432 B per point and key; no GPU needed; 0 for an unknown scheme).
+ *   create      : host arrays of k affine points (64 B each): pk_uv = PK, pk2_uv = PK' / Gen (NULL for
+ *                 single); blocks until the tables are built.
+ *   create_wire : pk_bytes = the reference's key records (PublicKey 32 B, PublicKeyDouble / PublicKeyVarGen
+ *                 64 B), decoded by the device decoder of the *_wire entry points (same accepted encodings).
+ * Contract:
+ *   Ownership   a key set belongs to the device that was current when it was created (it must be
+ *               initialised); it is immutable after creation, and any number of concurrent calls may read it.
+ *   Verdicts    ok[i] equals the unkeyed entry point's verdict on (u, R, PK[key_idx[i]], m) for every input
+ *               the reference's types can hold.
+ *   Key indices key_idx is uint32 per item; an index >= k gives ok = 0 and never a fault.
+ *   Invalid keys a key with a coordinate >= q, a point off the curve, or (wire form) an encoding from_bytes
+ *               rejects is recorded as invalid (dsv_keyset_key_ok: 0); every item under it gets ok = 0.
+ *   Workspace   the _dev calls take workspace_bytes >= dsv_keyed_workspace_bytes(n) (device, 256-byte
+ *               aligned); a shorter one returns DSV_ERR_INVALID_ARGUMENT and launches nothing.
+ *   Arguments   a scheme mismatch, a key set used on another device (the owner of `ok`), or a NULL pointer
+ *               with n > 0 returns DSV_ERR_INVALID_ARGUMENT; n = 0 returns DSV_OK.
+ *   Enqueue-only the _dev calls never synchronise and order on `stream` like every other _dev entry point
+ *               (the challenge hash, then the keyed kernel).
+ *   Host forms  take host arrays, stage in chunks on the key set's device and block.
+ *   Shutdown    dsv_shutdown[_device] frees the device memory of the live key sets of that device and marks
+ *               them dead: verify on a dead set returns DSV_ERR_NOT_INITIALIZED, dsv_keyset_destroy releases
+ *               the handle and returns DSV_OK.  dsv_keyset_destroy waits for the device's work first. */
+typedef struct dsv_keyset dsv_keyset;
+size_t dsv_keyset_bytes(int scheme, size_t k);
+int dsv_keyset_create(int scheme, const uint8_t *pk_uv, const uint8_t *pk2_uv, size_t k, dsv_keyset **out);
+int dsv_keyset_create_wire(int scheme, const uint8_t *pk_bytes, size_t k, dsv_keyset **out);
+int dsv_keyset_destroy(dsv_keyset *ks);
+int dsv_keyset_info(const dsv_keyset *ks, int *scheme, size_t *k, size_t *bytes, int *device);
+int dsv_keyset_key_ok(const dsv_keyset *ks, uint8_t *out /* k bytes */);
+size_t dsv_keyed_workspace_bytes(size_t n);
+int dsv_verify_single_keyed_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
+                                const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int dsv_verify_double_keyed_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *Rp_uv,
+                                const void *key_idx, const void *m, size_t n, void *ok, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int dsv_verify_vargen_keyed_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
+                                const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int dsv_verify_single_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv,
+                            const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
+int dsv_verify_double_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *Rp_uv,
+                            const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
+int dsv_verify_vargen_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv,
+                            const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
+/* introspection: affine u || v (canonical LE) of digit * 2^(8*window) * point, point 0 = PK, 1 = PK' / Gen,
+ * window 0 .. 31, digit -128 .. 128 */
+int dsv_debug_keyset_entry(const dsv_keyset *ks, size_t key, int point, int window, int digit,
+                           uint8_t out64[64]);
+
 /* ---- introspection for tests: copy one fixed-base table entry (affine niels v+u, v-u, 2duv
  * as canonical LE, 96 B) for generator `which` (0 = G, 1 = G'), window w (signed windows of
  * dsv_fixed_window_bits() bits), digit magnitude d ---- */

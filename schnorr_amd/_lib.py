@@ -52,10 +52,16 @@ SYMBOLS = [
     "dsv_verify_vargen_wire_rlc_dev",
     "dsv_verify_single_wire_rlc", "dsv_verify_double_wire_rlc", "dsv_verify_vargen_wire_rlc",
     "dsv_mixed_rlc_workspace_bytes", "dsv_verify_mixed_rlc_dev",
+    # registered key sets: verify by key index with per-key fixed-base tables
+    "dsv_keyset_bytes", "dsv_keyset_create", "dsv_keyset_create_wire", "dsv_keyset_destroy", "dsv_keyset_info",
+    "dsv_keyset_key_ok", "dsv_keyed_workspace_bytes", "dsv_verify_single_keyed_dev", "dsv_verify_double_keyed_dev",
+    "dsv_verify_vargen_keyed_dev", "dsv_verify_single_keyed", "dsv_verify_double_keyed", "dsv_verify_vargen_keyed",
+    "dsv_debug_keyset_entry",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
-                 "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes")
+                 "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes",
+                 "dsv_keyset_bytes", "dsv_keyed_workspace_bytes")
 
 
 class Column(ctypes.Structure):
@@ -98,6 +104,7 @@ def load():
     for name in _SIZE_T_FUNCS:
         getattr(L, name).restype = ctypes.c_size_t
         getattr(L, name).argtypes = [ctypes.c_size_t] + ([ctypes.c_int] if name in ("dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes") else [])
+    L.dsv_keyset_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("dsv_version", "dsv_last_error") + _SIZE_T_FUNCS:

@@ -483,6 +483,7 @@ int dsv_shutdown_device(int device) {
   int prev = -1;
   (void)hipGetDevice(&prev);
   ctx.ready.store(false);  // new calls are refused from here on
+  keysets_release_device(device);  // (before ctx.mu: a keyed host call holds the registry, then ctx.mu)
   {
     // host calls in flight finish first: the pipelined ones hold a pipe, the small ones `mu`
     std::unique_lock<std::mutex> pl(ctx.pipe_sync.mu);

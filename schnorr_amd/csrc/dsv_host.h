@@ -9,6 +9,7 @@
 //   dsv_wire.hip      serialized records (decode + verify), compress / decompress
 //   dsv_rlc.hip       the batch fast accept: control of k_rlc.hip, every *_rlc entry point
 //   dsv_inputs.hip    signing / key derivation / StdRng inputs (input generation), debug probes
+//   dsv_keyset.hip    registered key sets: per-key tables, verify by key index (keyed.h)
 // The host pipeline itself (run_pipelined, run_multi) is a template: dsv_pipeline.h.
 // Nothing here is part of the C ABI (include/dsv.h); everything lives in namespace dsvh.
 #pragma once
@@ -207,6 +208,8 @@ int host_context(Context*& out);
 // context of a device-pointer entry point: the device that owns `ptr` (one of the call's buffers)
 int device_context(const void* ptr, Context*& out);
 void release_context(Context& ctx);
+// dsv_keyset.hip: free the device memory of the live key sets of `device` and mark them dead (dsv_shutdown_device)
+void keysets_release_device(int device);
 
 // workspace layout for the *_dev verify entry points: c[n][32] | valid[n]
 // + the per-lane window tables of the verify kernels (fixed grid, see kMaxVerifyGrid)

@@ -1,0 +1,351 @@
+// dsv_keyset.hip — registered key sets (include/dsv.h: dsv_keyset_*, dsv_verify_*_keyed*): creation from
+// affine points or wire records, the registry that dsv_shutdown_device empties, and the keyed verify entry
+// points (k_challenge unchanged, then k_verify_keyed; keyed.h).
+#include <algorithm>
+#include <shared_mutex>
+
+#include "dsv_host.h"
+#include "keyed.h"
+
+struct dsv_keyset {
+  int scheme = 0;
+  size_t k = 0;
+  int device = -1;
+  size_t bytes = 0;
+  uint32_t* tables = nullptr;  // one allocation: the tables, then key_ok
+  uint8_t* key_ok = nullptr;
+  bool alive = false;
+};
+
+namespace dsvh {
+namespace {
+// live key sets; verify calls read under the shared lock, create / destroy / shutdown write under the
+// exclusive one
+std::shared_mutex g_ks_mu;
+std::vector<dsv_keyset*> g_keysets;
+
+constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
+constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
+
+bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
+size_t keyed_ws_bytes(size_t n) { return align_up(n * 32, 256) + align_up(n, 256); }
+
+void free_sets_of(int device) {  // (exclusive lock held)
+  for (dsv_keyset* ks : g_keysets) {
+    if (ks->device != device || !ks->alive) continue;
+    if (ks->tables) (void)hipFree(ks->tables);
+    ks->tables = nullptr;
+    ks->key_ok = nullptr;
+    ks->alive = false;
+  }
+}
+
+// the context a key set's device work runs in: its device must still be initialised
+int keyset_context(const dsv_keyset* ks, Context*& out) {
+  if (!ks->alive || ks->device < 0 || ks->device >= kMaxDevices ||
+      !g_ctx[ks->device].ready.load(std::memory_order_acquire))
+    return fail(DSV_ERR_NOT_INITIALIZED, "the key set's device was shut down");
+  out = &g_ctx[ks->device];
+  return DSV_OK;
+}
+
+// tables of k keys from device points P0 / P1 (and the decoder's verdicts valid_in); registers the set
+int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
+                       size_t k, hipStream_t s, dsv_keyset** out) {
+  dsv_keyset* ks = new dsv_keyset();
+  ks->scheme = scheme;
+  ks->k = k;
+  ks->device = ctx.device;
+  ks->bytes = keyset_total_bytes(scheme, k);
+  const int rc = [&]() -> int {
+    if (k == 0) return DSV_OK;
+    HIP_TRY(hipMalloc(&ks->tables, ks->bytes));
+    ks->key_ok = reinterpret_cast<uint8_t*>(ks->tables) + keyset_table_bytes(scheme, k);
+    launch_build_key_tables(P0, P1, valid_in, keyset_points(scheme), k, ks->tables, ks->key_ok, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return DSV_OK;
+  }();
+  std::unique_lock<std::shared_mutex> lk(g_ks_mu);
+  if (rc == DSV_OK && !ctx.ready.load(std::memory_order_acquire)) {
+    if (ks->tables) (void)hipFree(ks->tables);
+    delete ks;
+    return fail(DSV_ERR_NOT_INITIALIZED, "device %d was shut down", ctx.device);
+  }
+  if (rc != DSV_OK) {
+    if (ks->tables) (void)hipFree(ks->tables);
+    delete ks;
+    return rc;
+  }
+  ks->alive = true;
+  g_keysets.push_back(ks);
+  *out = ks;
+  return DSV_OK;
+}
+
+// the calling thread's current device, which must be initialised
+int current_context(Context*& out) {
+  if (g_primary.load(std::memory_order_acquire) < 0) return fail(DSV_ERR_NOT_INITIALIZED, "dsv_init() has not been called");
+  int d = -1;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices || !g_ctx[d].ready.load(std::memory_order_acquire))
+    return fail(DSV_ERR_NOT_INITIALIZED, "the current device %d is not initialised", d);
+  out = &g_ctx[d];
+  return DSV_OK;
+}
+
+// device buffers + stream of one create call, released on every path
+struct Scratch {
+  uint8_t* dev = nullptr;
+  hipStream_t s = nullptr;
+  ~Scratch() {
+    if (s) (void)hipStreamSynchronize(s);
+    if (dev) (void)hipFree(dev);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+int create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, bool is_wire, const uint8_t* wire, size_t k,
+           dsv_keyset** out) {
+  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null output handle");
+  *out = nullptr;
+  if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
+  if (k > kMaxKeys) return fail(DSV_ERR_TOO_LARGE, "%zu keys: indices are 32-bit", k);
+  const int np = keyset_points(scheme);
+  if (k && (is_wire ? !wire : (!pk_uv || (np == 2 && !pk2_uv)))) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  Context* cp = nullptr;
+  if (int r = current_context(cp)) return r;
+  Context& ctx = *cp;
+  DSV_ON_DEVICE(ctx);
+  Scratch x;
+  const uint8_t* P[2] = {nullptr, nullptr};
+  uint8_t* valid = nullptr;
+  if (k) {
+    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
+    // device scratch: the affine points (np x k x 64 B), then for wire records the records and the
+    // decoder's verdicts
+    const size_t rec = 32 * (size_t)np;
+    const size_t off_in = align_up((size_t)np * k * 64, 256), off_valid = off_in + align_up(k * rec, 256);
+    HIP_TRY(hipMalloc(&x.dev, is_wire ? off_valid + align_up(k, 256) : off_in));
+    for (int p = 0; p < np; p++) P[p] = x.dev + (size_t)p * k * 64;
+    if (is_wire) {
+      valid = x.dev + off_valid;
+      HIP_TRY(hipMemcpyAsync(x.dev + off_in, wire, k * rec, hipMemcpyHostToDevice, x.s));
+      for (int p = 0; p < np; p++)
+        if (int r = decompress_on(ctx, x.dev + off_in + 32 * p, rec, k, (void*)P[p], valid, p > 0, x.s)) return r;
+    } else {
+      HIP_TRY(hipMemcpyAsync((void*)P[0], pk_uv, k * 64, hipMemcpyHostToDevice, x.s));
+      if (np == 2) HIP_TRY(hipMemcpyAsync((void*)P[1], pk2_uv, k * 64, hipMemcpyHostToDevice, x.s));
+    }
+  }
+  return create_from_device(ctx, scheme, P[0], P[1], valid, k, x.s, out);
+}
+
+// one keyed call's per-item inputs: u, the signature's points R (and R' for the double scheme), m
+struct KeyedIn {
+  int scheme;
+  const uint8_t *u, *R, *Rp, *m;
+  bool any_null() const { return !u || !R || (scheme == 1 && !Rp) || !m; }
+  Items items() const {  // (what launch_hash reads: R, R', m)
+    Items in{scheme, u};
+    in.pt[layout(scheme).R] = R;
+    if (scheme == 1) in.pt[layout(scheme).Rp] = Rp;
+    in.m = m;
+    return in;
+  }
+};
+KeyedIn keyed_in(int scheme, const void* u, const void* R, const void* Rp, const void* m) {
+  return KeyedIn{scheme, (const uint8_t*)u, (const uint8_t*)R, (const uint8_t*)Rp, (const uint8_t*)m};
+}
+
+// checks shared by the _dev and host forms (shared lock held)
+int check_set(const dsv_keyset* ks, int scheme, Context*& ctx) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  if (int r = keyset_context(ks, ctx)) return r;
+  if (ks->scheme != scheme)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
+  return DSV_OK;
+}
+
+// challenge hash, then the keyed kernel; every pointer device memory of ctx's device
+void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n,
+                   uint8_t* ok, void* workspace, hipStream_t s) {
+  const Workspace w = carve(workspace, n);
+  launch_hash(in.items(), n, w.c, w.valid, s);
+  launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R, in.Rp, idx, n, ks->tables, ks->key_ok, ks->k,
+                      ctx.table[0], ctx.table[1], ok, s);
+}
+
+int verify_keyed_dev(const dsv_keyset* ks, const KeyedIn& in, const void* idx, size_t n, void* ok, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  if (int r = check_n(n)) return r;
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  Context* kctx = nullptr;
+  if (int r = check_set(ks, in.scheme, kctx)) return r;
+  if (n == 0) return DSV_OK;
+  if (in.any_null() || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (workspace_bytes < keyed_ws_bytes(n))
+    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, keyed_ws_bytes(n));
+  Context* octx = nullptr;
+  if (int r = device_context(ok, octx)) return r;
+  if (octx != kctx)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
+  Context& ctx = *kctx;
+  DSV_ON_DEVICE(ctx);
+  enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, workspace, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return DSV_OK;
+}
+
+// host arrays: chunks through the context's staging, on its null stream
+int verify_keyed_host(const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n, uint8_t* ok) {
+  if (int r = check_n(n)) return r;
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  Context* cp = nullptr;
+  if (int r = check_set(ks, in.scheme, cp)) return r;
+  if (n == 0) return DSV_OK;
+  if (in.any_null() || !idx || !ok) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  Context& ctx = *cp;
+  DSV_HOST_LOCK();
+  const int np = in.scheme == 1 ? 2 : 1;  // the signature's points
+  const size_t chunk = n < kKeyedHostChunk ? n : kKeyedHostChunk;
+  const size_t per_item = 32 + 32 + 4 + 1 + 64 * (size_t)np;
+  if (int r = ensure_stage(ctx, chunk * per_item + keyed_ws_bytes(chunk) + 8 * 256)) return r;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t cnt = n - off < chunk ? n - off : chunk;
+    Stager st(ctx.stage);
+    uint8_t* du = st.take(cnt * 32);
+    uint8_t* dm = st.take(cnt * 32);
+    uint8_t* di = st.take(cnt * 4);
+    uint8_t* dok = st.take(cnt);
+    uint8_t* dR = st.take(cnt * 64);
+    uint8_t* dRp = np == 2 ? st.take(cnt * 64) : nullptr;
+    void* ws = st.take(keyed_ws_bytes(cnt));
+    H2D(du, in.u + off * 32, cnt * 32);
+    H2D(dm, in.m + off * 32, cnt * 32);
+    H2D(di, idx + off, cnt * 4);
+    H2D(dR, in.R + off * 64, cnt * 64);
+    if (dRp) H2D(dRp, in.Rp + off * 64, cnt * 64);
+    const KeyedIn d{in.scheme, du, dR, dRp, dm};
+    enqueue_keyed(ctx, ks, d, (const uint32_t*)di, cnt, dok, ws, 0);
+    HIP_TRY(hipGetLastError());
+    D2H(ok + off, dok, cnt);
+    HIP_TRY(hipStreamSynchronize(0));
+  }
+  return DSV_OK;
+}
+}  // namespace
+
+// dsv_shutdown_device: the live key sets of `device` lose their device memory (the context is released
+// right after, under the same locks)
+void keysets_release_device(int device) {
+  std::unique_lock<std::shared_mutex> lk(g_ks_mu);
+  DeviceGuard guard(device);
+  free_sets_of(device);
+}
+}  // namespace dsvh
+
+using namespace dsvh;
+
+extern "C" {
+
+size_t dsv_keyset_bytes(int scheme, size_t k) { return scheme_ok(scheme) ? keyset_total_bytes(scheme, k) : 0; }
+size_t dsv_keyed_workspace_bytes(size_t n) { return keyed_ws_bytes(n); }
+
+int dsv_keyset_create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t k, dsv_keyset** out) {
+  return create(scheme, pk_uv, pk2_uv, false, nullptr, k, out);
+}
+int dsv_keyset_create_wire(int scheme, const uint8_t* pk_bytes, size_t k, dsv_keyset** out) {
+  return create(scheme, nullptr, nullptr, true, pk_bytes, k, out);
+}
+
+int dsv_keyset_destroy(dsv_keyset* ks) {
+  if (!ks) return DSV_OK;
+  std::unique_lock<std::shared_mutex> lk(g_ks_mu);
+  auto it = std::find(g_keysets.begin(), g_keysets.end(), ks);
+  if (it == g_keysets.end()) return fail(DSV_ERR_INVALID_ARGUMENT, "not a live key set handle");
+  g_keysets.erase(it);
+  int rc = DSV_OK;
+  if (ks->alive && ks->tables) {
+    DeviceGuard guard(ks->device);
+    if (guard.err != hipSuccess) rc = fail(DSV_ERR_HIP, "cannot select device %d", ks->device);
+    (void)hipDeviceSynchronize();  // work in flight may still read the tables
+    (void)hipFree(ks->tables);
+  }
+  delete ks;
+  return rc;
+}
+
+int dsv_keyset_info(const dsv_keyset* ks, int* scheme, size_t* k, size_t* bytes, int* device) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  if (scheme) *scheme = ks->scheme;
+  if (k) *k = ks->k;
+  if (bytes) *bytes = ks->bytes;
+  if (device) *device = ks->device;
+  return DSV_OK;
+}
+
+int dsv_keyset_key_ok(const dsv_keyset* ks, uint8_t* out) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  Context* cp = nullptr;
+  if (int r = keyset_context(ks, cp)) return r;
+  if (ks->k == 0) return DSV_OK;
+  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  DSV_ON_DEVICE(*cp);
+  HIP_TRY(hipMemcpy(out, ks->key_ok, ks->k, hipMemcpyDeviceToHost));
+  return DSV_OK;
+}
+
+int dsv_verify_single_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
+                                const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return verify_keyed_dev(ks, keyed_in(0, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes, stream);
+}
+int dsv_verify_double_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
+                                const void* key_idx, const void* m, size_t n, void* ok, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return verify_keyed_dev(ks, keyed_in(1, u, R_uv, Rp_uv, m), key_idx, n, ok, workspace,
+                          workspace_bytes, stream);
+}
+int dsv_verify_vargen_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
+                                const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return verify_keyed_dev(ks, keyed_in(2, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes,
+                          stream);
+}
+
+int dsv_verify_single_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint32_t* key_idx,
+                            const uint8_t* m, size_t n, uint8_t* ok) {
+  return verify_keyed_host(ks, keyed_in(0, u, R_uv, nullptr, m), key_idx, n, ok);
+}
+int dsv_verify_double_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
+                            const uint32_t* key_idx, const uint8_t* m, size_t n, uint8_t* ok) {
+  return verify_keyed_host(ks, keyed_in(1, u, R_uv, Rp_uv, m), key_idx, n, ok);
+}
+int dsv_verify_vargen_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint32_t* key_idx,
+                            const uint8_t* m, size_t n, uint8_t* ok) {
+  return verify_keyed_host(ks, keyed_in(2, u, R_uv, nullptr, m), key_idx, n, ok);
+}
+
+int dsv_debug_keyset_entry(const dsv_keyset* ks, size_t key, int point, int window, int digit, uint8_t out64[64]) {
+  if (!ks || !out64) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  Context* cp = nullptr;
+  if (int r = keyset_context(ks, cp)) return r;
+  if (key >= ks->k || point < 0 || point >= keyset_points(ks->scheme) || window < 0 || window >= kKeyWindows ||
+      digit < -(kKeyEntries - 1) || digit > kKeyEntries - 1)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "entry out of range");
+  Context& ctx = *cp;
+  DSV_HOST_LOCK();
+  if (int r = ensure_stage(ctx, 256)) return r;
+  const int mag = digit < 0 ? -digit : digit;
+  const uint32_t* entry = ks->tables + (key * keyset_points(ks->scheme) + (size_t)point) * kKeyPointWords +
+                          ((size_t)window * kKeyEntries + (size_t)mag) * kEntryWords;
+  launch_key_entry(entry, digit < 0, ctx.stage, 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out64, ctx.stage, 64, hipMemcpyDeviceToHost));
+  return DSV_OK;
+}
+
+}  // extern "C"

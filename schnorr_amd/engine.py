@@ -856,3 +856,132 @@ def stdrng_vargen_inputs_dev(seed, sk, g, m, r, first_item=0, stream=None):
     _lib.check(_lib.load().dsv_stdrng_vargen_inputs_dev(
         ctypes.c_uint64(seed), ctypes.c_size_t(first_item), ctypes.c_size_t(n), _tp(sk, 32),
         _tp(g, 32), _tp(m, 32), _tp(r, 32), _stream_ptr(stream, dev)))
+
+
+# ------------------------------------------------------------------ registered key sets
+_KEYED_SCHEMES = {"single": 0, "double": 1, "vargen": 2}
+
+
+def keyset_bytes(scheme, k):
+    """dsv_keyset_bytes: device bytes of a key set of k keys (no GPU needed)"""
+    return int(_lib.load().dsv_keyset_bytes(ctypes.c_int(_KEYED_SCHEMES[scheme]), ctypes.c_size_t(k)))
+
+
+def keyed_workspace_bytes(n):
+    return int(_lib.load().dsv_keyed_workspace_bytes(ctypes.c_size_t(n)))
+
+
+class KeySet:
+    """Registered keys (dsv_keyset_*): per-key fixed-base tables on the device that is current when the set
+    is built; verify by key index.  scheme: "single" (PK), "double" (PK, PK') or "vargen" (PK, Gen).
+
+        ks = KeySet("single", PK)                  # PK: uint8 [k, 64] affine points
+        ks = KeySet("double", PK, PKp)
+        ks = KeySet.from_wire("vargen", pk64)      # the reference's key records, [k, 32] or [k, 64]
+        ok = ks.verify(u, R, idx, m)               # double: ks.verify(u, R, Rp, idx, m); idx: uint32 [n]
+        ks.verify_dev(u, R, idx, m, ok, workspace) # CUDA tensors; idx int32 [n], read as uint32
+    """
+
+    def __init__(self, scheme, PK, PK2=None, _wire=None):
+        if scheme not in _KEYED_SCHEMES:
+            raise ValueError("scheme must be one of %s" % sorted(_KEYED_SCHEMES))
+        self.scheme = scheme
+        self._h = ctypes.c_void_p()
+        L = _lib.load()
+        code = ctypes.c_int(_KEYED_SCHEMES[scheme])
+        if _wire is not None:
+            rec = _arr(_wire, 32 if scheme == "single" else 64)
+            _lib.check(L.dsv_keyset_create_wire(code, _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(self._h)))
+        else:
+            pk = _arr(PK, 64)
+            if (PK2 is None) != (scheme == "single"):
+                raise ValueError("scheme %s takes %s" % (scheme, "PK only" if scheme == "single" else "PK and PK2"))
+            arrs = [pk] + ([_arr(PK2, 64)] if PK2 is not None else [])
+            _same_n(*arrs)
+            _lib.check(L.dsv_keyset_create(code, _p(pk), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0),
+                                           ctypes.c_size_t(pk.shape[0]), ctypes.byref(self._h)))
+        s, k, b, d = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+        _lib.check(L.dsv_keyset_info(self._h, ctypes.byref(s), ctypes.byref(k), ctypes.byref(b), ctypes.byref(d)))
+        self.k, self.nbytes, self.device = k.value, b.value, d.value
+
+    @classmethod
+    def from_wire(cls, scheme, pk_bytes):
+        """from the reference's key records: PublicKey (32 B) / PublicKeyDouble / PublicKeyVarGen (64 B)"""
+        return cls(scheme, None, _wire=pk_bytes)
+
+    def _handle(self):
+        if self._h.value is None:
+            raise ValueError("key set is closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value is not None:
+            h, self._h = self._h, ctypes.c_void_p()
+            _lib.check(_lib.load().dsv_keyset_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def key_ok(self):
+        out = np.zeros(self.k, dtype=np.uint8)
+        _lib.check(_lib.load().dsv_keyset_key_ok(self._handle(), _p(out)))
+        return out
+
+    def debug_entry(self, key, point, window, digit):
+        """affine u || v of digit * 2^(8 * window) * point (0: PK, 1: PK' / Gen) from the key's table"""
+        out = np.zeros(64, dtype=np.uint8)
+        _lib.check(_lib.load().dsv_debug_keyset_entry(self._handle(), ctypes.c_size_t(key), ctypes.c_int(point),
+                                                      ctypes.c_int(window), ctypes.c_int(digit), _p(out)))
+        return out
+
+    def _pts(self, args):
+        """(u, R[, Rp], idx, m) split by scheme"""
+        want = 5 if self.scheme == "double" else 4
+        if len(args) != want:
+            raise ValueError("%s key set: verify takes %s" % (
+                self.scheme, "(u, R, Rp, idx, m)" if want == 5 else "(u, R, idx, m)"))
+        return args[0], args[1:-2], args[-2], args[-1]
+
+    def verify(self, *args):
+        """host arrays -> verdicts [n]; idx: key indices (uint32 [n]; an index >= k gives 0)"""
+        u, pts, idx, m = self._pts(args)
+        u, m = _arr(u, 32), _arr(m, 32)
+        pts = [_arr(p, 64) for p in pts]
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        n = _same_n(u, m, *pts)
+        if idx.shape[0] != n:
+            raise ValueError("idx has %d entries, the batch %d items" % (idx.shape[0], n))
+        ok = np.zeros(n, dtype=np.uint8)
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed" % self.scheme)(
+            self._handle(), _p(u), *[_p(p) for p in pts], _p(idx), _p(m), ctypes.c_size_t(n), _p(ok)))
+        return ok
+
+    def verify_dev(self, *args, stream=None):
+        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace): verdicts into ok, enqueued on `stream` (default:
+        torch's current stream of the batch's device); does not synchronise.  idx: int32 [n], read as uint32;
+        workspace: >= keyed_workspace_bytes(n) bytes."""
+        if len(args) < 2:
+            raise ValueError("verify_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, idx, m = self._pts(args[:-2])
+        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
+        tensors = [u] + list(pts) + [m]
+        n, dev = _rows(*zip(tensors, [32] + [64] * len(pts) + [32], names))
+        ip = _idx(idx, n, dev, "idx")
+        if idx.dim() != 1 or idx.shape[0] != n:
+            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        ws_need = keyed_workspace_bytes(n)
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, ws_need, dev, "workspace")
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_dev" % self.scheme)(
+            self._handle(), _tp(u, 32), *[_tp(p, 64) for p in pts], ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))

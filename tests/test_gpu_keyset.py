@@ -1,0 +1,415 @@
+"""Registered key sets on the GPU (dsv_keyset_*, dsv_verify_*_keyed*): whole-vector parity with the oracle on
+the gathered keys for all three schemes, adversarial base sets registered by unique key, 2^20 items against
+the unkeyed kernels, table entries against true multiples, key validity, index checks, the _dev contract,
+lifetime, the host form and shutdown."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import edge_sets as ES
+import harness as H
+import oracle_lib as O
+import pymodel as M
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+POISON = 7
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCHEMES = ("single", "double", "vargen")
+NS = (1, 63, 64, 65, 4099, (1 << 16) + 3)
+Q, R_ORDER = M.Q, M.R_ORDER
+
+
+def _scalars(rng, n, top_mask):
+    s = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    s[:, 31] &= top_mask
+    return s
+
+
+def _keys(engine, scheme, k, seed):
+    """(PK, second point or None) of k random keys: PK' for double, Gen for var-generator; and the secrets"""
+    rng = np.random.default_rng(seed)
+    sk = _scalars(rng, k, 0x07)  # < 2^251 < r
+    if scheme == "single":
+        return sk, None, engine.public_keys(sk), None
+    if scheme == "double":
+        return sk, None, engine.public_keys(sk, 0), engine.public_keys(sk, 1)
+    gen = engine.public_keys(_scalars(rng, k, 0x07))
+    return sk, gen, engine.public_keys(sk, Gen=gen), gen
+
+
+def _oracle(scheme, u, R, Rp, P0, P1, m):
+    if scheme == "single":
+        return O.verify_single(u, R, P0, m, nthreads=16)
+    if scheme == "double":
+        return O.verify_double(u, R, Rp, P0, P1, m, nthreads=16)
+    return O.verify_vargen(u, R, P0, P1, m, nthreads=16)
+
+
+_BATCHES = {}
+
+
+def _batch(engine, scheme, k, n, seed=0):
+    """n items signed under k keys (uniform indices), every 16th tampered (harness.tamper) -> dict with the key
+    arrays P0 / P1, the items u, R, Rp, idx, m and the oracle's verdicts on the gathered keys"""
+    key = (scheme, k, n, seed)
+    if key in _BATCHES:
+        return _BATCHES[key]
+    sk, gen, P0, P1 = _keys(engine, scheme, k, 1000 * k + 7 + seed)
+    rng = np.random.default_rng(k * 31 + n + seed)
+    idx = rng.integers(0, k, size=n).astype(np.uint32)
+    m = _scalars(rng, n, 0x3F)   # < 2^254 < q
+    r = _scalars(rng, n, 0x07)
+    Rp = None
+    if scheme == "single":
+        u, R = engine.sign_single(sk[idx], m, r)
+    elif scheme == "double":
+        u, R, Rp = engine.sign_double(sk[idx], m, r)
+    else:
+        u, R = engine.sign_vargen(sk[idx], gen[idx], m, r)
+    b = {"u": u, "R": R, "PK": P0[idx].copy(), "m": m}
+    H.tamper(b, kind_single=scheme == "single", period=16)
+    # a tampered PK row that is another registered key becomes that key's index; any other stays the row's key
+    where = {P0[j].tobytes(): j for j in range(k)}
+    changed = np.flatnonzero((b["PK"] != P0[idx]).any(axis=1))
+    for i in changed:
+        idx[i] = where.get(b["PK"][i].tobytes(), idx[i])
+    g1 = P1[idx] if P1 is not None else None
+    want = _oracle(scheme, b["u"], b["R"], Rp, P0[idx], g1, b["m"])
+    out = {"P0": P0, "P1": P1, "u": b["u"], "R": b["R"], "Rp": Rp, "idx": idx, "m": b["m"], "want": want}
+    if len(_BATCHES) > 4:
+        _BATCHES.pop(next(iter(_BATCHES)))
+    _BATCHES[key] = out
+    return out
+
+
+def _items(b, lo=0, hi=None):
+    """(u, R[, Rp], idx, m) host arrays of items [lo, hi)"""
+    s = slice(lo, hi)
+    pts = [b["R"][s]] + ([b["Rp"][s]] if b["Rp"] is not None else [])
+    return [b["u"][s]] + pts + [b["idx"][s], b["m"][s]]
+
+
+def _dev(arrs):
+    out = []
+    for a in arrs:
+        t = torch.from_numpy(np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a))
+        out.append(t.to(DEV))
+    return out
+
+
+def _poison(n):
+    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
+
+
+def _run_dev(engine, ks, darrs, n, stream=None):
+    ok = _poison(n)
+    ws = torch.empty(max(engine.keyed_workspace_bytes(n), 1), dtype=torch.uint8, device=DEV)
+    ks.verify_dev(*[a[:n] for a in darrs], ok, ws, stream=stream)
+    torch.cuda.synchronize()
+    return ok.cpu().numpy()
+
+
+def _diff(got, want):
+    bad = np.flatnonzero(got != want)
+    return "%d verdicts differ, first at %s (got %s, want %s)" % (
+        len(bad), bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
+
+
+def _keyset(engine, scheme, b):
+    return engine.KeySet(scheme, b["P0"], b["P1"])
+
+
+# ---- oracle parity ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", (1, 37, 1000))
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_oracle_parity(engine, scheme, k):
+    b = _batch(engine, scheme, k, NS[-1])
+    assert 0 < b["want"].sum() < len(b["want"])
+    with _keyset(engine, scheme, b) as ks:
+        assert ks.k == k and ks.nbytes == engine.keyset_bytes(scheme, k)
+        assert (ks.key_ok() == 1).all()
+        darrs = _dev(_items(b))
+        for n in NS:
+            got = _run_dev(engine, ks, darrs, n)
+            assert (got == b["want"][:n]).all(), (scheme, k, n, _diff(got, b["want"][:n]))
+
+
+# ---- adversarial base sets, registered by unique key ------------------------------------------------------
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_adversarial_base_set(engine, scheme):
+    arrs, want = ES.base(scheme, "affine", "mixed")
+    names = ES.FIELDS[scheme]
+    d = dict(zip(names, arrs))
+    second = {"single": None, "double": "PKp", "vargen": "Gen"}[scheme]
+    rows = d["PK"] if second is None else np.hstack([d["PK"], d[second]])
+    uniq, inv = np.unique(rows, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1).astype(np.uint32)
+    P0 = np.ascontiguousarray(uniq[:, :64])
+    P1 = np.ascontiguousarray(uniq[:, 64:]) if second else None
+    items = [d["u"], d["R"]] + ([d["Rp"]] if scheme == "double" else []) + [inv, d["m"]]
+    with engine.KeySet(scheme, P0, P1) as ks:
+        got = _run_dev(engine, ks, _dev(items), len(want))
+        assert (got == want).all(), _diff(got, want)
+        assert (ks.verify(*items) == want).all()
+
+
+# ---- 2^20 items against the unkeyed kernels ---------------------------------------------------------------
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_two_pow_20_matches_unkeyed(engine, scheme):
+    n, k = 1 << 20, 64
+    sk, gen, P0, P1 = _keys(engine, scheme, k, 4242)
+    rng = np.random.default_rng(99)
+    idx = rng.integers(0, k, size=n).astype(np.uint32)
+    m = _scalars(rng, n, 0x3F)
+    r = _scalars(rng, n, 0x07)
+    Rp = None
+    if scheme == "single":
+        u, R = engine.sign_single(sk[idx], m, r)
+    elif scheme == "double":
+        u, R, Rp = engine.sign_double(sk[idx], m, r)
+    else:
+        u, R = engine.sign_vargen(sk[idx], gen[idx], m, r)
+    # every 16th item: another key's index (a signature checked against the wrong key), every 16th + 5: u + 1
+    idx[::16] = (idx[::16] + 1) % k
+    u[5::16, 0] ^= 1
+    items = [u, R] + ([Rp] if Rp is not None else []) + [idx, m]
+    d = _dev(items)
+    with engine.KeySet(scheme, P0, P1) as ks:
+        got = _run_dev(engine, ks, d, n)
+    g0, g1 = torch.from_numpy(P0[idx]).to(DEV), (torch.from_numpy(P1[idx]).to(DEV) if P1 is not None else None)
+    ok = _poison(n)
+    ws = torch.empty(engine.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+    du, dR, dm = d[0], d[1], d[-1]
+    if scheme == "single":
+        engine.verify_single_dev(du, dR, g0, dm, ok, ws)
+    elif scheme == "double":
+        engine.verify_double_dev(du, dR, d[2], g0, g1, dm, ok, ws)
+    else:
+        engine.verify_vargen_dev(du, dR, g0, g1, dm, ok, ws)
+    torch.cuda.synchronize()
+    ref = ok.cpu().numpy()
+    assert (got == ref).all(), _diff(got, ref)
+    assert 0.8 < got.mean() < 0.9
+    sample = np.sort(rng.choice(n, 4096, replace=False))
+    want = _oracle(scheme, u[sample], R[sample], Rp[sample] if Rp is not None else None, P0[idx[sample]],
+                   P1[idx[sample]] if P1 is not None else None, m[sample])
+    assert (got[sample] == want).all(), _diff(got[sample], want)
+
+
+# ---- table entries ----------------------------------------------------------------------------------------
+def _small_order_point():
+    import test_halfgcd as TH
+    return TH.order8_point()
+
+
+@pytest.mark.parametrize("point", (0, 1))
+def test_table_entries_are_true_multiples(engine, point):
+    """entry [w][d] of a normal and a small-order (order 8) point equals d * 2^(8w) * P; -d its negation"""
+    normal = H.to_int_point(engine.public_keys(_scalars(np.random.default_rng(5), 1, 0x07))[0])
+    small = _small_order_point()
+    pts = [normal, small]
+    P0 = np.stack([np.frombuffer(M.point_bytes(p), np.uint8) for p in pts])
+    # point 1 (double: PK'): the same two points in the other slot, a different first point
+    P1 = P0.copy()
+    if point == 1:
+        P0 = np.stack([np.frombuffer(M.point_bytes(M.pmul(M.GEN, 12345 + j)), np.uint8) for j in range(2)])
+    scheme = "single" if point == 0 else "double"
+    with engine.KeySet(scheme, P0, P1 if point == 1 else None) as ks:
+        assert (ks.key_ok() == 1).all()
+        for key, P in enumerate(pts):
+            Pb = np.frombuffer(M.point_bytes(P), np.uint8).reshape(1, 64)
+            for w in (0, 1, 15, 30, 31):
+                for d in (0, 1, 2, 15, 32, 127, 128):
+                    s = d << (8 * w)
+                    if s < 1 << 252:
+                        want = O.scalar_mul(np.frombuffer(M.le32(s), np.uint8).reshape(1, 32), Pb)[0]
+                    else:
+                        want = np.frombuffer(M.point_bytes(M.pmul(P, s)), np.uint8)
+                    got = ks.debug_entry(key, point, w, d)
+                    assert (got == want).all(), (key, w, d)
+                    neg = np.frombuffer(M.point_bytes(M.pneg(H.to_int_point(want))), np.uint8)
+                    assert (ks.debug_entry(key, point, w, -d) == neg).all(), (key, w, -d)
+
+
+# ---- key validity -----------------------------------------------------------------------------------------
+def test_invalid_keys_and_wire_form(engine):
+    b = _batch(engine, "single", 37, 4099)
+    P0 = b["P0"].copy()
+    pk1 = H.to_int_point(P0[1])
+    if pk1[0] + Q < 1 << 256:
+        P0[1, :32] = np.frombuffer(M.le32(pk1[0] + Q), np.uint8)  # u >= q, same residue
+    else:
+        P0[1, :32] = 0xFF
+    P0[2, 40] ^= 1                                                # v changed: off the curve
+    assert not M.on_curve(H.to_int_point(P0[2]))
+    items = _items(b)
+    idx = b["idx"]
+    with engine.KeySet("single", P0) as ks:
+        kok = ks.key_ok()
+        assert kok[1] == 0 and kok[2] == 0 and kok.sum() == 35
+        got = ks.verify(*items)
+    bad = np.isin(idx, (1, 2))
+    assert bad.sum() > 0 and (got[bad] == 0).all()
+    assert (got[~bad] == b["want"][~bad]).all(), _diff(got[~bad], b["want"][~bad])
+    # wire records: the same verdicts as the affine set; an undecodable record is an invalid key
+    for scheme in SCHEMES:
+        bs = _batch(engine, scheme, 37, 4099)
+        rec = O.compress(bs["P0"]) if scheme == "single" else np.hstack([O.compress(bs["P0"]), O.compress(bs["P1"])])
+        rec = np.ascontiguousarray(rec)
+        its = _items(bs)
+        with engine.KeySet(scheme, bs["P0"], bs["P1"]) as ka, engine.KeySet.from_wire(scheme, rec) as kw:
+            assert (kw.key_ok() == 1).all()
+            va = ka.verify(*its)
+            assert (va == bs["want"]).all(), _diff(va, bs["want"])
+            assert (kw.verify(*its) == va).all()
+        rec[3, :32] = np.frombuffer(M.le32(Q), np.uint8)  # v = q: from_bytes rejects it
+        with engine.KeySet.from_wire(scheme, rec) as kw:
+            kok = kw.key_ok()
+            assert kok[3] == 0 and kok.sum() == 36
+            got = kw.verify(*its)
+            under = bs["idx"] == 3
+            assert under.sum() > 0 and (got[under] == 0).all() and (got[~under] == va[~under]).all()
+
+
+# ---- indices ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_index_checks(engine, scheme):
+    b = _batch(engine, scheme, 37, 4099)
+    items = _items(b)
+    idx = b["idx"].copy()
+    honest = np.flatnonzero(b["want"] == 1)
+    bad = honest[:4]
+    idx[bad[0]], idx[bad[1]], idx[bad[2]] = 37, 1 << 31, (1 << 32) - 1
+    idx[bad[3]] = (idx[bad[3]] + 1) % 37  # another key's index
+    items[-2] = idx
+    want = b["want"].copy()
+    want[bad] = 0
+    with _keyset(engine, scheme, b) as ks:
+        got = _run_dev(engine, ks, _dev(items), len(want))
+        assert (got == want).all(), _diff(got, want)
+        assert (ks.verify(*items) == want).all()
+
+
+# ---- the _dev contract ------------------------------------------------------------------------------------
+def test_dev_semantics(engine):
+    from schnorr_amd import _lib
+
+    L = _lib.load()
+    b = _batch(engine, "single", 37, 4099)
+    n = 4099
+    du, dR, di, dm = _dev(_items(b))
+    with _keyset(engine, "single", b) as ks:
+        # enqueued on a side stream behind a poison fill on that stream
+        side = torch.cuda.Stream(device=DEV)
+        ws = torch.empty(engine.keyed_workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        with torch.cuda.stream(side):
+            ok = torch.empty(n, dtype=torch.uint8, device=DEV).fill_(POISON)
+            ks.verify_dev(du, dR, di, dm, ok, ws, stream=side)
+        side.synchronize()
+        assert (ok.cpu().numpy() == b["want"]).all()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        args = lambda nn, okt, wst, wsb: (ks._h, ctypes.c_void_p(du.data_ptr()), ctypes.c_void_p(dR.data_ptr()),
+                                         ctypes.c_void_p(di.data_ptr()), ctypes.c_void_p(dm.data_ptr()),
+                                         ctypes.c_size_t(nn), ctypes.c_void_p(okt.data_ptr()),
+                                         ctypes.c_void_p(wst.data_ptr()), ctypes.c_size_t(wsb), stream)
+        # a workspace one byte short: DSV_ERR_INVALID_ARGUMENT, nothing launched
+        ok = _poison(n)
+        assert L.dsv_verify_single_keyed_dev(*args(n, ok, ws, ws.numel() - 1)) == -2
+        torch.cuda.synchronize()
+        assert (ok.cpu().numpy() == POISON).all()
+        # n = 0
+        assert L.dsv_verify_single_keyed_dev(*args(0, ok, ws, 0)) == 0
+        # a key set of the wrong scheme
+        assert L.dsv_verify_vargen_keyed_dev(*args(n, ok, ws, ws.numel())) == -2
+        dRp = dR.clone()
+        assert L.dsv_verify_double_keyed_dev(ks._h, ctypes.c_void_p(du.data_ptr()), ctypes.c_void_p(dR.data_ptr()),
+                                             ctypes.c_void_p(dRp.data_ptr()), ctypes.c_void_p(di.data_ptr()),
+                                             ctypes.c_void_p(dm.data_ptr()), ctypes.c_size_t(n),
+                                             ctypes.c_void_p(ok.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                             ctypes.c_size_t(ws.numel()), stream) == -2
+        # null pointer with n > 0
+        assert L.dsv_verify_single_keyed_dev(ks._h, None, ctypes.c_void_p(dR.data_ptr()), ctypes.c_void_p(di.data_ptr()),
+                                             ctypes.c_void_p(dm.data_ptr()), ctypes.c_size_t(n),
+                                             ctypes.c_void_p(ok.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                             ctypes.c_size_t(ws.numel()), stream) == -2
+        torch.cuda.synchronize()
+        assert (ok.cpu().numpy() == POISON).all()
+        with pytest.raises(ValueError):
+            ks.verify_dev(du, dR, dR, di, dm, ok, ws)  # double arguments on a single key set
+        with pytest.raises(ValueError):
+            ks.verify_dev(du, dR, di, dm, ok, ws[:10])
+
+
+# ---- lifetime ---------------------------------------------------------------------------------------------
+def test_lifetime(engine):
+    b1 = _batch(engine, "single", 37, 4099)
+    b2 = _batch(engine, "vargen", 37, 4099)
+    ks1, ks2 = _keyset(engine, "single", b1), _keyset(engine, "vargen", b2)
+    assert (ks1.verify(*_items(b1)) == b1["want"]).all()
+    ks1.close()
+    ks1.close()  # idempotent
+    assert (ks2.verify(*_items(b2)) == b2["want"]).all()
+    with pytest.raises(ValueError):
+        ks1.verify(*_items(b1))
+    ks2.close()
+    torch.cuda.synchronize()
+    pk = b1["P0"]
+    big = np.tile(pk, (3, 1))[:100]
+    with engine.KeySet("single", big):
+        pass
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(10):
+        ks = engine.KeySet("single", big)
+        assert ks.nbytes > 50 << 20
+        ks.close()
+    free1 = torch.cuda.mem_get_info()[0]
+    assert free0 - free1 < 32 << 20, (free0, free1)
+
+
+# ---- host form --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_host_form_equals_dev_form(engine, scheme):
+    b = _batch(engine, scheme, 37, NS[-1])
+    n = (1 << 18) + 5
+    reps = -(-n // NS[-1])
+    items = [np.concatenate([a] * reps)[:n] for a in _items(b)]
+    with _keyset(engine, scheme, b) as ks:
+        host = ks.verify(*items)
+        dev = _run_dev(engine, ks, _dev(items), n)
+    want = np.tile(b["want"], reps)[:n]
+    assert (host == dev).all(), _diff(host, dev)
+    assert (host == want).all(), _diff(host, want)
+
+
+# ---- shutdown (a process of its own: the session's engine stays up) ----------------------------------------
+def test_shutdown_kills_live_sets():
+    code = r"""
+import ctypes, sys
+import numpy as np
+sys.path.insert(0, %r)
+sys.path.insert(0, %r)
+import torch
+from schnorr_amd import engine as E, _lib
+E.init(0)
+L = _lib.load()
+sk = np.zeros((2, 32), np.uint8); sk[:, 0] = (3, 5)
+pk = E.public_keys(sk)
+ks = E.KeySet("single", pk)
+assert list(ks.key_ok()) == [1, 1]
+E.shutdown()
+h = ks._h
+u = np.zeros((1, 32), np.uint8); R = np.zeros((1, 64), np.uint8); idx = np.zeros(1, np.uint32); ok = np.zeros(1, np.uint8)
+p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+assert L.dsv_verify_single_keyed(h, p(u), p(R), p(idx), p(u), ctypes.c_size_t(1), p(ok)) == -1
+assert L.dsv_keyset_key_ok(h, p(ok)) == -1
+ks.close()  # dsv_keyset_destroy on a dead set: DSV_OK
+print("ok")
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
