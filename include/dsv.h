@@ -566,6 +566,49 @@ int dsv_verify_double_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_
                             const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
 int dsv_verify_vargen_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv,
                             const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
+/* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
+ * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
+ * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with
+ * secret 128-bit weights z_i (z'_i) drawn per call (getrandom, ChaCha12), a sub-group is ACCEPTED iff
+ *   (1) every R_i (R'_i) that enters the sum lies in the prime-order subgroup (r * S_p == O for the per-bit
+ *       subset sums of the nonce points),
+ *   (2) every key point an item of the sub-group references is torsion-free: r * PK_k == O (and r * PK'_k /
+ *       r * Gen_k), from the key's own table, per call and only for referenced keys, and
+ *   (3) single:  (sum z_i u_i) G + sum_k s_k PK_k - sum z_i R_i == O,   s_k = sum over key k of z_i c_i mod r
+ *       double:  the same with (z'_i, G', s'_k, PK'_k, R'_i) added (two weights per item)
+ *       vargen:  sum_k a_k Gen_k + sum_k s_k PK_k - sum z_i R_i == O,   a_k = sum over key k of z_i u_i mod r.
+ * Accepted: every eligible item's verdict is `true` (error <= 2^-112 for a batch that holds a wrong
+ * signature).  Malformed items — u >= r, a coordinate >= q, m >= q, idx >= k, key_ok[idx] == 0 — stay out
+ * of the sum with verdict 0 (an index >= k never reads a table).  Anything else — a wrong signature, a torsion
+ * component, an eligible R off the curve, a bin overflow — sends the sub-group to the keyed per-signature
+ * kernel, which is enqueued behind the aggregate and returns at once where it accepted.
+ * window_bits: 0 = automatic (groups below 2^19 items go straight to the keyed per-signature kernel: the
+ * aggregate's tail does not pay below that), else one of 4, 6, 8, 12, 14, 16.
+ * accepted: as for dsv_verify_single_rlc_dev (device-writable memory: written by a kernel; ordinary host
+ * memory: the call waits for `stream` at its end).
+ * workspace: workspace_bytes >= dsv_keyed_rlc_workspace_bytes(n, k, window_bits) (k: keys of the set;
+ * 0 for bad bits; never less for a larger n or k).  Arguments as for the keyed _dev calls (short workspace,
+ * scheme mismatch, wrong device, NULL with n > 0: DSV_ERR_INVALID_ARGUMENT, nothing launched; dead set:
+ * DSV_ERR_NOT_INITIALIZED; n = 0: DSV_OK).
+ * History: keyed calls keep counters of their own (dsv_debug_keyed_rlc_history) and never change
+ * dsv_debug_rlc_history / _long; dsv_debug_rlc_subgroups applies to them too.
+ * No graph capture: the weight key is drawn on the host per call, so a call on a capturing stream returns
+ * DSV_ERR_INVALID_ARGUMENT with nothing enqueued (its first HIP call is hipStreamIsCapturing). */
+size_t dsv_keyed_rlc_workspace_bytes(size_t n, size_t k, int window_bits);
+/* the keyed plan of one group (no GPU needed): out[24] as dsv_rlc_plan_info's (no key windows: wpk = 0, no
+ * long points), out[23] = workspace bytes of this plan for k keys */
+int dsv_keyed_rlc_plan_info(int scheme, size_t n, size_t k, int window_bits, int groups, uint64_t *out /*[24]*/);
+/* the device's keyed history counter (> 0: the next keyed calls run in sub-groups); set >= 0 overrides it */
+int dsv_debug_keyed_rlc_history(int device, int set);
+int dsv_verify_single_keyed_rlc_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
+                                    const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
+                                    void *stream, int window_bits, int *accepted);
+int dsv_verify_double_keyed_rlc_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *Rp_uv,
+                                    const void *key_idx, const void *m, size_t n, void *ok, void *workspace,
+                                    size_t workspace_bytes, void *stream, int window_bits, int *accepted);
+int dsv_verify_vargen_keyed_rlc_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
+                                    const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
+                                    void *stream, int window_bits, int *accepted);
 /* introspection: affine u || v (canonical LE) of digit * 2^(8*window) * point, point 0 = PK, 1 = PK' / Gen,
  * window 0 .. 31, digit -128 .. 128 */
 int dsv_debug_keyset_entry(const dsv_keyset *ks, size_t key, int point, int window, int digit,

@@ -407,6 +407,16 @@ int rlc_verdict_target(Context& ctx, int* accepted, RlcVerdictTarget& t);
 int rlc_verdict_wait(const RlcVerdictTarget& t, hipStream_t s);
 int rlc_clear_accepted(int* accepted);
 int rlc_history(Context& ctx);  // the device's history counter (-1: no pinned memory to be had)
+// pieces of the fast accept's control that the keyed one (dsv_keyed_rlc.hip) shares
+void carve_rlc_buffers(Stager& st, const RlcPlan& p, RlcBuffers& b);
+size_t rlc_group_items(size_t n);
+int rlc_split_groups(size_t cnt, int window_bits);
+RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups, bool keyed = false);
+int check_rlc_bits(int window_bits);
+int rlc_random_key(ChaChaKey& key);
+int rlc_forced_groups();  // dsv_debug_rlc_subgroups / DSV_RLC_SUBGROUPS (0: by the history)
+// the keyed calls' own pinned counters ([0] history, [1] calls, [2] long history; k_rlc_verdict's layout), or null
+u32* rlc_keyed_history(Context& ctx);
 
 #define H2D(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, 0))
 #define D2H(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, 0))

@@ -4,18 +4,7 @@
 #include <algorithm>
 #include <shared_mutex>
 
-#include "dsv_host.h"
-#include "keyed.h"
-
-struct dsv_keyset {
-  int scheme = 0;
-  size_t k = 0;
-  int device = -1;
-  size_t bytes = 0;
-  uint32_t* tables = nullptr;  // one allocation: the tables, then key_ok
-  uint8_t* key_ok = nullptr;
-  bool alive = false;
-};
+#include "keyset_host.h"
 
 namespace dsvh {
 namespace {
@@ -28,7 +17,6 @@ constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
 constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
 
 bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
-size_t keyed_ws_bytes(size_t n) { return align_up(n * 32, 256) + align_up(n, 256); }
 
 void free_sets_of(int device) {  // (exclusive lock held)
   for (dsv_keyset* ks : g_keysets) {
@@ -140,40 +128,6 @@ int create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, bool is_wire
   return create_from_device(ctx, scheme, P[0], P[1], valid, k, x.s, out);
 }
 
-// one keyed call's per-item inputs: u, the signature's points R (and R' for the double scheme), m
-struct KeyedIn {
-  int scheme;
-  const uint8_t *u, *R, *Rp, *m;
-  bool any_null() const { return !u || !R || (scheme == 1 && !Rp) || !m; }
-  Items items() const {  // (what launch_hash reads: R, R', m)
-    Items in{scheme, u};
-    in.pt[layout(scheme).R] = R;
-    if (scheme == 1) in.pt[layout(scheme).Rp] = Rp;
-    in.m = m;
-    return in;
-  }
-};
-KeyedIn keyed_in(int scheme, const void* u, const void* R, const void* Rp, const void* m) {
-  return KeyedIn{scheme, (const uint8_t*)u, (const uint8_t*)R, (const uint8_t*)Rp, (const uint8_t*)m};
-}
-
-// checks shared by the _dev and host forms (shared lock held)
-int check_set(const dsv_keyset* ks, int scheme, Context*& ctx) {
-  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
-  if (int r = keyset_context(ks, ctx)) return r;
-  if (ks->scheme != scheme)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
-  return DSV_OK;
-}
-
-// challenge hash, then the keyed kernel; every pointer device memory of ctx's device
-void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n,
-                   uint8_t* ok, void* workspace, hipStream_t s) {
-  const Workspace w = carve(workspace, n);
-  launch_hash(in.items(), n, w.c, w.valid, s);
-  launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R, in.Rp, idx, n, ks->tables, ks->key_ok, ks->k,
-                      ctx.table[0], ctx.table[1], ok, s);
-}
 
 int verify_keyed_dev(const dsv_keyset* ks, const KeyedIn& in, const void* idx, size_t n, void* ok, void* workspace,
                      size_t workspace_bytes, void* stream) {
@@ -234,6 +188,25 @@ int verify_keyed_host(const dsv_keyset* ks, const KeyedIn& in, const uint32_t* i
   return DSV_OK;
 }
 }  // namespace
+
+// checks shared by the _dev and host forms (shared lock held)
+int check_set(const dsv_keyset* ks, int scheme, Context*& ctx) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  if (int r = keyset_context(ks, ctx)) return r;
+  if (ks->scheme != scheme)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
+  return DSV_OK;
+}
+std::shared_mutex& keyset_mutex() { return g_ks_mu; }
+// challenge hash, then the keyed kernel; every pointer device memory of ctx's device
+void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n,
+                   uint8_t* ok, void* workspace, hipStream_t s) {
+  const Workspace w = carve(workspace, n);
+  launch_hash(in.items(), n, w.c, w.valid, s);
+  launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R, in.Rp, idx, n, ks->tables, ks->key_ok, ks->k,
+                      ctx.table[0], ctx.table[1], ok, s);
+}
+
 
 // dsv_shutdown_device: the live key sets of `device` lose their device memory (the context is released
 // right after, under the same locks)

@@ -41,6 +41,83 @@ extern "C" {
 // batch in ~200 on, hence the counter's 128.  A caller whose batches never fail never enqueues it;
 // DSV_RLC_GUARD=0 switches it off.
 extern "C++" {
+namespace dsvh {
+// the bucket buffers of a plan, carved from `st` (the unkeyed workspace after its fixed places; the keyed one)
+void carve_rlc_buffers(Stager& st, const RlcPlan& p, RlcBuffers& b) {
+  auto words = [&](size_t count) { return reinterpret_cast<u32*>(st.take(count * 4)); };
+  const size_t G = p.groups, sub = p.sub;
+  b.pts_stride = (size_t)(p.lpts + p.spts) * sub * 32;
+  b.pts = words(G * b.pts_stride);
+  b.fsc_stride = (size_t)(p.fixed ? p.fixed : 1) * sub * 8;
+  b.fsc = words(G * b.fsc_stride);
+  b.fpart = words(G * 2 * kRlcFsumBlocks * 8);
+  b.fsum = words(G * 16);
+  b.digits_stride = align_up((size_t)p.rows * p.row_stride, 128);
+  b.digits = reinterpret_cast<uint16_t*>(st.take(G * b.digits_stride * 2));
+  b.counters_stride = (size_t)p.bins + 512;
+  b.counters = words(G * b.counters_stride);
+  b.bin_stride = (size_t)p.bins * p.bin_cap;
+  b.binned = words(G * b.bin_stride);
+  b.sorted = words(G * b.bin_stride);
+  b.bucket_stride = p.buckets;
+  b.start = words(G * p.buckets);
+  b.cnt = words(G * p.buckets);
+  b.order = words(G * p.buckets);
+  b.buckets = words(G * p.buckets * 36);
+  b.buckets2 = G == 1 ? words(p.buckets * 36) : nullptr;
+  for (int k = 0; k < 2; k++) {
+    b.tmp_stride[k] = rlc_tmp_points(p, k);
+    b.tmp[k] = words(G * b.tmp_stride[k] * 36);
+  }
+}
+// groups of equal size (a batch just above 2^22 items is two halves, not one full group and a tail too
+// small for an aggregate)
+size_t rlc_group_items(size_t n) {
+  if (n <= kRlcMaxGroup) return n;
+  const size_t groups = (n + kRlcMaxGroup - 1) / kRlcMaxGroup;
+  return (n + groups - 1) / groups;
+}
+// sub-groups a group of cnt items is cut into while the history says "batches fail": sub-groups of
+// 2^16 items (DSV_RLC_SUB_LOG2; measured, 2^20 items with one wrong signature: 6.5 ms in sixteen sub-groups, 7.1 in eight, 8.1 in four, 10.8 in two; 2^18 items: 2.96 ms in four, 3.48 in two), at least two from 2^18 items on, at most kRlcMaxSub
+int rlc_split_groups(size_t cnt, int window_bits) {
+  static const int sub_log2 = [] {
+    const char* e = getenv("DSV_RLC_SUB_LOG2");
+    const int v = e ? atoi(e) : 16;
+    return v < 10 ? 10 : (v > 22 ? 22 : v);
+  }();
+  size_t g = cnt >> sub_log2;
+  if (g < 2 && (window_bits ? cnt >= 2 : cnt >= 2 * kRlcMinAuto)) g = 2;
+  if (g > (size_t)kRlcMaxSub) g = kRlcMaxSub;
+  return g < 1 ? 1 : (int)g;
+}
+// the plan of one group: window bits from the SUB-group's size; sub-groups are whole sub-batches of the
+// per-signature path (kSplitItems), so that no launch of the fallback straddles two of them; keyed: the
+// plan of a registered key set's pass (rlc.h: rlc_plan)
+RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups, bool keyed) {
+  if (groups <= 1) return rlc_plan(scheme, cnt, window_bits ? window_bits : rlc_default_bits(cnt), 1, 1, keyed);
+  const size_t align = cnt >= 2 * kSplitItems ? kSplitItems : 64;
+  RlcPlan probe = rlc_plan(scheme, cnt, window_bits ? window_bits : 8, groups, align, keyed);
+  return rlc_plan(scheme, cnt, window_bits ? window_bits : rlc_default_bits(probe.sub), groups, align, keyed);
+}
+int check_rlc_bits(int window_bits) {
+  if (window_bits && !rlc_bits_ok(window_bits))
+    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16");
+  return DSV_OK;
+}
+int rlc_random_key(ChaChaKey& key) {
+  uint8_t* p = reinterpret_cast<uint8_t*>(key.w);
+  size_t have = 0;
+  while (have < sizeof key.w) {
+    const ssize_t got = getrandom(p + have, sizeof key.w - have, 0);
+    if (got < 0) {
+      if (errno == EINTR) continue;
+      return fail(DSV_ERR_HIP, "getrandom: %s (the batch weights must be unpredictable)", strerror(errno));
+    }
+    have += (size_t)got;
+  }
+  return DSV_OK;
+}
+}  // namespace dsvh
 namespace {
 // Before an aggregate is paid for, the per-signature kernel (eight lanes per signature: 0.26 ms)
 // verifies kRlcSample consecutive items — at a position drawn from the call's secret key — from the
@@ -67,102 +144,39 @@ RlcCarve carve_rlc(void* ws, size_t nmax, size_t cnt, const RlcPlan& p) {
   r.w = carve(ws, cnt);
   Stager st(static_cast<uint8_t*>(ws) + align_up(dsv_workspace_bytes(nmax), 256));
   auto words = [&](size_t count) { return reinterpret_cast<u32*>(st.take(count * 4)); };
-  const size_t G = p.groups, sub = p.sub;
   // fixed places first: the same whatever the plan
   r.flags_area = words(kRlcFlagBlocks * kRlcGroupFlagWords);
   r.b.flags = r.flags_area;
   r.sample_ok = st.take(kRlcSample);
   r.sample_ws = st.take(dsv_workspace_bytes(kRlcSample));
-  RlcBuffers& b = r.b;
-  b.pts_stride = (size_t)(p.lpts + p.spts) * sub * 32;
-  b.pts = words(G * b.pts_stride);
-  b.fsc_stride = (size_t)(p.fixed ? p.fixed : 1) * sub * 8;
-  b.fsc = words(G * b.fsc_stride);
-  b.fpart = words(G * 2 * kRlcFsumBlocks * 8);
-  b.fsum = words(G * 16);
-  b.digits_stride = align_up((size_t)p.rows * p.row_stride, 128);
-  b.digits = reinterpret_cast<uint16_t*>(st.take(G * b.digits_stride * 2));
-  b.counters_stride = (size_t)p.bins + 512;
-  b.counters = words(G * b.counters_stride);
-  b.bin_stride = (size_t)p.bins * p.bin_cap;
-  b.binned = words(G * b.bin_stride);
-  b.sorted = words(G * b.bin_stride);
-  b.bucket_stride = p.buckets;
-  b.start = words(G * p.buckets);
-  b.cnt = words(G * p.buckets);
-  b.order = words(G * p.buckets);
-  b.buckets = words(G * p.buckets * 36);
-  b.buckets2 = G == 1 ? words(p.buckets * 36) : nullptr;
-  for (int k = 0; k < 2; k++) {
-    b.tmp_stride[k] = rlc_tmp_points(p, k);
-    b.tmp[k] = words(G * b.tmp_stride[k] * 36);
-  }
+  carve_rlc_buffers(st, p, r.b);
   r.bytes = align_up(dsv_workspace_bytes(nmax), 256) + st.off;
   return r;
-}
-// groups of equal size (a batch just above 2^22 items is two halves, not one full group and a tail too
-// small for an aggregate)
-size_t rlc_group_items(size_t n) {
-  if (n <= kRlcMaxGroup) return n;
-  const size_t groups = (n + kRlcMaxGroup - 1) / kRlcMaxGroup;
-  return (n + groups - 1) / groups;
-}
-// sub-groups a group of cnt items is cut into while the history says "batches fail": sub-groups of
-// 2^16 items (DSV_RLC_SUB_LOG2; measured, 2^20 items with one wrong signature: 6.5 ms in sixteen sub-groups, 7.1 in eight, 8.1 in four, 10.8 in two; 2^18 items: 2.96 ms in four, 3.48 in two), at least two from 2^18 items on, at most kRlcMaxSub
-int rlc_split_groups(size_t cnt, int window_bits) {
-  static const int sub_log2 = [] {
-    const char* e = getenv("DSV_RLC_SUB_LOG2");
-    const int v = e ? atoi(e) : 16;
-    return v < 10 ? 10 : (v > 22 ? 22 : v);
-  }();
-  size_t g = cnt >> sub_log2;
-  if (g < 2 && (window_bits ? cnt >= 2 : cnt >= 2 * kRlcMinAuto)) g = 2;
-  if (g > (size_t)kRlcMaxSub) g = kRlcMaxSub;
-  return g < 1 ? 1 : (int)g;
-}
-// the plan of one group: window bits from the SUB-group's size; sub-groups are whole sub-batches of the
-// per-signature path (kSplitItems), so that no launch of the fallback straddles two of them
-RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups) {
-  if (groups <= 1) return rlc_plan(scheme, cnt, window_bits ? window_bits : rlc_default_bits(cnt));
-  const size_t align = cnt >= 2 * kSplitItems ? kSplitItems : 64;
-  RlcPlan probe = rlc_plan(scheme, cnt, window_bits ? window_bits : 8, groups, align);
-  return rlc_plan(scheme, cnt, window_bits ? window_bits : rlc_default_bits(probe.sub), groups, align);
-}
-int check_rlc_bits(int window_bits) {
-  if (window_bits && !rlc_bits_ok(window_bits))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "window_bits must be 0 (automatic) or one of 4, 6, 8, 12, 14, 16");
-  return DSV_OK;
-}
-int rlc_random_key(ChaChaKey& key) {
-  uint8_t* p = reinterpret_cast<uint8_t*>(key.w);
-  size_t have = 0;
-  while (have < sizeof key.w) {
-    const ssize_t got = getrandom(p + have, sizeof key.w - have, 0);
-    if (got < 0) {
-      if (errno == EINTR) continue;
-      return fail(DSV_ERR_HIP, "getrandom: %s (the batch weights must be unpredictable)", strerror(errno));
-    }
-    have += (size_t)got;
-  }
-  return DSV_OK;
 }
 // sub-groups per group, forced (DSV_RLC_SUBGROUPS, dsv_debug_rlc_subgroups; tests and tools); 0: by the history
 std::atomic<int> g_rlc_force_groups{getenv("DSV_RLC_SUBGROUPS") ? atoi(getenv("DSV_RLC_SUBGROUPS")) : 0};
 // pinned host words the device writes: [0] the history counter, [1] calls completed, [2] the long history
-// counter, [4 ..] a ring of verdict slots for callers whose `accepted` is pageable memory
-constexpr u32 kRlcSlots = 60, kRlcSlot0 = 4;
+// counter, [4 ..] a ring of verdict slots for callers whose `accepted` is pageable memory, [64 ..] the same
+// three counters of the keyed calls (dsv_keyed_rlc.hip: they never touch the unkeyed ones)
+constexpr u32 kRlcSlots = 60, kRlcSlot0 = 4, kRlcKeyed0 = kRlcSlot0 + kRlcSlots, kRlcPinnedWords = kRlcKeyed0 + 4;
 int ensure_rlc_pinned(Context& ctx) {
   std::lock_guard<std::mutex> lk(ctx.rlc_pinned_mu);
   if (ctx.rlc_pinned) return DSV_OK;
   u32* p = nullptr;
-  HIP_TRY(hipHostMalloc((void**)&p, (kRlcSlot0 + kRlcSlots) * sizeof(u32), hipHostMallocDefault));
-  for (u32 k = 0; k < kRlcSlot0 + kRlcSlots; k++) p[k] = 0;
+  HIP_TRY(hipHostMalloc((void**)&p, kRlcPinnedWords * sizeof(u32), hipHostMallocDefault));
+  for (u32 k = 0; k < kRlcPinnedWords; k++) p[k] = 0;
   p[0] = 1;  // the first call of a device checks a sample and runs in sub-groups
+  p[kRlcKeyed0] = 1;  // (keyed: runs in sub-groups)
   ctx.rlc_pinned = p;
   return DSV_OK;
 }
 }  // namespace
 namespace dsvh {
+int rlc_forced_groups() { return g_rlc_force_groups.load(std::memory_order_relaxed); }
+u32* rlc_keyed_history(Context& ctx) {
+  if (ensure_rlc_pinned(ctx) != DSV_OK) return nullptr;
+  return ctx.rlc_pinned + kRlcKeyed0;
+}
 int rlc_history(Context& ctx) {
   if (ensure_rlc_pinned(ctx) != DSV_OK) return -1;
   return (int)*reinterpret_cast<volatile u32*>(ctx.rlc_pinned);

@@ -111,9 +111,7 @@ k_build_key_tables(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P
 }
 
 // ------------------------------------------------------------------------------------------
-// One lane per item, grid-stride.  The accumulator starts at -R; u*Gen and c*PK are table additions;
-// the verdict is the identity test inside the last one.  NCHAIN = 2 (double): both equations share u,
-// c and the key index and run through the same code, (G, PK, R) then (G', PK', R').
+// One lane per item, grid-stride (keyed.h: keyed_item_ok).
 // ------------------------------------------------------------------------------------------
 template <int SCHEME>
 __global__ void __launch_bounds__(kKeyedBlock)
@@ -122,38 +120,9 @@ k_verify_keyed(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c, con
                const u32* __restrict__ key_idx, size_t n, const u32* __restrict__ tables,
                const uint8_t* __restrict__ key_ok, size_t k, const u32* __restrict__ gtab0,
                const u32* __restrict__ gtab1, uint8_t* __restrict__ ok) {
-  constexpr int NP = SCHEME == 0 ? 1 : 2;
-  constexpr int NCHAIN = SCHEME == 1 ? 2 : 1;
 #pragma unroll 1
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const u32 idx = key_idx[i];
-    if ((size_t)idx >= k) {  // no table is read for an index out of range
-      ok[i] = 0;
-      continue;
-    }
-    bool good = (valid[i] != 0) & (key_ok[idx] != 0);
-    u32 us[8], cs[8];
-    load_words8(us, u, i);
-    load_words8(cs, c, i);
-    const bool u_ok = words_lt(us, kR32);
-    good &= u_ok;
-    if (!u_ok) us[7] &= 0x0fffffffu;  // keep the recodings in range; the verdict is 0 anyway
-    const u32* kt = tables + (size_t)idx * NP * kKeyPointWords;
-#pragma unroll 1
-    for (int h = 0; h < NCHAIN; h++) {
-      const uint8_t* Rsrc = h ? Rp_uv : R_uv;
-      Fe ru, rv;
-      good &= load_fq_signed(ru, Rsrc, 2 * i, true);  // -R
-      good &= load_fq(rv, Rsrc, 2 * i + 1);
-      Ext acc = ext_from_affine(ru, rv);
-      if (SCHEME == 2)
-        acc = key_accumulate(acc, us, kt + kKeyPointWords);  // u * Gen from the key's Gen table
-      else
-        acc = fixed_base_accumulate(acc, us, h ? gtab1 : gtab0);
-      good &= key_accumulate_is_identity(acc, cs, kt + (size_t)h * kKeyPointWords);
-    }
-    ok[i] = good ? 1 : 0;
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    ok[i] = keyed_item_ok<SCHEME>(u, c, valid, R_uv, Rp_uv, key_idx, i, tables, key_ok, k, gtab0, gtab1) ? 1 : 0;
 }
 
 // affine (u, v) of an entry: u = ((v+u) - (v-u)) / 2, v = ((v+u) + (v-u)) / 2, canonical LE

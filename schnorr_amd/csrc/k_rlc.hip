@@ -40,147 +40,11 @@
 //   k_rlc_sample_decide / k_rlc_verdict   the sample's and the call's verdicts (dsv_rlc.hip: no host round trip)
 // Every kernel of the chain returns at once when word 0 of the group's flag block is set (the sample
 // found a wrong signature: the per-signature kernels decide).
-#include "common.h"
+#define DSV_RLC_KERNELS 1
 #include "rlc.h"
-#include "stdrng.h"
 
 namespace dsv {
 
-namespace {
-constexpr int kPtWords = 32;     // affine niels (v+u, v-u, 2d*uv): 27 words, padded to one 128-byte line
-constexpr int kNielsWords = 36;  // (v+u, v-u, z, 2d*t)
-
-// signed binary expansion of r (non-adjacent form, 85 non-zero digits, top digit +2^252):
-// r = kRNafPos - kRNafNeg, checked at compile time below
-__device__ constexpr u32 kRNafPos[8] = {0x00004100u, 0x10a01080u, 0x11081084u, 0xa8882094u,
-                                        0x01444000u, 0x08884001u, 0x85440029u, 0x1080050au};
-__device__ constexpr u32 kRNafNeg[8] = {0x29091449u, 0x40090221u, 0x44400001u, 0x02200000u,
-                                        0x00100500u, 0x02210500u, 0x20105080u, 0x02025020u};
-constexpr u32 kRWords[8] = DSV_R32;
-constexpr bool naf_is_r() {
-  const u32 pos[8] = {0x00004100u, 0x10a01080u, 0x11081084u, 0xa8882094u, 0x01444000u, 0x08884001u, 0x85440029u, 0x1080050au};
-  const u32 neg[8] = {0x29091449u, 0x40090221u, 0x44400001u, 0x02200000u, 0x00100500u, 0x02210500u, 0x20105080u, 0x02025020u};
-  u64 borrow = 0;
-  for (int i = 0; i < 8; i++) {
-    const u64 d = (u64)pos[i] - neg[i] - borrow;
-    if ((u32)d != kRWords[i]) return false;
-    borrow = (d >> 63) & 1;
-    if (pos[i] & neg[i]) return false;
-  }
-  return borrow == 0;
-}
-static_assert(naf_is_r(), "kRNafPos - kRNafNeg must be the subgroup order r");
-
-DSV_DEV void fr_add(u32 (&out)[8], const u32 (&a)[8], const u32 (&b)[8]) {  // a + b mod r (a, b < r)
-  u32 s[8], d[8];
-  u32 carry = 0, borrow = 0;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const u64 y = (u64)a[j] + b[j] + carry;
-    s[j] = (u32)y;
-    carry = (u32)(y >> 32);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const u64 y = (u64)s[j] - kR32[j] - borrow;
-    d[j] = (u32)y;
-    borrow = (u32)(y >> 63);
-  }
-  const bool ge = borrow == 0;  // (r < 2^252: a + b never carries out of 256 bits)
-#pragma unroll
-  for (int j = 0; j < 8; j++) out[j] = ge ? d[j] : s[j];
-}
-
-DSV_DEV void store_pt(u32* p, const ANiels& n) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  u32 w[28];
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    w[i] = n.vpu.l[i];
-    w[NL + i] = n.vmu.l[i];
-    w[2 * NL + i] = n.t2d.l[i];
-  }
-  w[27] = 0;
-#pragma unroll
-  for (int k = 0; k < 7; k++) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-}
-DSV_DEV ANiels load_pt(const u32* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  u32 w[28];
-#pragma unroll
-  for (int k = 0; k < 7; k++) {
-    const uint4 x = q[k];
-    w[4 * k] = x.x, w[4 * k + 1] = x.y, w[4 * k + 2] = x.z, w[4 * k + 3] = x.w;
-  }
-  ANiels n;
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    n.vpu.l[i] = w[i];
-    n.vmu.l[i] = w[NL + i];
-    n.t2d.l[i] = w[2 * NL + i];
-  }
-  return n;
-}
-DSV_DEV void store_niels(u32* p, const Niels& n) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  u32 w[kNielsWords];
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    w[i] = n.vpu.l[i];
-    w[NL + i] = n.vmu.l[i];
-    w[2 * NL + i] = n.z.l[i];
-    w[3 * NL + i] = n.t2d.l[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 9; k++) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-}
-DSV_DEV Niels load_niels(const u32* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  u32 w[kNielsWords];
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const uint4 x = q[k];
-    w[4 * k] = x.x, w[4 * k + 1] = x.y, w[4 * k + 2] = x.z, w[4 * k + 3] = x.w;
-  }
-  Niels n;
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    n.vpu.l[i] = w[i];
-    n.vmu.l[i] = w[NL + i];
-    n.z.l[i] = w[2 * NL + i];
-    n.t2d.l[i] = w[3 * NL + i];
-  }
-  return n;
-}
-DSV_DEV Niels niels_neg(const Niels& n) {
-  Niels r;
-  r.vpu = n.vmu;
-  r.vmu = n.vpu;
-  r.z = n.z;
-  r.t2d = fe_neg2(n.t2d);
-  return r;
-}
-
-// -u^2 + v^2 == 1 + d u^2 v^2, as 2 v^2 == 2 u^2 + 2 + (2d) u^2 v^2 (u, v: fe_mul outputs)
-DSV_DEV bool on_curve(const Fe& u, const Fe& v) {
-  const Fe uu = fe_sqr(u), vv = fe_sqr(v);
-  const Fe rhs = fe_mul(fe_mul(uu, vv), fe_const(kD2));
-  const Fe a = fe_carry(fe_dbl(vv));                                           // < 3q
-  const Fe b0 = fe_carry(fe_add(fe_dbl(uu), fe_dbl(fe_one())));                // < 5q
-  const Fe b = fe_carry(fe_add(b0, rhs));                                      // < 6.5q, limbs < 2^29 + 8
-  return fe_equal(a, b);
-}
-// (v+u, v-u, 2d*uv) of (u, v), or of (-u, v) — forms as ext_to_niels stores them
-DSV_DEV ANiels affine_niels(const Fe& u, const Fe& v, bool negate) {
-  ANiels n;
-  const Fe s = fe_carry(fe_add(v, u)), d = fe_sub2(v, u);
-  const Fe t = fe_mul(fe_mul(u, v), fe_const(kD2));
-  n.vpu = negate ? d : s;
-  n.vmu = negate ? s : d;
-  n.t2d = negate ? fe_neg2(t) : t;
-  return n;
-}
-}  // namespace
 
 // ---- per item ---------------------------------------------------------------------------------
 // What an item contributes (SCHEME 0 single, 1 double, 2 var-generator; p.lpts "long" points with
@@ -189,93 +53,6 @@ DSV_DEV ANiels affine_niels(const Fe& u, const Fe& v, bool negate) {
 //   double  ... and u G' + c PK' - R'   : long { PK: z c, PK': z' c }, short { -R: z, -R': z' }, fixed { G: z u, G': z' u }
 //   vargen  u Gen + c PK - R            : long { PK: z c, Gen: z u },  short { -R: z },          fixed { }
 // (/root/reference/src/keys/public.rs:121-130, :222-244, :401-415), z and z' independent.
-namespace {
-// which items a workgroup's sub-group covers (rlc.h: RlcPlan)
-struct SubView {
-  u32 g;      // the sub-group (blockIdx.y)
-  u32 base;   // its first item in the group's arrays
-  u32 first;  // first item of this pass inside the sub-group
-  u32 n;      // items of this pass
-  u32 total;  // items of the sub-group
-};
-DSV_DEV SubView sub_view(const RlcPlan& p) {
-  SubView v;
-  v.g = blockIdx.y;
-  if (p.groups == 1) {
-    v.base = 0, v.first = p.first, v.n = p.n, v.total = p.total;
-  } else {
-    v.base = v.g * p.sub;
-    const u32 left = p.items - v.base;
-    v.total = left < p.sub ? left : p.sub;
-    v.first = 0, v.n = v.total;
-  }
-  return v;
-}
-struct PrepOut {
-  size_t gi;  // the item's place in the group's arrays (inputs, ok)
-  u32 i;      // ... in its sub-group (points, weights)
-  u32 il;     // ... and in the range this pass covers (the digit rows)
-  u32 total;  // items of the sub-group
-  const RlcPlan& p;
-  u32* pts;
-  uint16_t* digits;
-};
-// loads one point, folds its range check into `good`, returns "is on the curve", stores it as affine niels
-DSV_DEV bool prep_point(const PrepOut& o, const uint8_t* __restrict__ uv, int slot, bool negate, bool& good) {
-  Fe pu, pv;
-  good &= load_fq(pu, uv, 2 * o.gi);
-  good &= load_fq(pv, uv, 2 * o.gi + 1);
-  store_pt(o.pts + ((size_t)slot * o.total + o.i) * kPtWords, affine_niels(pu, pv, negate));
-  return on_curve(pu, pv);
-}
-// e' = e + k r, k uniform below floor(2^(wpk c) / r): the same multiple of a point of the prime-order
-// subgroup (any other point fails the subgroup test anyway), but uniform over ALL wpk * c bits —
-// without it the top window of a 252-bit scalar has a few thousand (c = 16: 2^12) digits only, and
-// its buckets get runs 16 times as long as the others: a lane per bucket would wait for those.
-// Then one digit per window into the point's row of that window (digit 0: the entry enters no bucket).
-DSV_DEV void emit_long(const PrepOut& o, u32 (&e)[8], u32 kr, int slot) {
-  const RlcPlan& p = o.p;
-  u64 carry = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const u64 t = (u64)kR32[k] * kr + e[k] + carry;
-    e[k] = (u32)t;
-    carry = t >> 32;
-  }
-  const u32 mask = (1u << p.c) - 1u;
-#pragma unroll 1
-  for (int w = 0; w < p.wpk; w++) {
-    const u32 d = e[0] & mask;
-#pragma unroll
-    for (int k = 0; k < 7; k++) e[k] = __funnelshift_r(e[k], e[k + 1], p.c);
-    e[7] >>= p.c;
-    o.digits[(size_t)(w * p.lpts + slot) * p.row_stride + o.il] = (uint16_t)d;
-  }
-}
-DSV_DEV void emit_short(const PrepOut& o, const u32 (&zz)[8], int slot) {
-  const RlcPlan& p = o.p;
-  u32 z[5] = {zz[0], zz[1], zz[2], zz[3], zz[4]};
-  const u32 mask = (1u << p.c) - 1u;
-  const size_t first = (size_t)p.wpk * p.lpts;
-#pragma unroll 1
-  for (int w = 0; w < p.wr; w++) {
-    const u32 d = z[0] & mask;
-#pragma unroll
-    for (int k = 0; k < 4; k++) z[k] = __funnelshift_r(z[k], z[k + 1], p.c);
-    z[4] >>= p.c;
-    o.digits[(first + (size_t)(w * p.spts + slot)) * p.row_stride + o.il] = (uint16_t)d;
-  }
-}
-// wr * c >= 128 random bits from five keystream words: every window of z is uniform
-DSV_DEV void draw_z(u32 (&z)[8], const u32* blk, int zbits, bool good) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int left = zbits - 32 * k;
-    const u32 m = left >= 32 ? ~0u : (left > 0 ? (1u << left) - 1u : 0u);
-    z[k] = (good && k < 5) ? (blk[k] & m) : 0u;
-  }
-}
-}  // namespace
 
 template <int SCHEME>
 __global__ void __launch_bounds__(256)
@@ -791,7 +568,8 @@ DSV_DEV Xp xp_identity() {
 // 256 threads = 4 waves x 64 points.  Workgroups [0, g): flags |= kRlcTorsion unless r * S_l == O.
 // Workgroups [g, 2g): W_l = 2^pos(l) * S_l, pos = bit position inside the scalar the window belongs to
 // (every lane runs the workgroup's longest chain and keeps its own result once it is there).
-// Workgroup 2g: W_lanes = (sum f_i) * G (+ (sum f'_i) * G') from the fixed-base tables, one lane.
+// Workgroup 2g: W_lanes = (sum f_i) * G (+ (sum f'_i) * G') from the fixed-base tables, one lane (+ the
+// sub-group's key term of a registered key set, keyed_rlc.h, when key_terms is given).
 // The LAST of the g + 1 workgroups that produce a W (a counter in the sub-group's flag words) also adds
 // them all up and tests the sum for the identity — r05 had a kernel of its own for that, 0.07 ms behind
 // this one; here it runs in the shadow of the subgroup test's longer chains (337 point operations against
@@ -828,7 +606,8 @@ DSV_DEV bool xp_sum_is_identity(const u32* __restrict__ W, u32 count, u32* sh, u
 }  // namespace
 __global__ void __launch_bounds__(256)
 k_rlc_scale(const u32* __restrict__ S, size_t S_stride, const u32* __restrict__ fsum, const u32* __restrict__ tableG,
-            const u32* __restrict__ tableG2, RlcPlan p, u32* __restrict__ W, size_t W_stride, u32* __restrict__ gflags) {
+            const u32* __restrict__ tableG2, RlcPlan p, u32* __restrict__ W, size_t W_stride, u32* __restrict__ gflags,
+            const u32* __restrict__ key_terms) {
   if (gflags[0]) return;  // (uniform: no barrier is left waiting)
   __shared__ u32 sh[2 * 4 * NL * 64];
   __shared__ __attribute__((aligned(16))) u32 tree[64 * kNielsWords];
@@ -849,6 +628,7 @@ k_rlc_scale(const u32* __restrict__ S, size_t S_stride, const u32* __restrict__ 
         load_words8(f, reinterpret_cast<const uint8_t*>(fsum), k);
         fg = fixed_base_accumulate(fg, f, k ? tableG2 : tableG);
       }
+      if (key_terms) fg = ext_add_niels(fg, load_niels(key_terms + (size_t)blockIdx.y * kNielsWords));
       store_niels(W + (size_t)lanes * kNielsWords, ext_to_niels(fg));
     }
   } else {
@@ -1000,6 +780,11 @@ hipError_t launch_rlc_buckets(int scheme, const RlcPlan& p, const RlcBuffers& b,
   if (scheme == 0) hipLaunchKernelGGL(k_rlc_prep<0>, grid, block, 0, s, in, key, p, b, ok);
   else if (scheme == 1) hipLaunchKernelGGL(k_rlc_prep<1>, grid, block, 0, s, in, key, p, b, ok);
   else hipLaunchKernelGGL(k_rlc_prep<2>, grid, block, 0, s, in, key, p, b, ok);
+  return launch_rlc_sort(p, b, second, s);
+}
+
+hipError_t launch_rlc_sort(const RlcPlan& p, const RlcBuffers& b, bool second, hipStream_t s) {
+  const unsigned G = p.groups;
   const unsigned tiles = (p.row_stride + kRlcTile - 1) / kRlcTile;
   hipLaunchKernelGGL(k_rlc_part1, dim3(p.rows * tiles, G), dim3(256), 0, s, p, b);
   hipLaunchKernelGGL(k_rlc_part2, dim3(p.bins, G), dim3(256), 0, s, p, b);
@@ -1011,7 +796,7 @@ hipError_t launch_rlc_buckets(int scheme, const RlcPlan& p, const RlcBuffers& b,
 }
 
 hipError_t launch_rlc_finish(const RlcPlan& p, const RlcBuffers& b, const uint32_t* tableG, const uint32_t* tableG2,
-                             bool merged, hipStream_t s) {
+                             bool merged, hipStream_t s, const uint32_t* key_terms) {
   const unsigned G = p.groups;
   if (merged) hipLaunchKernelGGL(k_rlc_merge, dim3(grid_for(p.buckets, 64), G), dim3(64), 0, s, p, b);
   const unsigned side = 1u << p.half;
@@ -1029,7 +814,7 @@ hipError_t launch_rlc_finish(const RlcPlan& p, const RlcBuffers& b, const uint32
   hipLaunchKernelGGL(k_rlc_sum<3>, dim3(g3, G), dim3(64), 0, s, b.tmp[0], b.tmp_stride[0], p, b.tmp[1], b.tmp_stride[1], b, g3);
   const unsigned lanes = (unsigned)p.windows * p.c, g = (lanes + 63) / 64;
   hipLaunchKernelGGL(k_rlc_scale, dim3(2 * g + 1, G), dim3(256), 0, s, b.tmp[1], b.tmp_stride[1], b.fsum, tableG, tableG2, p,
-                     b.tmp[0], b.tmp_stride[0], b.flags);
+                     b.tmp[0], b.tmp_stride[0], b.flags, key_terms);
   return hipGetLastError();
 }
 

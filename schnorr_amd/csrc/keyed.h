@@ -107,6 +107,59 @@ DSV_DEV bool key_accumulate_is_identity(Ext acc, const u32 (&s)[8], const u32* _
   for (int w = 0; w < kKeyWindows - 1; w++) acc = ext_add_aniels(acc, load_key_aniels(table, w, next_key_digit(y)));
   return ext_add_aniels_is_identity(acc, load_key_aniels(table, kKeyWindows - 1, next_key_digit(y)));
 }
+// acc + (the part of s * P in windows 4 part .. 4 part + 3): eight lanes, part = 0 .. 7, share one
+// product; word `part` of the recoding holds its four digits (selected without a dynamic register index)
+DSV_DEV Ext key_accumulate_part(Ext acc, const u32 (&s)[8], const u32* __restrict__ table, int part) {
+  u32 y[8];
+  recode_key(y, s);
+  u32 word = y[0];
+#pragma unroll
+  for (int q = 1; q < 8; q++) word = part == q ? y[q] : word;
+#pragma unroll 1
+  for (int w = 0; w < 4; w++) {
+    const int d = (int)((word >> (kKeyBits * w)) & 0xffu) - 128;
+    acc = ext_add_aniels(acc, load_key_aniels(table, 4 * part + w, d));
+  }
+  return acc;
+}
+
+// the verdict of item i (k_verify_keyed, and the gated fallback of the keyed fast accept, k_keyed_rlc.hip):
+// the accumulator starts at -R; u*Gen and c*PK are table additions; the verdict is the identity test inside
+// the last one.  NCHAIN = 2 (double): both equations share u, c and the key index and run through the same
+// code, (G, PK, R) then (G', PK', R').  No table is read for an index out of range.
+template <int SCHEME>
+DSV_DEV bool keyed_item_ok(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c,
+                           const uint8_t* __restrict__ valid, const uint8_t* __restrict__ R_uv,
+                           const uint8_t* __restrict__ Rp_uv, const u32* __restrict__ key_idx, size_t i,
+                           const u32* __restrict__ tables, const uint8_t* __restrict__ key_ok, size_t k,
+                           const u32* __restrict__ gtab0, const u32* __restrict__ gtab1) {
+  constexpr int NP = SCHEME == 0 ? 1 : 2;
+  constexpr int NCHAIN = SCHEME == 1 ? 2 : 1;
+  const u32 idx = key_idx[i];
+  if ((size_t)idx >= k) return false;
+  bool good = (valid[i] != 0) & (key_ok[idx] != 0);
+  u32 us[8], cs[8];
+  load_words8(us, u, i);
+  load_words8(cs, c, i);
+  const bool u_ok = words_lt(us, kR32);
+  good &= u_ok;
+  if (!u_ok) us[7] &= 0x0fffffffu;  // keep the recodings in range; the verdict is 0 anyway
+  const u32* kt = tables + (size_t)idx * NP * kKeyPointWords;
+#pragma unroll 1
+  for (int h = 0; h < NCHAIN; h++) {
+    const uint8_t* Rsrc = h ? Rp_uv : R_uv;
+    Fe ru, rv;
+    good &= load_fq_signed(ru, Rsrc, 2 * i, true);  // -R
+    good &= load_fq(rv, Rsrc, 2 * i + 1);
+    Ext acc = ext_from_affine(ru, rv);
+    if (SCHEME == 2)
+      acc = key_accumulate(acc, us, kt + kKeyPointWords);  // u * Gen from the key's Gen table
+    else
+      acc = fixed_base_accumulate(acc, us, h ? gtab1 : gtab0);
+    good &= key_accumulate_is_identity(acc, cs, kt + (size_t)h * kKeyPointWords);
+  }
+  return good;
+}
 
 }  // namespace dsv
 #endif

@@ -84,8 +84,10 @@ inline RlcPlan rlc_range(const RlcPlan& whole, size_t first, size_t cnt) {
 }
 // scheme: 0 single, 1 double, 2 var-generator (k_rlc.hip: k_rlc_prep says which point gets which scalar);
 // `items` in `groups` sub-groups (of ceil(items / groups) items rounded up to `align`; fewer sub-groups if
-// that leaves some empty)
-inline RlcPlan rlc_plan(int scheme, size_t items, int c, int groups = 1, size_t align = 1) {
+// that leaves some empty).  keyed: the pass of a registered key set (keyed_rlc.h) — the keys' terms are one
+// fixed-base product per key outside the buckets, so only the nonce points have rows: no key windows
+// (wpk = 0, lpts = 0), the fixed-base terms on G / G' as in the unkeyed plan
+inline RlcPlan rlc_plan(int scheme, size_t items, int c, int groups = 1, size_t align = 1, bool keyed = false) {
   RlcPlan p;
   if (groups < 1) groups = 1;
   if (groups > kRlcMaxSub) groups = kRlcMaxSub;
@@ -99,12 +101,12 @@ inline RlcPlan rlc_plan(int scheme, size_t items, int c, int groups = 1, size_t 
   p.n = p.sub;
   p.first = 0;
   p.total = p.sub;
-  p.lpts = scheme == 0 ? 1 : 2;
+  p.lpts = keyed ? 0 : (scheme == 0 ? 1 : 2);
   p.spts = scheme == 1 ? 2 : 1;
   p.fixed = scheme == 0 ? 1 : (scheme == 1 ? 2 : 0);
   p.c = c;
   p.half = c / 2;
-  p.wpk = (252 + c - 1) / c;
+  p.wpk = keyed ? 0 : (252 + c - 1) / c;
   p.wr = (128 + c - 1) / c;
   p.windows = p.wpk + p.wr;
   const int side = 1 << p.half;
@@ -180,8 +182,12 @@ hipError_t launch_rlc(int scheme, const RlcPlan& p, const RlcBuffers& b, const R
 hipError_t launch_rlc_begin(const RlcBuffers& b, hipStream_t s);
 hipError_t launch_rlc_buckets(int scheme, const RlcPlan& range, const RlcBuffers& b, const RlcInputs& in,
                               ChaChaKey key, uint8_t* ok, bool second, hipStream_t s);
+// key_terms (may be null): one extended-niels point per sub-group that the tail adds to its sum before the
+// identity test (keyed_rlc.h: the registered keys' terms)
 hipError_t launch_rlc_finish(const RlcPlan& whole, const RlcBuffers& b, const uint32_t* tableG,
-                             const uint32_t* tableG2, bool merged, hipStream_t s);
+                             const uint32_t* tableG2, bool merged, hipStream_t s, const uint32_t* key_terms = nullptr);
+// the bucket pass after the prep: partition, runs, order, accumulation (b.counters zeroed beforehand)
+hipError_t launch_rlc_sort(const RlcPlan& p, const RlcBuffers& b, bool second, hipStream_t s);
 // The sample check, on the device: flags[0] of the group = 1 ("skip the aggregate") when one of the `count`
 // items from `first` on is well-formed (valid byte set, u < r, every key coordinate < q) and still has
 // verdict 0 in sample_ok — a WRONG signature; malformed ones do not count, they stay out of the sum.
@@ -205,3 +211,238 @@ void launch_rlc_verdict(const uint32_t* flags, RlcVerdictArgs a, uint32_t* accep
 void launch_rlc_chain(const uint32_t* first, uint32_t* second, uint32_t subs, hipStream_t s);
 
 }  // namespace dsv
+
+#ifdef DSV_RLC_KERNELS
+// ---- device helpers of the bucket pass, shared by k_rlc.hip and k_keyed_rlc.hip ------------------------
+#include "common.h"
+#include "stdrng.h"
+
+namespace dsv {
+
+namespace {
+constexpr int kPtWords = 32;     // affine niels (v+u, v-u, 2d*uv): 27 words, padded to one 128-byte line
+constexpr int kNielsWords = 36;  // (v+u, v-u, z, 2d*t)
+
+// signed binary expansion of r (non-adjacent form, 85 non-zero digits, top digit +2^252):
+// r = kRNafPos - kRNafNeg, checked at compile time below
+__device__ constexpr u32 kRNafPos[8] = {0x00004100u, 0x10a01080u, 0x11081084u, 0xa8882094u,
+                                        0x01444000u, 0x08884001u, 0x85440029u, 0x1080050au};
+__device__ constexpr u32 kRNafNeg[8] = {0x29091449u, 0x40090221u, 0x44400001u, 0x02200000u,
+                                        0x00100500u, 0x02210500u, 0x20105080u, 0x02025020u};
+constexpr u32 kRWords[8] = DSV_R32;
+constexpr bool naf_is_r() {
+  const u32 pos[8] = {0x00004100u, 0x10a01080u, 0x11081084u, 0xa8882094u, 0x01444000u, 0x08884001u, 0x85440029u, 0x1080050au};
+  const u32 neg[8] = {0x29091449u, 0x40090221u, 0x44400001u, 0x02200000u, 0x00100500u, 0x02210500u, 0x20105080u, 0x02025020u};
+  u64 borrow = 0;
+  for (int i = 0; i < 8; i++) {
+    const u64 d = (u64)pos[i] - neg[i] - borrow;
+    if ((u32)d != kRWords[i]) return false;
+    borrow = (d >> 63) & 1;
+    if (pos[i] & neg[i]) return false;
+  }
+  return borrow == 0;
+}
+static_assert(naf_is_r(), "kRNafPos - kRNafNeg must be the subgroup order r");
+
+DSV_DEV void fr_add(u32 (&out)[8], const u32 (&a)[8], const u32 (&b)[8]) {  // a + b mod r (a, b < r)
+  u32 s[8], d[8];
+  u32 carry = 0, borrow = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const u64 y = (u64)a[j] + b[j] + carry;
+    s[j] = (u32)y;
+    carry = (u32)(y >> 32);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const u64 y = (u64)s[j] - kR32[j] - borrow;
+    d[j] = (u32)y;
+    borrow = (u32)(y >> 63);
+  }
+  const bool ge = borrow == 0;  // (r < 2^252: a + b never carries out of 256 bits)
+#pragma unroll
+  for (int j = 0; j < 8; j++) out[j] = ge ? d[j] : s[j];
+}
+
+DSV_DEV void store_pt(u32* p, const ANiels& n) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  u32 w[28];
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    w[i] = n.vpu.l[i];
+    w[NL + i] = n.vmu.l[i];
+    w[2 * NL + i] = n.t2d.l[i];
+  }
+  w[27] = 0;
+#pragma unroll
+  for (int k = 0; k < 7; k++) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+DSV_DEV ANiels load_pt(const u32* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  u32 w[28];
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    const uint4 x = q[k];
+    w[4 * k] = x.x, w[4 * k + 1] = x.y, w[4 * k + 2] = x.z, w[4 * k + 3] = x.w;
+  }
+  ANiels n;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    n.vpu.l[i] = w[i];
+    n.vmu.l[i] = w[NL + i];
+    n.t2d.l[i] = w[2 * NL + i];
+  }
+  return n;
+}
+DSV_DEV void store_niels(u32* p, const Niels& n) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  u32 w[kNielsWords];
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    w[i] = n.vpu.l[i];
+    w[NL + i] = n.vmu.l[i];
+    w[2 * NL + i] = n.z.l[i];
+    w[3 * NL + i] = n.t2d.l[i];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; k++) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+DSV_DEV Niels load_niels(const u32* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  u32 w[kNielsWords];
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const uint4 x = q[k];
+    w[4 * k] = x.x, w[4 * k + 1] = x.y, w[4 * k + 2] = x.z, w[4 * k + 3] = x.w;
+  }
+  Niels n;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    n.vpu.l[i] = w[i];
+    n.vmu.l[i] = w[NL + i];
+    n.z.l[i] = w[2 * NL + i];
+    n.t2d.l[i] = w[3 * NL + i];
+  }
+  return n;
+}
+DSV_DEV Niels niels_neg(const Niels& n) {
+  Niels r;
+  r.vpu = n.vmu;
+  r.vmu = n.vpu;
+  r.z = n.z;
+  r.t2d = fe_neg2(n.t2d);
+  return r;
+}
+
+// -u^2 + v^2 == 1 + d u^2 v^2, as 2 v^2 == 2 u^2 + 2 + (2d) u^2 v^2 (u, v: fe_mul outputs)
+DSV_DEV bool on_curve(const Fe& u, const Fe& v) {
+  const Fe uu = fe_sqr(u), vv = fe_sqr(v);
+  const Fe rhs = fe_mul(fe_mul(uu, vv), fe_const(kD2));
+  const Fe a = fe_carry(fe_dbl(vv));                                           // < 3q
+  const Fe b0 = fe_carry(fe_add(fe_dbl(uu), fe_dbl(fe_one())));                // < 5q
+  const Fe b = fe_carry(fe_add(b0, rhs));                                      // < 6.5q, limbs < 2^29 + 8
+  return fe_equal(a, b);
+}
+// (v+u, v-u, 2d*uv) of (u, v), or of (-u, v) — forms as ext_to_niels stores them
+DSV_DEV ANiels affine_niels(const Fe& u, const Fe& v, bool negate) {
+  ANiels n;
+  const Fe s = fe_carry(fe_add(v, u)), d = fe_sub2(v, u);
+  const Fe t = fe_mul(fe_mul(u, v), fe_const(kD2));
+  n.vpu = negate ? d : s;
+  n.vmu = negate ? s : d;
+  n.t2d = negate ? fe_neg2(t) : t;
+  return n;
+}
+}  // namespace
+
+// ---- per item ---------------------------------------------------------------------------------
+namespace {
+// which items a workgroup's sub-group covers (rlc.h: RlcPlan)
+struct SubView {
+  u32 g;      // the sub-group (blockIdx.y)
+  u32 base;   // its first item in the group's arrays
+  u32 first;  // first item of this pass inside the sub-group
+  u32 n;      // items of this pass
+  u32 total;  // items of the sub-group
+};
+DSV_DEV SubView sub_view(const RlcPlan& p) {
+  SubView v;
+  v.g = blockIdx.y;
+  if (p.groups == 1) {
+    v.base = 0, v.first = p.first, v.n = p.n, v.total = p.total;
+  } else {
+    v.base = v.g * p.sub;
+    const u32 left = p.items - v.base;
+    v.total = left < p.sub ? left : p.sub;
+    v.first = 0, v.n = v.total;
+  }
+  return v;
+}
+struct PrepOut {
+  size_t gi;  // the item's place in the group's arrays (inputs, ok)
+  u32 i;      // ... in its sub-group (points, weights)
+  u32 il;     // ... and in the range this pass covers (the digit rows)
+  u32 total;  // items of the sub-group
+  const RlcPlan& p;
+  u32* pts;
+  uint16_t* digits;
+};
+// loads one point, folds its range check into `good`, returns "is on the curve", stores it as affine niels
+DSV_DEV bool prep_point(const PrepOut& o, const uint8_t* __restrict__ uv, int slot, bool negate, bool& good) {
+  Fe pu, pv;
+  good &= load_fq(pu, uv, 2 * o.gi);
+  good &= load_fq(pv, uv, 2 * o.gi + 1);
+  store_pt(o.pts + ((size_t)slot * o.total + o.i) * kPtWords, affine_niels(pu, pv, negate));
+  return on_curve(pu, pv);
+}
+// e' = e + k r, k uniform below floor(2^(wpk c) / r): the same multiple of a point of the prime-order
+// subgroup (any other point fails the subgroup test anyway), but uniform over ALL wpk * c bits —
+// without it the top window of a 252-bit scalar has a few thousand (c = 16: 2^12) digits only, and
+// its buckets get runs 16 times as long as the others: a lane per bucket would wait for those.
+// Then one digit per window into the point's row of that window (digit 0: the entry enters no bucket).
+DSV_DEV void emit_long(const PrepOut& o, u32 (&e)[8], u32 kr, int slot) {
+  const RlcPlan& p = o.p;
+  u64 carry = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const u64 t = (u64)kR32[k] * kr + e[k] + carry;
+    e[k] = (u32)t;
+    carry = t >> 32;
+  }
+  const u32 mask = (1u << p.c) - 1u;
+#pragma unroll 1
+  for (int w = 0; w < p.wpk; w++) {
+    const u32 d = e[0] & mask;
+#pragma unroll
+    for (int k = 0; k < 7; k++) e[k] = __funnelshift_r(e[k], e[k + 1], p.c);
+    e[7] >>= p.c;
+    o.digits[(size_t)(w * p.lpts + slot) * p.row_stride + o.il] = (uint16_t)d;
+  }
+}
+DSV_DEV void emit_short(const PrepOut& o, const u32 (&zz)[8], int slot) {
+  const RlcPlan& p = o.p;
+  u32 z[5] = {zz[0], zz[1], zz[2], zz[3], zz[4]};
+  const u32 mask = (1u << p.c) - 1u;
+  const size_t first = (size_t)p.wpk * p.lpts;
+#pragma unroll 1
+  for (int w = 0; w < p.wr; w++) {
+    const u32 d = z[0] & mask;
+#pragma unroll
+    for (int k = 0; k < 4; k++) z[k] = __funnelshift_r(z[k], z[k + 1], p.c);
+    z[4] >>= p.c;
+    o.digits[(first + (size_t)(w * p.spts + slot)) * p.row_stride + o.il] = (uint16_t)d;
+  }
+}
+// wr * c >= 128 random bits from five keystream words: every window of z is uniform
+DSV_DEV void draw_z(u32 (&z)[8], const u32* blk, int zbits, bool good) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int left = zbits - 32 * k;
+    const u32 m = left >= 32 ? ~0u : (left > 0 ? (1u << left) - 1u : 0u);
+    z[k] = (good && k < 5) ? (blk[k] & m) : 0u;
+  }
+}
+}  // namespace
+
+}  // namespace dsv
+#endif

@@ -871,6 +871,34 @@ def keyed_workspace_bytes(n):
     return int(_lib.load().dsv_keyed_workspace_bytes(ctypes.c_size_t(n)))
 
 
+def keyed_rlc_workspace_bytes(n, k, window_bits=0):
+    """dsv_keyed_rlc_workspace_bytes: device bytes of KeySet.verify_rlc_dev's workspace for n items over k keys"""
+    b = int(_lib.load().dsv_keyed_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_size_t(k), ctypes.c_int(window_bits)))
+    if b == 0:
+        raise ValueError("window_bits must be 0 or one of 4, 6, 8, 12, 14, 16")
+    return b
+
+
+def keyed_rlc_plan_info(scheme, n, k, window_bits=0, groups=1):
+    """dsv_keyed_rlc_plan_info as a dict (no GPU needed): rlc_plan_info's fields for the keyed plan"""
+    out = (ctypes.c_uint64 * 24)()
+    _lib.check(_lib.load().dsv_keyed_rlc_plan_info(ctypes.c_int(_KEYED_SCHEMES[scheme]), ctypes.c_size_t(n),
+                                                   ctypes.c_size_t(k), ctypes.c_int(window_bits), ctypes.c_int(groups),
+                                                   out))
+    names = ("c", "half", "wpk", "wr", "windows", "nseg", "nseg2", "fine_bits", "kmul", "lpts", "spts", "fixed",
+             "entries", "buckets", "tmp0", "tmp1", "coarse_bits", "rows", "row_stride", "bins", "bin_cap", "groups",
+             "sub", "bytes")
+    return dict(zip(names, [int(x) for x in out]))
+
+
+def keyed_rlc_history(device=0, set_to=-1):
+    """dsv_debug_keyed_rlc_history: the keyed calls' own history counter; returns the value before the call"""
+    r = _lib.load().dsv_debug_keyed_rlc_history(ctypes.c_int(device), ctypes.c_int(set_to))
+    if r < 0:
+        _lib.check(r)
+    return r
+
+
 class KeySet:
     """Registered keys (dsv_keyset_*): per-key fixed-base tables on the device that is current when the set
     is built; verify by key index.  scheme: "single" (PK), "double" (PK, PK') or "vargen" (PK, Gen).
@@ -985,3 +1013,27 @@ class KeySet:
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_dev" % self.scheme)(
             self._handle(), _tp(u, 32), *[_tp(p, 64) for p in pts], ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
             ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))
+
+    def verify_rlc_dev(self, *args, stream=None, window_bits=0, accepted_out=None):
+        """The keyed fast accept (dsv_verify_*_keyed_rlc_dev): the verdicts of verify_dev, through one aggregate
+        test per group (or sub-group) when it is valid.  Same arguments; workspace: >=
+        keyed_rlc_workspace_bytes(n, k, window_bits) bytes.  accepted_out None: the call waits for the stream and
+        returns the accepted flag (bool); an int32 tensor on the batch's device or in pinned host memory: written
+        by the device, the call does not block and returns None.  Never inside a graph capture (refused)."""
+        if len(args) < 2:
+            raise ValueError("verify_rlc_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, idx, m = self._pts(args[:-2])
+        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
+        tensors = [u] + list(pts) + [m]
+        n, dev = _rows(*zip(tensors, [32] + [64] * len(pts) + [32], names))
+        ip = _idx(idx, n, dev, "idx")
+        if idx.dim() != 1 or idx.shape[0] != n:
+            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        arg, box = _accepted_arg(accepted_out, dev)
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_rlc_workspace_bytes(n, self.k, window_bits), dev, "workspace")
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_rlc_dev" % self.scheme)(
+            self._handle(), _tp(u, 32), *[_tp(p, 64) for p in pts], ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
+        return bool(box.value) if box is not None else None

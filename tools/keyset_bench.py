@@ -2,12 +2,22 @@
 
     python tools/keyset_bench.py [--out FILE] [--log2-n 20] [--reps 21] [--ks 1,64,4096,16384]
     python tools/keyset_bench.py --one SCHEME K [--reps R]      # one measurement (what the driver runs)
+    python tools/keyset_bench.py --rlc [--out FILE] [--log2-ns 18,20] [--ks ...] [--workloads valid,wrong_h8,wrong_h0]
+    python tools/keyset_bench.py --soak 10000000 [--out FILE]   # keyed fast accept against the keyed per-signature path
 
 Each (scheme, k) is measured in a process of its own: n items signed under k keys, inputs in HBM, then
 dsv_verify_<scheme>_keyed_dev and dsv_verify_<scheme>_dev on the gathered keys alternate on one stream,
 each timed with device events after warm-up; the verdict vectors must be equal.  Reported: the median of
 the reps per path, the ratio, and the key-set build time per key (dsv_keyset_create, host arrays in,
 blocking).  Kernel times: run one measurement under `rocprofv3 --kernel-trace --stats -- python ...`.
+
+--rlc: the keyed fast accept (KeySet.verify_rlc_dev) against the keyed per-signature path (KeySet.verify_dev)
+and the unkeyed fast accept (verify_*_rlc_dev on the gathered keys), on identical device-resident inputs, for
+three workloads: all valid; one wrong item with the history counters at 8 (a caller whose batches fail now and
+then: sub-groups); one wrong item with the counters at 0 (the first wrong batch after a run of valid ones).
+The counters are set before every timed call; all three paths must return the same verdict vector.
+--soak: calls of 2^20 items (a fresh set of wrong items, none to many, and forced sub-groups per call) through
+both keyed paths; reports how many verdicts differ.
 """
 import argparse
 import json
@@ -115,6 +125,154 @@ def measure(scheme, k, log2_n, reps, warmup=3):
     return out
 
 
+def _signed_batch(E, scheme, k, n, seed):
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    sk = _scalars(rng, k, 0x07)
+    gen = None
+    if scheme == "single":
+        P0, P1 = E.public_keys(sk), None
+    elif scheme == "double":
+        P0, P1 = E.public_keys(sk, 0), E.public_keys(sk, 1)
+    else:
+        gen = E.public_keys(_scalars(rng, k, 0x07))
+        P0, P1 = E.public_keys(sk, Gen=gen), gen
+    idx = rng.integers(0, k, size=n).astype(np.uint32)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
+    Rp = None
+    if scheme == "single":
+        u, R = E.sign_single(sk[idx], m, r)
+    elif scheme == "double":
+        u, R, Rp = E.sign_double(sk[idx], m, r)
+    else:
+        u, R = E.sign_vargen(sk[idx], gen[idx], m, r)
+    return P0, P1, idx, u, R, Rp, m
+
+
+def measure_rlc(scheme, k, log2_n, reps, workload, warmup=2, bits=0):
+    """median ms of keyed per-signature, keyed fast accept and unkeyed fast accept on one workload (bits: the
+    keyed fast accept's window bits, 0 = automatic)"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    dev = "cuda:0"
+    n = 1 << log2_n
+    P0, P1, idx, u, R, Rp, m = _signed_batch(E, scheme, k, n, 4321 + k)
+    if workload != "valid":
+        u[n // 3, 0] ^= 1  # one wrong signature
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    du, dR, dm, di = T(u), T(R), T(m), T(idx.view(np.int32))
+    dRp = T(Rp) if Rp is not None else None
+    g0, g1 = T(P0[idx]), (T(P1[idx]) if P1 is not None else None)
+    ks = E.KeySet(scheme, P0, P1)
+    ok = {p: torch.empty(n, dtype=torch.uint8, device=dev) for p in ("keyed", "keyed_rlc", "rlc")}
+    ws_k = torch.empty(E.keyed_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws_kr = torch.empty(E.keyed_rlc_workspace_bytes(n, k, bits), dtype=torch.uint8, device=dev)
+    ws_r = torch.empty(E.rlc_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    acc = {p: torch.zeros(1, dtype=torch.int32, device=dev) for p in ("keyed_rlc", "rlc")}
+    items = (du, dR) + ((dRp,) if dRp is not None else ()) + (di, dm)
+    hist = {"valid": None, "wrong_h8": 8, "wrong_h0": 0}[workload]
+    torch.cuda.synchronize()
+
+    def keyed():
+        ks.verify_dev(*items, ok["keyed"], ws_k)
+
+    def keyed_rlc():
+        if hist is not None:
+            E.keyed_rlc_history(0, hist)
+        ks.verify_rlc_dev(*items, ok["keyed_rlc"], ws_kr, window_bits=bits, accepted_out=acc["keyed_rlc"])
+
+    def rlc():
+        if hist is not None:
+            E.rlc_history(0, hist)
+            E.rlc_history_long(0, 0)  # (no guarded second stage: the keyed path has none)
+        a = dict(accepted_out=acc["rlc"])
+        if scheme == "single":
+            E.verify_single_rlc_dev(du, dR, g0, dm, ok["rlc"], ws_r, **a)
+        elif scheme == "double":
+            E.verify_double_rlc_dev(du, dR, dRp, g0, g1, dm, ok["rlc"], ws_r, **a)
+        else:
+            E.verify_vargen_rlc_dev(du, dR, g0, g1, dm, ok["rlc"], ws_r, **a)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    fns = {"keyed": keyed, "keyed_rlc": keyed_rlc, "rlc": rlc}
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    t = {p: [] for p in fns}
+    for _ in range(reps):
+        for p, f in fns.items():
+            t[p].append(timed(f))
+    torch.cuda.synchronize()
+    v = {p: o.cpu().numpy() for p, o in ok.items()}
+    assert (v["keyed"] == v["keyed_rlc"]).all(), "keyed fast accept differs at %d items" % int((v["keyed"] != v["keyed_rlc"]).sum())
+    assert (v["keyed"] == v["rlc"]).all(), "unkeyed fast accept differs at %d items" % int((v["keyed"] != v["rlc"]).sum())
+    med = lambda x: sorted(x)[len(x) // 2]
+    out = {"scheme": scheme, "k": k, "n": n, "workload": workload, "reps": reps, "window_bits": bits}
+    for p in fns:
+        out[p + "_ms"] = round(med(t[p]), 4)
+    out["keyed_rlc_vs_keyed"] = round(med(t["keyed"]) / med(t["keyed_rlc"]), 3)
+    out["keyed_rlc_vs_rlc"] = round(med(t["rlc"]) / med(t["keyed_rlc"]), 3)
+    out["accepted"] = {p: int(a.item()) for p, a in acc.items()}
+    out["verdicts_equal"] = True
+    ks.close()
+    return out
+
+
+def soak(total, log2_n=20, k=64, seed=99):
+    """keyed fast accept vs keyed per-signature verdicts over `total` verdicts, all three schemes in turn"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    dev = "cuda:0"
+    n = 1 << log2_n
+    rng = np.random.default_rng(seed)
+    done, differ, calls, accepted = 0, 0, 0, 0
+    sets = {}
+    while done < total:
+        scheme = SCHEMES[calls % 3]
+        if scheme not in sets:
+            P0, P1, idx, u, R, Rp, m = _signed_batch(E, scheme, k, n, seed + calls)
+            sets[scheme] = (E.KeySet(scheme, P0, P1), idx, u, R, Rp, m)
+        ks, idx, u, R, Rp, m = sets[scheme]
+        uu = u.copy()
+        wrong = rng.choice([0, 0, 1, 3, 1000])
+        uu[rng.integers(0, n, size=wrong), 0] ^= 1
+        E.rlc_subgroups(int(rng.choice([0, 0, 1, 2, 16])))
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        items = (T(uu), T(R)) + ((T(Rp),) if Rp is not None else ()) + (T(idx.view(np.int32)), T(m))
+        ok_a = torch.empty(n, dtype=torch.uint8, device=dev)
+        ok_b = torch.empty(n, dtype=torch.uint8, device=dev)
+        ks.verify_dev(*items, ok_a, torch.empty(E.keyed_workspace_bytes(n), dtype=torch.uint8, device=dev))
+        acc = ks.verify_rlc_dev(*items, ok_b, torch.empty(E.keyed_rlc_workspace_bytes(n, k), dtype=torch.uint8, device=dev))
+        torch.cuda.synchronize()
+        differ += int((ok_a != ok_b).sum().item())
+        accepted += int(acc)
+        done += n
+        calls += 1
+    E.rlc_subgroups(0)
+    for v in sets.values():
+        v[0].close()
+    return {"verdicts": done, "calls": calls, "accepted_calls": accepted, "differ": differ, "k": k, "n": n}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", nargs=2, metavar=("SCHEME", "K"))
@@ -124,7 +282,44 @@ def main():
     ap.add_argument("--schemes", default=",".join(SCHEMES))
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=600)
+    ap.add_argument("--rlc", action="store_true")
+    ap.add_argument("--one-rlc", nargs=4, metavar=("SCHEME", "K", "LOG2N", "WORKLOAD"))
+    ap.add_argument("--log2-ns", default="18,20")
+    ap.add_argument("--workloads", default="valid,wrong_h8,wrong_h0")
+    ap.add_argument("--soak", type=int)
+    ap.add_argument("--bits", type=int, default=0)
     a = ap.parse_args()
+    if a.soak:
+        row = soak(a.soak)
+        print(json.dumps(row), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(row, f, indent=1)
+        return
+    if a.one_rlc:
+        s, k, l2, w = a.one_rlc
+        print(json.dumps(measure_rlc(s, int(k), int(l2), a.reps, w, bits=a.bits)), flush=True)
+        return
+    if a.rlc:
+        rows = []
+        for scheme in a.schemes.split(","):
+            for l2 in [int(x) for x in a.log2_ns.split(",")]:
+                for k in [int(x) for x in a.ks.split(",")]:
+                    for w in a.workloads.split(","):
+                        cmd = [sys.executable, os.path.abspath(__file__), "--one-rlc", scheme, str(k), str(l2), w,
+                               "--reps", str(a.reps)]
+                        p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+                        if p.returncode != 0:
+                            sys.stderr.write(p.stdout + p.stderr)
+                            raise SystemExit("measurement %s k=%d 2^%d %s failed with status %d" % (scheme, k, l2, w, p.returncode))
+                        row = json.loads(p.stdout.strip().splitlines()[-1])
+                        print(json.dumps(row), flush=True)
+                        rows.append(row)
+                        if a.out:
+                            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                            with open(a.out, "w") as f:
+                                json.dump({"rows": rows}, f, indent=1)
+        return
     if a.one:
         print(json.dumps(measure(a.one[0], int(a.one[1]), a.log2_n, a.reps)), flush=True)
         return
