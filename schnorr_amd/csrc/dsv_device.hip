@@ -313,6 +313,9 @@ namespace {
 int verify_mixed_dev(const void* kinds, const void* u, const void* R_uv, const void* Rp_uv, const void* PK_uv,
                      const void* PKp_uv, const void* m, size_t n, size_t n_double, void* ok, void* workspace,
                      void* stream, bool fast, int* accepted) {
+  hipStream_t s = (hipStream_t)stream;
+  if (fast)
+    if (int r = refuse_capture(s, "the fast accept")) return r;
   if (n == 0 || !fast) {
     if (int r = rlc_clear_accepted(accepted)) return r;
   }
@@ -323,7 +326,6 @@ int verify_mixed_dev(const void* kinds, const void* u, const void* R_uv, const v
   RlcVerdictTarget vt;
   if (fast)
     if (int r = rlc_verdict_target(ctx, accepted, vt)) return r;
-  hipStream_t s = (hipStream_t)stream;
   const size_t ns = n - n_double, nd = n_double;
   Stager st(static_cast<uint8_t*>(workspace));
   void* scratch = st.take(split_scratch_bytes(n));

@@ -338,7 +338,7 @@ struct Items {
   Items at(size_t off, size_t pt_bytes = 64) const {
     Items r = *this;
     r.u = u + 32 * off;
-    for (int k = 0; k < layout(scheme).points; k++) r.pt[k] = pt[k] + pt_bytes * off;
+    for (int k = 0; k < layout(scheme).points; k++) r.pt[k] = pt[k] ? pt[k] + pt_bytes * off : nullptr;
     r.m = m ? m + 32 * off : nullptr;
     return r;
   }
@@ -414,6 +414,11 @@ int rlc_split_groups(size_t cnt, int window_bits);
 RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups, bool keyed = false);
 int check_rlc_bits(int window_bits);
 int rlc_random_key(ChaChaKey& key);
+// the fast accept's weight key is drawn on the host per call: a captured call would replay it — every fast-accept
+// _dev call refuses a capturing stream before anything touches the stream or `accepted`
+int refuse_capture(hipStream_t s, const char* what);
+// out[24] of dsv_rlc_plan_info / dsv_keyed_rlc_plan_info: the plan's geometry, then its workspace bytes
+void rlc_plan_words(const RlcPlan& p, size_t bytes, uint64_t* out);
 int rlc_forced_groups();  // dsv_debug_rlc_subgroups / DSV_RLC_SUBGROUPS (0: by the history)
 // the keyed calls' own pinned counters ([0] history, [1] calls, [2] long history; k_rlc_verdict's layout), or null
 u32* rlc_keyed_history(Context& ctx);

@@ -63,12 +63,9 @@ size_t keyed_rlc_workspace_for(size_t n, size_t k, int window_bits) {
     }
   return most;
 }
-KeyedIn keyed_at(const KeyedIn& in, size_t off) {
-  return KeyedIn{in.scheme, in.u + 32 * off, in.R + 64 * off, in.Rp ? in.Rp + 64 * off : nullptr, in.m + 32 * off};
-}
 
 // enqueues everything on `s`; *accepted_dev (device-accessible, may be null) = every group was decided by its aggregates
-int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n, uint8_t* ok,
+int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n, uint8_t* ok,
                  void* workspace, hipStream_t s, int window_bits, u32* accepted_dev, u32* history_words) {
   const int scheme = in.scheme;
   const size_t group = rlc_group_items(n);
@@ -81,7 +78,7 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const ui
     const size_t cnt = n - off < group ? n - off : group;
     if (g >= kRlcMaxGroupsPerCall) return fail(DSV_ERR_TOO_LARGE, "more than %zu groups", kRlcMaxGroupsPerCall);
     va.ngroups = (u32)g + 1;
-    const KeyedIn gin = keyed_at(in, off);
+    const Items gin = in.at(off);
     if (!window_bits && cnt < keyed_rlc_min_auto(scheme)) {
       va.subs[g] = 0;  // (the verdict kernel: not decided by an aggregate)
       enqueue_keyed(ctx, ks, gin, idx + off, cnt, ok + off, workspace, s);
@@ -97,10 +94,10 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const ui
     ChaChaKey key;
     if (int r = rlc_random_key(key)) return r;
     HIP_TRY(launch_rlc_begin(cv.b, s));
-    launch_hash(gin.items(), cnt, cv.w.c, cv.w.valid, s);
+    launch_hash(gin, cnt, cv.w.c, cv.w.valid, s);
     RlcInputs ri = {};
     ri.u = gin.u, ri.c = cv.w.c, ri.valid = cv.w.valid;
-    ri.r[0] = gin.R, ri.r[1] = gin.Rp;
+    ri.r[0] = gin.R(), ri.r[1] = gin.Rp();
     HIP_TRY(launch_keyed_rlc_prep(scheme, plan, cv.b, cv.kb, ri, idx + off, keys, key, ok + off, s));
     // The keys' terms (a few dozen dependent point operations on a few workgroups: ~0.2 ms of latency at 64
     // keys) need only the prep: they run on an internal stream beside the bucket pass and join before the tail
@@ -119,7 +116,7 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const ui
       HIP_TRY(launch_keyed_rlc_terms(scheme, plan, cv.b, cv.kb, keys, s));
     }
     HIP_TRY(launch_rlc_finish(plan, cv.b, ctx.table[0], ctx.table[1], false, s, cv.kb.terms));
-    launch_keyed_fallback(scheme, plan, gin.u, cv.w.c, cv.w.valid, gin.R, gin.Rp, idx + off, keys, ctx.table[0],
+    launch_keyed_fallback(scheme, plan, gin.u, cv.w.c, cv.w.valid, gin.R(), gin.Rp(), idx + off, keys, ctx.table[0],
                           ctx.table[1], ok + off, cv.b.flags, s);
     HIP_TRY(hipGetLastError());
   }
@@ -130,30 +127,18 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const ui
   return DSV_OK;
 }
 
-int verify_keyed_rlc_dev(const dsv_keyset* ks, const KeyedIn& in, const void* idx, size_t n, void* ok, void* workspace,
+int verify_keyed_rlc_dev(const dsv_keyset* ks, const Items& in, const void* idx, size_t n, void* ok, void* workspace,
                          size_t workspace_bytes, void* stream, int window_bits, int* accepted) {
   const hipStream_t s = (hipStream_t)stream;
-  if (int r = check_n(n)) return r;
   std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  Context* kctx = nullptr;
-  if (int r = check_set(ks, in.scheme, kctx)) return r;
-  // the weights' key is drawn on the host per call: a captured call would replay it — refused before anything
-  // else touches the stream or the runtime
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(s, &cap));
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "the keyed fast accept cannot be captured (its weights are drawn per call)");
+  Context* cp = nullptr;
+  if (int r = check_set(ks, in.scheme, n, cp)) return r;
+  if (int r = refuse_capture(s, "the keyed fast accept")) return r;
   if (n == 0) return rlc_clear_accepted(accepted);
-  if (in.any_null() || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int r = check_rlc_bits(window_bits)) return r;
-  const size_t need = keyed_rlc_workspace_for(n, ks->k, window_bits) + 256;
-  if (workspace_bytes < need)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  Context* octx = nullptr;
-  if (int r = device_context(ok, octx)) return r;
-  if (octx != kctx)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
-  Context& ctx = *kctx;
+  if (int r = check_keyed_dev(ks, cp, in, idx, n, ok, workspace, workspace_bytes, window_bits,
+                              dsv_keyed_rlc_workspace_bytes))
+    return r;
+  Context& ctx = *cp;
   DSV_ON_DEVICE(ctx);
   u32* history_words = rlc_keyed_history(ctx);
   if (!history_words) return fail(DSV_ERR_HIP, "no pinned memory for the keyed history counters");
@@ -181,44 +166,26 @@ int dsv_keyed_rlc_plan_info(int scheme, size_t n, size_t k, int window_bits, int
     return fail(DSV_ERR_INVALID_ARGUMENT, "bad argument");
   if (int r = check_rlc_bits(window_bits)) return r;
   const RlcPlan p = rlc_group_plan(scheme, n, window_bits, groups, true);
-  const uint64_t v[24] = {(uint64_t)p.c, (uint64_t)p.half, (uint64_t)p.wpk, (uint64_t)p.wr, (uint64_t)p.windows,
-                          (uint64_t)p.nseg, (uint64_t)p.nseg2, (uint64_t)p.fine_bits, p.kmul, (uint64_t)p.lpts,
-                          (uint64_t)p.spts, (uint64_t)p.fixed, p.entries, p.buckets, rlc_tmp_points(p, 0),
-                          rlc_tmp_points(p, 1), (uint64_t)p.coarse_bits, p.rows, p.row_stride, p.bins, p.bin_cap,
-                          p.groups, p.sub,
-                          carve_keyed_rlc(reinterpret_cast<void*>((uintptr_t)4096), n, n, p, scheme, k).bytes};
-  for (int j = 0; j < 24; j++) out[j] = v[j];
+  rlc_plan_words(p, carve_keyed_rlc(reinterpret_cast<void*>((uintptr_t)4096), n, n, p, scheme, k).bytes, out);
   return DSV_OK;
-}
-
-int dsv_debug_keyed_rlc_history(int device, int set) {
-  if (device < 0 || device >= kMaxDevices || !g_ctx[device].ready.load(std::memory_order_acquire))
-    return fail(DSV_ERR_NOT_INITIALIZED, "device %d is not initialised", device);
-  Context& ctx = g_ctx[device];
-  DSV_ON_DEVICE(ctx);
-  u32* h = rlc_keyed_history(ctx);
-  if (!h) return DSV_ERR_HIP;
-  const int before = (int)*reinterpret_cast<volatile u32*>(h);
-  if (set >= 0) *reinterpret_cast<volatile u32*>(h) = (u32)set;
-  return before;
 }
 
 int dsv_verify_single_keyed_rlc_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
                                     const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
                                     void* stream, int window_bits, int* accepted) {
-  return verify_keyed_rlc_dev(ks, keyed_in(0, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes, stream,
+  return verify_keyed_rlc_dev(ks, make_items(0, u, {R_uv}, m), key_idx, n, ok, workspace, workspace_bytes, stream,
                               window_bits, accepted);
 }
 int dsv_verify_double_keyed_rlc_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
                                     const void* key_idx, const void* m, size_t n, void* ok, void* workspace,
                                     size_t workspace_bytes, void* stream, int window_bits, int* accepted) {
-  return verify_keyed_rlc_dev(ks, keyed_in(1, u, R_uv, Rp_uv, m), key_idx, n, ok, workspace, workspace_bytes, stream,
-                              window_bits, accepted);
+  return verify_keyed_rlc_dev(ks, make_items(1, u, {R_uv, Rp_uv}, m), key_idx, n, ok, workspace, workspace_bytes,
+                              stream, window_bits, accepted);
 }
 int dsv_verify_vargen_keyed_rlc_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
                                     const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
                                     void* stream, int window_bits, int* accepted) {
-  return verify_keyed_rlc_dev(ks, keyed_in(2, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes, stream,
+  return verify_keyed_rlc_dev(ks, make_items(2, u, {R_uv}, m), key_idx, n, ok, workspace, workspace_bytes, stream,
                               window_bits, accepted);
 }
 

@@ -129,21 +129,16 @@ int create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, bool is_wire
 }
 
 
-int verify_keyed_dev(const dsv_keyset* ks, const KeyedIn& in, const void* idx, size_t n, void* ok, void* workspace,
+size_t keyed_need(size_t n, size_t, int) { return keyed_ws_bytes(n); }
+
+int verify_keyed_dev(const dsv_keyset* ks, const Items& in, const void* idx, size_t n, void* ok, void* workspace,
                      size_t workspace_bytes, void* stream) {
-  if (int r = check_n(n)) return r;
   std::shared_lock<std::shared_mutex> rl(g_ks_mu);
-  Context* kctx = nullptr;
-  if (int r = check_set(ks, in.scheme, kctx)) return r;
+  Context* cp = nullptr;
+  if (int r = check_set(ks, in.scheme, n, cp)) return r;
   if (n == 0) return DSV_OK;
-  if (in.any_null() || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  if (workspace_bytes < keyed_ws_bytes(n))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, keyed_ws_bytes(n));
-  Context* octx = nullptr;
-  if (int r = device_context(ok, octx)) return r;
-  if (octx != kctx)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
-  Context& ctx = *kctx;
+  if (int r = check_keyed_dev(ks, cp, in, idx, n, ok, workspace, workspace_bytes, 0, keyed_need)) return r;
+  Context& ctx = *cp;
   DSV_ON_DEVICE(ctx);
   enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, workspace, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
@@ -151,13 +146,12 @@ int verify_keyed_dev(const dsv_keyset* ks, const KeyedIn& in, const void* idx, s
 }
 
 // host arrays: chunks through the context's staging, on its null stream
-int verify_keyed_host(const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n, uint8_t* ok) {
-  if (int r = check_n(n)) return r;
+int verify_keyed_host(const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n, uint8_t* ok) {
   std::shared_lock<std::shared_mutex> rl(g_ks_mu);
   Context* cp = nullptr;
-  if (int r = check_set(ks, in.scheme, cp)) return r;
+  if (int r = check_set(ks, in.scheme, n, cp)) return r;
   if (n == 0) return DSV_OK;
-  if (in.any_null() || !idx || !ok) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (keyed_any_null(in) || !idx || !ok) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   Context& ctx = *cp;
   DSV_HOST_LOCK();
   const int np = in.scheme == 1 ? 2 : 1;  // the signature's points
@@ -177,10 +171,9 @@ int verify_keyed_host(const dsv_keyset* ks, const KeyedIn& in, const uint32_t* i
     H2D(du, in.u + off * 32, cnt * 32);
     H2D(dm, in.m + off * 32, cnt * 32);
     H2D(di, idx + off, cnt * 4);
-    H2D(dR, in.R + off * 64, cnt * 64);
-    if (dRp) H2D(dRp, in.Rp + off * 64, cnt * 64);
-    const KeyedIn d{in.scheme, du, dR, dRp, dm};
-    enqueue_keyed(ctx, ks, d, (const uint32_t*)di, cnt, dok, ws, 0);
+    H2D(dR, in.R() + off * 64, cnt * 64);
+    if (dRp) H2D(dRp, in.Rp() + off * 64, cnt * 64);
+    enqueue_keyed(ctx, ks, make_items(in.scheme, du, {dR, dRp}, dm), (const uint32_t*)di, cnt, dok, ws, 0);
     HIP_TRY(hipGetLastError());
     D2H(ok + off, dok, cnt);
     HIP_TRY(hipStreamSynchronize(0));
@@ -190,20 +183,35 @@ int verify_keyed_host(const dsv_keyset* ks, const KeyedIn& in, const uint32_t* i
 }  // namespace
 
 // checks shared by the _dev and host forms (shared lock held)
-int check_set(const dsv_keyset* ks, int scheme, Context*& ctx) {
+int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx) {
+  if (int r = check_n(n)) return r;
   if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
   if (int r = keyset_context(ks, ctx)) return r;
   if (ks->scheme != scheme)
     return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
   return DSV_OK;
 }
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
+                    const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
+                    size_t (*need)(size_t n, size_t k, int window_bits)) {
+  if (keyed_any_null(in) || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int r = check_rlc_bits(window_bits)) return r;
+  const size_t bytes = need(n, ks->k, window_bits);
+  if (workspace_bytes < bytes)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, bytes);
+  Context* octx = nullptr;
+  if (int r = device_context(ok, octx)) return r;
+  if (octx != ctx)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
+  return DSV_OK;
+}
 std::shared_mutex& keyset_mutex() { return g_ks_mu; }
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
-void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n,
+void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,
                    uint8_t* ok, void* workspace, hipStream_t s) {
   const Workspace w = carve(workspace, n);
-  launch_hash(in.items(), n, w.c, w.valid, s);
-  launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R, in.Rp, idx, n, ks->tables, ks->key_ok, ks->k,
+  launch_hash(in, n, w.c, w.valid, s);
+  launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R(), in.Rp(), idx, n, ks->tables, ks->key_ok, ks->k,
                       ctx.table[0], ctx.table[1], ok, s);
 }
 
@@ -273,32 +281,31 @@ int dsv_keyset_key_ok(const dsv_keyset* ks, uint8_t* out) {
 int dsv_verify_single_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
                                 const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  return verify_keyed_dev(ks, keyed_in(0, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes, stream);
+  return verify_keyed_dev(ks, make_items(0, u, {R_uv}, m), key_idx, n, ok, workspace, workspace_bytes, stream);
 }
 int dsv_verify_double_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
                                 const void* key_idx, const void* m, size_t n, void* ok, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  return verify_keyed_dev(ks, keyed_in(1, u, R_uv, Rp_uv, m), key_idx, n, ok, workspace,
-                          workspace_bytes, stream);
+  return verify_keyed_dev(ks, make_items(1, u, {R_uv, Rp_uv}, m), key_idx, n, ok, workspace, workspace_bytes,
+                          stream);
 }
 int dsv_verify_vargen_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
                                 const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  return verify_keyed_dev(ks, keyed_in(2, u, R_uv, nullptr, m), key_idx, n, ok, workspace, workspace_bytes,
-                          stream);
+  return verify_keyed_dev(ks, make_items(2, u, {R_uv}, m), key_idx, n, ok, workspace, workspace_bytes, stream);
 }
 
 int dsv_verify_single_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint32_t* key_idx,
                             const uint8_t* m, size_t n, uint8_t* ok) {
-  return verify_keyed_host(ks, keyed_in(0, u, R_uv, nullptr, m), key_idx, n, ok);
+  return verify_keyed_host(ks, make_items(0, u, {R_uv}, m), key_idx, n, ok);
 }
 int dsv_verify_double_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
                             const uint32_t* key_idx, const uint8_t* m, size_t n, uint8_t* ok) {
-  return verify_keyed_host(ks, keyed_in(1, u, R_uv, Rp_uv, m), key_idx, n, ok);
+  return verify_keyed_host(ks, make_items(1, u, {R_uv, Rp_uv}, m), key_idx, n, ok);
 }
 int dsv_verify_vargen_keyed(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint32_t* key_idx,
                             const uint8_t* m, size_t n, uint8_t* ok) {
-  return verify_keyed_host(ks, keyed_in(2, u, R_uv, nullptr, m), key_idx, n, ok);
+  return verify_keyed_host(ks, make_items(2, u, {R_uv}, m), key_idx, n, ok);
 }
 
 int dsv_debug_keyset_entry(const dsv_keyset* ks, size_t key, int point, int window, int digit, uint8_t out64[64]) {

@@ -117,6 +117,24 @@ int rlc_random_key(ChaChaKey& key) {
   }
   return DSV_OK;
 }
+int refuse_capture(hipStream_t s, const char* what) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) {  // no device, or not a stream: not capturing either (the
+    (void)hipGetLastError();                            // call's own checks say what is wrong)
+    return DSV_OK;
+  }
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "%s cannot be captured (its weights are drawn per call)", what);
+  return DSV_OK;
+}
+void rlc_plan_words(const RlcPlan& p, size_t bytes, uint64_t* out) {
+  const uint64_t v[24] = {(uint64_t)p.c, (uint64_t)p.half, (uint64_t)p.wpk, (uint64_t)p.wr, (uint64_t)p.windows,
+                          (uint64_t)p.nseg, (uint64_t)p.nseg2, (uint64_t)p.fine_bits, p.kmul, (uint64_t)p.lpts,
+                          (uint64_t)p.spts, (uint64_t)p.fixed, p.entries, p.buckets, rlc_tmp_points(p, 0),
+                          rlc_tmp_points(p, 1), (uint64_t)p.coarse_bits, p.rows, p.row_stride, p.bins, p.bin_cap,
+                          p.groups, p.sub, bytes};
+  for (int k = 0; k < 24; k++) out[k] = v[k];
+}
 }  // namespace dsvh
 namespace {
 // Before an aggregate is paid for, the per-signature kernel (eight lanes per signature: 0.26 ms)
@@ -169,6 +187,19 @@ int ensure_rlc_pinned(Context& ctx) {
   p[kRlcKeyed0] = 1;  // (keyed: runs in sub-groups)
   ctx.rlc_pinned = p;
   return DSV_OK;
+}
+// pinned word `word` of a device (the dsv_debug_*history* exports: tests, tools): its value before the call; set >= 0
+// overrides it
+int debug_pinned_word(int device, u32 word, int set) {
+  if (device < 0 || device >= kMaxDevices || !g_ctx[device].ready.load(std::memory_order_acquire))
+    return fail(DSV_ERR_NOT_INITIALIZED, "device %d is not initialised", device);
+  Context& ctx = g_ctx[device];
+  DSV_ON_DEVICE(ctx);
+  if (ensure_rlc_pinned(ctx) != DSV_OK) return DSV_ERR_HIP;
+  volatile u32* w = ctx.rlc_pinned + word;
+  const int before = (int)*w;
+  if (set >= 0) *w = (u32)set;
+  return before;
 }
 }  // namespace
 namespace dsvh {
@@ -455,36 +486,15 @@ int dsv_rlc_plan_info(int scheme, size_t n, int window_bits, int groups, uint64_
     return fail(DSV_ERR_INVALID_ARGUMENT, "bad argument");
   if (int r = check_rlc_bits(window_bits)) return r;
   const RlcPlan p = rlc_group_plan(scheme, n, window_bits, groups);
-  const uint64_t v[24] = {(uint64_t)p.c, (uint64_t)p.half, (uint64_t)p.wpk, (uint64_t)p.wr, (uint64_t)p.windows,
-                          (uint64_t)p.nseg, (uint64_t)p.nseg2, (uint64_t)p.fine_bits, p.kmul, (uint64_t)p.lpts,
-                          (uint64_t)p.spts, (uint64_t)p.fixed, p.entries, p.buckets, rlc_tmp_points(p, 0),
-                          rlc_tmp_points(p, 1), (uint64_t)p.coarse_bits, p.rows, p.row_stride, p.bins, p.bin_cap,
-                          p.groups, p.sub, carve_rlc(reinterpret_cast<void*>((uintptr_t)4096), n, n, p).bytes};
-  for (int k = 0; k < 24; k++) out[k] = v[k];
+  rlc_plan_words(p, carve_rlc(reinterpret_cast<void*>((uintptr_t)4096), n, n, p).bytes, out);
   return DSV_OK;
 }
 // the history counter of a device (tests, tools): > 0 = the next call checks a sample and runs in
 // sub-groups; set >= 0 overrides it
-int dsv_debug_rlc_history(int device, int set) {
-  if (device < 0 || device >= kMaxDevices || !g_ctx[device].ready.load(std::memory_order_acquire))
-    return fail(DSV_ERR_NOT_INITIALIZED, "device %d is not initialised", device);
-  Context& ctx = g_ctx[device];
-  DSV_ON_DEVICE(ctx);
-  const int h = rlc_history(ctx);
-  if (h < 0) return DSV_ERR_HIP;
-  if (set >= 0) *reinterpret_cast<volatile u32*>(ctx.rlc_pinned) = (u32)set;
-  return h;
-}
-int dsv_debug_rlc_history_long(int device, int set) {
-  if (device < 0 || device >= kMaxDevices || !g_ctx[device].ready.load(std::memory_order_acquire))
-    return fail(DSV_ERR_NOT_INITIALIZED, "device %d is not initialised", device);
-  Context& ctx = g_ctx[device];
-  DSV_ON_DEVICE(ctx);
-  if (rlc_history(ctx) < 0) return DSV_ERR_HIP;
-  const int h = (int)*reinterpret_cast<volatile u32*>(ctx.rlc_pinned + 2);
-  if (set >= 0) *reinterpret_cast<volatile u32*>(ctx.rlc_pinned + 2) = (u32)set;
-  return h;
-}
+int dsv_debug_rlc_history(int device, int set) { return debug_pinned_word(device, 0, set); }
+int dsv_debug_rlc_history_long(int device, int set) { return debug_pinned_word(device, 2, set); }
+// the keyed calls' own history counter (dsv_keyed_rlc.hip)
+int dsv_debug_keyed_rlc_history(int device, int set) { return debug_pinned_word(device, kRlcKeyed0, set); }
 int dsv_debug_rlc_subgroups(int groups) {
   const int before = g_rlc_force_groups.load();
   if (groups >= 0) g_rlc_force_groups.store(groups > kRlcMaxSub ? kRlcMaxSub : groups);
@@ -494,6 +504,7 @@ extern "C++" {
 namespace {
 // the fast accept over affine items resident in HBM
 int verify_rlc_dev(const Items& in, size_t n, void* ok, void* workspace, void* stream, int window_bits, int* accepted) {
+  if (int r = refuse_capture((hipStream_t)stream, "the fast accept")) return r;
   if (n == 0) return rlc_clear_accepted(accepted);
   if (in.any_null() || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   if (int r = check_rlc_bits(window_bits)) return r;
@@ -741,6 +752,7 @@ namespace {
 size_t wire_arrays_bytes(size_t n) { return align_up(n * 32, 256) + 4 * align_up(n * 64, 256) + align_up(n, 256); }
 int verify_wire_rlc_dev(int kind, const void* sig, const void* pk, const void* m, size_t n, void* ok,
                         void* workspace, void* stream, int window_bits, int* accepted) {
+  if (int r = refuse_capture((hipStream_t)stream, "the fast accept")) return r;
   if (n == 0) return rlc_clear_accepted(accepted);
   if (!sig || !pk || !m || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   if (((uintptr_t)sig | (uintptr_t)pk) & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");

@@ -818,13 +818,4 @@ hipError_t launch_rlc_finish(const RlcPlan& p, const RlcBuffers& b, const uint32
   return hipGetLastError();
 }
 
-hipError_t launch_rlc(int scheme, const RlcPlan& p, const RlcBuffers& b, const RlcInputs& in, ChaChaKey key,
-                      const uint32_t* tableG, const uint32_t* tableG2, uint8_t* ok, hipStream_t s) {
-  hipError_t err = launch_rlc_begin(b, s);
-  if (err != hipSuccess) return err;
-  err = launch_rlc_buckets(scheme, p, b, in, key, ok, false, s);
-  if (err != hipSuccess) return err;
-  return launch_rlc_finish(p, b, tableG, tableG2, false, s);
-}
-
 }  // namespace dsv

@@ -1,5 +1,5 @@
 // keyset_host.h — what the host units know about a registered key set (keyed.h: the tables): the handle,
-// the registry's lock and checks (dsv_keyset.hip), a keyed call's per-item inputs.
+// the registry's lock and checks (dsv_keyset.hip), what a keyed call reads of its items.
 #pragma once
 #include <shared_mutex>
 
@@ -18,30 +18,23 @@ struct dsv_keyset {
 
 namespace dsvh {
 
-// one keyed call's per-item inputs: u, the signature's points R (and R' for the double scheme), m
-struct KeyedIn {
-  int scheme;
-  const uint8_t *u, *R, *Rp, *m;
-  bool any_null() const { return !u || !R || (scheme == 1 && !Rp) || !m; }
-  Items items() const {  // (what launch_hash reads: R, R', m)
-    Items in{scheme, u};
-    in.pt[layout(scheme).R] = R;
-    if (scheme == 1) in.pt[layout(scheme).Rp] = Rp;
-    in.m = m;
-    return in;
-  }
-};
-inline KeyedIn keyed_in(int scheme, const void* u, const void* R, const void* Rp, const void* m) {
-  return KeyedIn{scheme, (const uint8_t*)u, (const uint8_t*)R, (const uint8_t*)Rp, (const uint8_t*)m};
-}
+// A keyed call's items are make_items(scheme, u, {R[, R']}, m): the signature's points in their canonical slots,
+// the key slots (PK, PK', Gen) null — the keys come from the set.
+inline bool keyed_any_null(const Items& in) { return !in.u || !in.R() || (in.scheme == 1 && !in.Rp()) || !in.m; }
 
 inline size_t keyed_ws_bytes(size_t n) { return align_up(n * 32, 256) + align_up(n, 256); }
 // live key sets: verify calls read under the shared lock, create / destroy / shutdown write under the exclusive one
 std::shared_mutex& keyset_mutex();
-// (shared lock held) ks is live, of `scheme`, on an initialised device: ctx = its context
-int check_set(const dsv_keyset* ks, int scheme, Context*& ctx);
+// (shared lock held) n is in range; ks is live, of `scheme`, on an initialised device: ctx = its context
+int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx);
+// (shared lock held, check_set passed, n > 0) the rest of a keyed _dev call's checks, in this order: null
+// pointers, the window bits (0 for the per-signature form), workspace_bytes >= need(n, ks->k, window_bits), `ok`
+// on the set's device (ctx: the set's context)
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
+                    const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
+                    size_t (*need)(size_t n, size_t k, int window_bits));
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
-void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const KeyedIn& in, const uint32_t* idx, size_t n,
+void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,
                    uint8_t* ok, void* workspace, hipStream_t s);
 
 }  // namespace dsvh

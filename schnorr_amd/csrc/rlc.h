@@ -173,12 +173,10 @@ inline size_t rlc_tmp_points(const RlcPlan& p, int k) {
   const size_t a = w * 2 * side, b = w * p.c;
   return a > b ? a : b;
 }
-// hash output c / valid of the group in, ok[i] = "item i is well-formed" and flags out; never synchronises;
-// returns the first error of a launch
-hipError_t launch_rlc(int scheme, const RlcPlan& p, const RlcBuffers& b, const RlcInputs& in, ChaChaKey key,
-                      const uint32_t* tableG, const uint32_t* tableG2, uint8_t* ok, hipStream_t s);
-// the same in pieces: begin (flags), the bucket pass of one range into b.buckets (second = false) or
-// b.buckets2, and the rest over the whole group (`merged`: the two bucket arrays are added first)
+// One aggregate from the hash output c / valid of the group `in` (ok[i] = "item i is well-formed", flags out), in
+// pieces that never synchronise and return the first error of a launch: begin (flags), the bucket pass of one
+// range into b.buckets (second = false) or b.buckets2, and the rest over the whole group (`merged`: the two bucket
+// arrays are added first)
 hipError_t launch_rlc_begin(const RlcBuffers& b, hipStream_t s);
 hipError_t launch_rlc_buckets(int scheme, const RlcPlan& range, const RlcBuffers& b, const RlcInputs& in,
                               ChaChaKey key, uint8_t* ok, bool second, hipStream_t s);

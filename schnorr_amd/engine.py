@@ -115,6 +115,7 @@ def _same_n(*arrs):
 _SCHEMES = {"single": (("u", "R", "PK", "m"), (64, 32)),
             "double": (("u", "R", "Rp", "PK", "PKp", "m"), (96, 64)),
             "vargen": (("u", "R", "PK", "Gen", "m"), (64, 64))}
+_SCHEME_CODE = {"single": 0, "double": 1, "vargen": 2}  # the C ABI's scheme argument
 _POINT_WIDTH = {"": 64, "_ext": 96, "_mont": 96}
 
 
@@ -547,32 +548,42 @@ def rlc_workspace_bytes(n, window_bits=0):
     return b
 
 
+# out[24] of dsv_rlc_plan_info / dsv_keyed_rlc_plan_info
+_PLAN_FIELDS = ("c", "half", "wpk", "wr", "windows", "nseg", "nseg2", "fine_bits", "kmul", "lpts", "spts", "fixed",
+                "entries", "buckets", "tmp0", "tmp1", "coarse_bits", "rows", "row_stride", "bins", "bin_cap", "groups",
+                "sub", "bytes")
+
+
+def _plan(fn, scheme, *args):
+    """fn(scheme code, *args, out[24]) -> dict of _PLAN_FIELDS"""
+    out = (ctypes.c_uint64 * 24)()
+    _lib.check(fn(ctypes.c_int(_SCHEME_CODE[scheme]), *args, out))
+    return dict(zip(_PLAN_FIELDS, [int(x) for x in out]))
+
+
+def _history(fn, device, set_to):
+    """a dsv_debug_*history* counter: its value before the call; set_to >= 0 overrides it"""
+    r = fn(ctypes.c_int(device), ctypes.c_int(set_to))
+    if r < 0:
+        _lib.check(r)
+    return r
+
+
 def rlc_plan_info(scheme, n, window_bits=0, groups=1):
     """dsv_rlc_plan_info as a dict (no GPU needed)"""
-    out = (ctypes.c_uint64 * 24)()
-    _lib.check(_lib.load().dsv_rlc_plan_info(ctypes.c_int({"single": 0, "double": 1, "vargen": 2}[scheme]),
-                                             ctypes.c_size_t(n), ctypes.c_int(window_bits), ctypes.c_int(groups), out))
-    names = ("c", "half", "wpk", "wr", "windows", "nseg", "nseg2", "fine_bits", "kmul", "lpts", "spts", "fixed",
-             "entries", "buckets", "tmp0", "tmp1", "coarse_bits", "rows", "row_stride", "bins", "bin_cap", "groups",
-             "sub", "bytes")
-    return dict(zip(names, [int(x) for x in out]))
+    return _plan(_lib.load().dsv_rlc_plan_info, scheme, ctypes.c_size_t(n), ctypes.c_int(window_bits),
+                 ctypes.c_int(groups))
 
 
 def rlc_history(device=0, set_to=-1):
     """dsv_debug_rlc_history: the device's fast-accept history counter (> 0: the next call checks a sample
     and runs in sub-groups); set_to >= 0 overrides it.  Returns the value before the call."""
-    r = _lib.load().dsv_debug_rlc_history(ctypes.c_int(device), ctypes.c_int(set_to))
-    if r < 0:
-        _lib.check(r)
-    return r
+    return _history(_lib.load().dsv_debug_rlc_history, device, set_to)
 
 
 def rlc_history_long(device=0, set_to=-1):
     """dsv_debug_rlc_history_long: the slow counter behind "guarded" calls; returns the value before the call"""
-    r = _lib.load().dsv_debug_rlc_history_long(ctypes.c_int(device), ctypes.c_int(set_to))
-    if r < 0:
-        _lib.check(r)
-    return r
+    return _history(_lib.load().dsv_debug_rlc_history_long, device, set_to)
 
 
 def rlc_subgroups(groups=-1):
@@ -599,7 +610,8 @@ def verify_single_rlc_dev(u, R, PK, m, ok, workspace, stream=None, window_bits=0
     """dsv_verify_single_rlc_dev: the verdict vector of verify_single_dev, through one aggregate test
     per group (or sub-group) when it is valid.  Enqueue-only when `accepted_out` (an int32 tensor on the
     device or in pinned host memory) is given: it receives 1 if every group was accepted by its aggregates
-    once the stream gets there.  Without it the call waits for `stream` and returns that as a bool."""
+    once the stream gets there.  Without it the call waits for `stream` and returns that as a bool.  Never inside
+    a graph capture (refused: the weights are drawn per call; so are the wire and mixed forms)."""
     return _dev("single", "", (u, R, PK, m), ok, workspace, stream, (window_bits, accepted_out))
 
 
@@ -859,12 +871,9 @@ def stdrng_vargen_inputs_dev(seed, sk, g, m, r, first_item=0, stream=None):
 
 
 # ------------------------------------------------------------------ registered key sets
-_KEYED_SCHEMES = {"single": 0, "double": 1, "vargen": 2}
-
-
 def keyset_bytes(scheme, k):
     """dsv_keyset_bytes: device bytes of a key set of k keys (no GPU needed)"""
-    return int(_lib.load().dsv_keyset_bytes(ctypes.c_int(_KEYED_SCHEMES[scheme]), ctypes.c_size_t(k)))
+    return int(_lib.load().dsv_keyset_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
 
 
 def keyed_workspace_bytes(n):
@@ -881,22 +890,13 @@ def keyed_rlc_workspace_bytes(n, k, window_bits=0):
 
 def keyed_rlc_plan_info(scheme, n, k, window_bits=0, groups=1):
     """dsv_keyed_rlc_plan_info as a dict (no GPU needed): rlc_plan_info's fields for the keyed plan"""
-    out = (ctypes.c_uint64 * 24)()
-    _lib.check(_lib.load().dsv_keyed_rlc_plan_info(ctypes.c_int(_KEYED_SCHEMES[scheme]), ctypes.c_size_t(n),
-                                                   ctypes.c_size_t(k), ctypes.c_int(window_bits), ctypes.c_int(groups),
-                                                   out))
-    names = ("c", "half", "wpk", "wr", "windows", "nseg", "nseg2", "fine_bits", "kmul", "lpts", "spts", "fixed",
-             "entries", "buckets", "tmp0", "tmp1", "coarse_bits", "rows", "row_stride", "bins", "bin_cap", "groups",
-             "sub", "bytes")
-    return dict(zip(names, [int(x) for x in out]))
+    return _plan(_lib.load().dsv_keyed_rlc_plan_info, scheme, ctypes.c_size_t(n), ctypes.c_size_t(k),
+                 ctypes.c_int(window_bits), ctypes.c_int(groups))
 
 
 def keyed_rlc_history(device=0, set_to=-1):
     """dsv_debug_keyed_rlc_history: the keyed calls' own history counter; returns the value before the call"""
-    r = _lib.load().dsv_debug_keyed_rlc_history(ctypes.c_int(device), ctypes.c_int(set_to))
-    if r < 0:
-        _lib.check(r)
-    return r
+    return _history(_lib.load().dsv_debug_keyed_rlc_history, device, set_to)
 
 
 class KeySet:
@@ -911,12 +911,12 @@ class KeySet:
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None):
-        if scheme not in _KEYED_SCHEMES:
-            raise ValueError("scheme must be one of %s" % sorted(_KEYED_SCHEMES))
+        if scheme not in _SCHEME_CODE:
+            raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
         self.scheme = scheme
         self._h = ctypes.c_void_p()
         L = _lib.load()
-        code = ctypes.c_int(_KEYED_SCHEMES[scheme])
+        code = ctypes.c_int(_SCHEME_CODE[scheme])
         if _wire is not None:
             rec = _arr(_wire, 32 if scheme == "single" else 64)
             _lib.check(L.dsv_keyset_create_wire(code, _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(self._h)))
@@ -993,12 +993,11 @@ class KeySet:
             self._handle(), _p(u), *[_p(p) for p in pts], _p(idx), _p(m), ctypes.c_size_t(n), _p(ok)))
         return ok
 
-    def verify_dev(self, *args, stream=None):
-        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace): verdicts into ok, enqueued on `stream` (default:
-        torch's current stream of the batch's device); does not synchronise.  idx: int32 [n], read as uint32;
-        workspace: >= keyed_workspace_bytes(n) bytes."""
+    def _dev_args(self, args, what):
+        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace), checked -> (n, dev, the input pointers in argument
+        order, ok, workspace)"""
         if len(args) < 2:
-            raise ValueError("verify_dev takes the inputs, then ok and workspace")
+            raise ValueError("%s takes the inputs, then ok and workspace" % what)
         ok, workspace = args[-2], args[-1]
         u, pts, idx, m = self._pts(args[:-2])
         names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
@@ -1007,12 +1006,19 @@ class KeySet:
         ip = _idx(idx, n, dev, "idx")
         if idx.dim() != 1 or idx.shape[0] != n:
             raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        return n, dev, [_tp(u, 32)] + [_tp(p, 64) for p in pts] + [ip, _tp(m, 32)], ok, workspace
+
+    def verify_dev(self, *args, stream=None):
+        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace): verdicts into ok, enqueued on `stream` (default:
+        torch's current stream of the batch's device); does not synchronise.  idx: int32 [n], read as uint32;
+        workspace: >= keyed_workspace_bytes(n) bytes."""
+        n, dev, ins, ok, workspace = self._dev_args(args, "verify_dev")
         ws_need = keyed_workspace_bytes(n)
         okp = _bytes_out(ok, n, dev, "ok")
         wsp = _bytes_out(workspace, ws_need, dev, "workspace")
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_dev" % self.scheme)(
-            self._handle(), _tp(u, 32), *[_tp(p, 64) for p in pts], ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))
+            self._handle(), *ins, ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
+            _stream_ptr(stream, dev)))
 
     def verify_rlc_dev(self, *args, stream=None, window_bits=0, accepted_out=None):
         """The keyed fast accept (dsv_verify_*_keyed_rlc_dev): the verdicts of verify_dev, through one aggregate
@@ -1020,20 +1026,11 @@ class KeySet:
         keyed_rlc_workspace_bytes(n, k, window_bits) bytes.  accepted_out None: the call waits for the stream and
         returns the accepted flag (bool); an int32 tensor on the batch's device or in pinned host memory: written
         by the device, the call does not block and returns None.  Never inside a graph capture (refused)."""
-        if len(args) < 2:
-            raise ValueError("verify_rlc_dev takes the inputs, then ok and workspace")
-        ok, workspace = args[-2], args[-1]
-        u, pts, idx, m = self._pts(args[:-2])
-        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
-        tensors = [u] + list(pts) + [m]
-        n, dev = _rows(*zip(tensors, [32] + [64] * len(pts) + [32], names))
-        ip = _idx(idx, n, dev, "idx")
-        if idx.dim() != 1 or idx.shape[0] != n:
-            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        n, dev, ins, ok, workspace = self._dev_args(args, "verify_rlc_dev")
         arg, box = _accepted_arg(accepted_out, dev)
         okp = _bytes_out(ok, n, dev, "ok")
         wsp = _bytes_out(workspace, keyed_rlc_workspace_bytes(n, self.k, window_bits), dev, "workspace")
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_rlc_dev" % self.scheme)(
-            self._handle(), _tp(u, 32), *[_tp(p, 64) for p in pts], ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
+            self._handle(), *ins, ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
+            _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
         return bool(box.value) if box is not None else None

@@ -2,7 +2,7 @@
 against the oracle and against the keyed per-signature path (KeySet.verify_dev) — all valid, one wrong
 signature in forced sub-groups, malformed items, order-8 components in keys and nonce points, 2^20 items,
 small batches, both kinds of `accepted` target, two streams, the keyed history counter, argument errors and
-the refusal of graph capture."""
+the refusal of graph capture (keyed and unkeyed device-pointer forms)."""
 import ctypes
 import random
 
@@ -337,3 +337,42 @@ def test_capture_is_refused(engine):
         assert (ok.cpu().numpy() == 7).all()
         # the same call outside a capture works
         assert _rlc(engine, ks, b, 8)[0] is True
+
+
+@pytest.mark.parametrize("form", ["single", "wire", "mixed"])
+def test_capture_is_refused_unkeyed(engine, form):
+    """the unkeyed device-pointer fast accepts (affine, wire records, mixed batch) draw their weights on the host
+    per call too: a capturing stream is refused as the keyed form refuses it"""
+    from schnorr_amd import _lib
+
+    b = _signed(engine, "single", 3, 1000)
+    n, PK = len(b["m"]), b["P0"][b["idx"]]
+    if form == "wire":
+        cp = engine.compress_points
+        args = TK._dev([np.concatenate([b["u"], cp(b["R"])], axis=1), cp(PK), b["m"]])
+        ws = torch.empty(engine.wire_rlc_workspace_bytes(n, 8), dtype=torch.uint8, device=DEV)
+        call = lambda ok: engine.verify_wire_rlc_dev("single", *args, ok, ws, window_bits=8)
+    elif form == "mixed":
+        u, R, PKt, m = TK._dev([b["u"], b["R"], PK, b["m"]])
+        kinds = torch.zeros(n, dtype=torch.uint8, device=DEV)
+        ws = torch.empty(engine.mixed_rlc_workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        call = lambda ok: engine.verify_mixed_rlc_dev(kinds, u, R, R, PKt, PKt, m, 0, ok, ws)
+    else:
+        args = TK._dev([b["u"], b["R"], PK, b["m"]])
+        ws = torch.empty(engine.rlc_workspace_bytes(n, 8), dtype=torch.uint8, device=DEV)
+        call = lambda ok: engine.verify_single_rlc_dev(*args, ok, ws, window_bits=8)
+    ok = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        twice = ok.to(torch.int32) * 2  # (a node of its own: the capture is not empty)
+        with pytest.raises(_lib.DsvError):
+            call(ok)
+    del g, twice  # ended, never replayed
+    torch.cuda.synchronize()
+    assert (ok.cpu().numpy() == 7).all()
+    # the same call outside a capture works (mixed: automatic window bits, below the aggregate's threshold)
+    accepted = call(ok)
+    torch.cuda.synchronize()
+    assert (ok.cpu().numpy() == 1).all()
+    assert accepted is (form != "mixed")

@@ -35,7 +35,7 @@ def test_plan_invariants(scheme):
             assert side % p["nseg"] == 0 and (side // 2) % p["nseg2"] == 0
             assert side // p["nseg"] <= 16 or p["nseg"] == 1 and side <= 16
             assert side // 2 // p["nseg2"] <= 16 or p["nseg2"] == 1
-            # scratch areas hold every stage that writes them (k_rlc.hip: launch_rlc)
+            # scratch areas hold every stage that writes them (k_rlc.hip: launch_rlc_finish)
             lanes = p["windows"] * c
             assert p["tmp0"] >= max(p["windows"] * 2 * side * p["nseg"], p["windows"] * 2 * p["half"] * p["nseg2"], lanes + 1)
             assert p["tmp1"] >= max(p["windows"] * 2 * side, lanes)
