@@ -568,6 +568,43 @@ int dsv_verify_double_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_
                             const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
 int dsv_verify_vargen_keyed(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv,
                             const uint32_t *key_idx, const uint8_t *m, size_t n, uint8_t *ok);
+/* ---- keyed wire form: serialized signatures against a registered key set -----------
+ * The signatures arrive as the reference's `Signature::to_bytes()` records — sig64 = u || R (single,
+ * var-generator), sig96 = u || R || R' (double), nonce points compressed — and the key by its index in `ks`.
+ * One decode launch (u copied out, the nonce points decompressed, one validity byte per item), then the
+ * challenge hash and the keyed kernel: three launches, one stream.
+ *   Verdicts    ok[i] = 1 iff `Signature*::from_bytes(sig_i)` would succeed, key_idx[i] is in range, the key
+ *               is valid and `verify` returns true: ok[i] equals dsv_verify_*_keyed_dev's verdict on
+ *               (u_i, decompress(R_i)[, decompress(R'_i)], key_idx[i], m_i) AND-ed with the decode flags of the
+ *               item's nonce points (dsv_decompress_points_dev's: v < q, u^2 d == n, root by the sign bit, no
+ *               further canonicity or subgroup test).  For a set whose keys are all valid this is also
+ *               dsv_verify_*_wire's verdict on (sig_i, to_bytes(key[key_idx[i]]), m_i).
+ *   Arguments   everything the keyed _dev calls promise: a short workspace, a scheme mismatch, a key set of
+ *               another device (the owner of `ok`), a NULL pointer with n > 0: DSV_ERR_INVALID_ARGUMENT and
+ *               nothing launched; a dead set: DSV_ERR_NOT_INITIALIZED; n = 0: DSV_OK; an index >= k gives 0
+ *               and reads no table.  In addition `sig` must be 16-byte aligned (DSV_ERR_INVALID_ARGUMENT).
+ *   Enqueue-only the _dev calls never synchronise and order on `stream`.
+ *   Workspace   workspace_bytes >= dsv_keyed_wire_workspace_bytes(scheme, n) (device, 256-byte aligned) =
+ *               the decoded columns u (32 B), R (64 B)[, R' (64 B)] and the decode flags (1 B per item), then
+ *               dsv_keyed_workspace_bytes(n); each part rounded up to 256 B; never smaller for a larger n; no
+ *               GPU needed; 0 for an unknown scheme.
+ *   Host forms  take host arrays (pageable or pinned) and run on the key set's device through the chunked
+ *               host pipeline of the other host entry points (copy and compute overlap; dsv_set_host_threads
+ *               and the two-calls-in-flight rule apply); they block, and a set cannot be destroyed or shut
+ *               down under a running call. */
+size_t dsv_keyed_wire_workspace_bytes(int scheme, size_t n);
+int dsv_verify_single_keyed_wire_dev(const dsv_keyset *ks, const void *sig64, const void *key_idx, const void *m,
+                                     size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream);
+int dsv_verify_double_keyed_wire_dev(const dsv_keyset *ks, const void *sig96, const void *key_idx, const void *m,
+                                     size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream);
+int dsv_verify_vargen_keyed_wire_dev(const dsv_keyset *ks, const void *sig64, const void *key_idx, const void *m,
+                                     size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream);
+int dsv_verify_single_keyed_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint32_t *key_idx,
+                                 const uint8_t *m, size_t n, uint8_t *ok);
+int dsv_verify_double_keyed_wire(const dsv_keyset *ks, const uint8_t *sig96, const uint32_t *key_idx,
+                                 const uint8_t *m, size_t n, uint8_t *ok);
+int dsv_verify_vargen_keyed_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint32_t *key_idx,
+                                 const uint8_t *m, size_t n, uint8_t *ok);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

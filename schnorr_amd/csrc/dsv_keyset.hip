@@ -191,10 +191,10 @@ int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx) {
     return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
   return DSV_OK;
 }
-int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, size_t n,
                     const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
                     size_t (*need)(size_t n, size_t k, int window_bits)) {
-  if (keyed_any_null(in) || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (inputs_null || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   if (int r = check_rlc_bits(window_bits)) return r;
   const size_t bytes = need(n, ks->k, window_bits);
   if (workspace_bytes < bytes)
@@ -208,9 +208,9 @@ int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, c
 std::shared_mutex& keyset_mutex() { return g_ks_mu; }
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
 void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,
-                   uint8_t* ok, void* workspace, hipStream_t s) {
+                   uint8_t* ok, void* workspace, hipStream_t s, const uint8_t* valid_in) {
   const Workspace w = carve(workspace, n);
-  launch_hash(in, n, w.c, w.valid, s);
+  launch_hash(in, n, w.c, w.valid, s, valid_in);
   launch_verify_keyed(ks->scheme, in.u, w.c, w.valid, in.R(), in.Rp(), idx, n, ks->tables, ks->key_ok, ks->k,
                       ctx.table[0], ctx.table[1], ok, s);
 }

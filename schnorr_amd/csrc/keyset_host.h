@@ -4,7 +4,7 @@
 #include <shared_mutex>
 
 #include "dsv_host.h"
-#include "keyed.h"
+#include "keyed_wire.h"
 
 struct dsv_keyset {
   int scheme = 0;
@@ -30,11 +30,35 @@ int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx);
 // (shared lock held, check_set passed, n > 0) the rest of a keyed _dev call's checks, in this order: null
 // pointers, the window bits (0 for the per-signature form), workspace_bytes >= need(n, ks->k, window_bits), `ok`
 // on the set's device (ctx: the set's context)
-int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
+// inputs_null: one of the call's input pointers other than idx is null (affine items: keyed_any_null; the wire
+// form: the records or m)
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, size_t n,
                     const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
                     size_t (*need)(size_t n, size_t k, int window_bits));
+inline int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
+                           const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
+                           size_t (*need)(size_t n, size_t k, int window_bits)) {
+  return check_keyed_dev(ks, ctx, keyed_any_null(in), idx, n, ok, workspace, workspace_bytes, window_bits, need);
+}
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
+// valid_in (may be null): per-item bytes of an earlier stage (the wire form's decoder), AND-ed in by the hash
 void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,
-                   uint8_t* ok, void* workspace, hipStream_t s);
+                   uint8_t* ok, void* workspace, hipStream_t s, const uint8_t* valid_in = nullptr);
+
+// ---- the keyed wire form (dsv_keyed_wire.hip, keyed_wire.h) -----------------------------------------------
+// the decoder's outputs for n records, in this order (dsv_keyed_wire_workspace_bytes): u, R, R' (double scheme
+// only), valid; each part rounded up to 256 B
+inline size_t keyed_wire_cols_bytes(int scheme, size_t n) {
+  return align_up(n * 32, 256) + (size_t)keyed_wire_points(scheme) * align_up(n * 64, 256) + align_up(n, 256);
+}
+struct KeyedWireCols {
+  uint8_t *u, *R, *Rp, *valid;
+  Items items(int scheme, const void* m) const { return make_items(scheme, u, {R, Rp}, m); }
+};
+KeyedWireCols carve_keyed_wire(Stager& x, int scheme, size_t n);
+// n signature records (device memory, 16-byte aligned) -> out.u, out.R() [, out.Rp()] and valid, one launch on
+// `stream`; a step of its own so that it can stand in front of the keyed fast accept as well
+void decode_keyed_wire(const Context& ctx, int scheme, const uint8_t* sig, size_t n, const Items& out, uint8_t* valid,
+                       hipStream_t stream);
 
 }  // namespace dsvh

@@ -880,6 +880,13 @@ def keyed_workspace_bytes(n):
     return int(_lib.load().dsv_keyed_workspace_bytes(ctypes.c_size_t(n)))
 
 
+def keyed_wire_workspace_bytes(scheme, n):
+    """dsv_keyed_wire_workspace_bytes: device bytes of KeySet.verify_wire_dev's workspace (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyed_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+
+
 def keyed_rlc_workspace_bytes(n, k, window_bits=0):
     """dsv_keyed_rlc_workspace_bytes: device bytes of KeySet.verify_rlc_dev's workspace for n items over k keys"""
     b = int(_lib.load().dsv_keyed_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_size_t(k), ctypes.c_int(window_bits)))
@@ -908,6 +915,8 @@ class KeySet:
         ks = KeySet.from_wire("vargen", pk64)      # the reference's key records, [k, 32] or [k, 64]
         ok = ks.verify(u, R, idx, m)               # double: ks.verify(u, R, Rp, idx, m); idx: uint32 [n]
         ks.verify_dev(u, R, idx, m, ok, workspace) # CUDA tensors; idx int32 [n], read as uint32
+        ok = ks.verify_wire(sig, idx, m)           # sig: the reference's signature records, [n, 64] or [n, 96]
+        ks.verify_wire_dev(sig, idx, m, ok, workspace)
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None):
@@ -1034,3 +1043,31 @@ class KeySet:
             self._handle(), *ins, ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
             _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
         return bool(box.value) if box is not None else None
+
+    def verify_wire(self, sig, idx, m):
+        """Serialized signatures (dsv_verify_*_keyed_wire): host arrays sig [n, 64] (double: [n, 96]), idx
+        uint32 [n], m [n, 32] -> verdicts [n], through the chunked host pipeline on the set's device."""
+        sig, m = _arr(sig, _SCHEMES[self.scheme][1][0]), _arr(m, 32)
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        n = _same_n(sig, m)
+        if idx.shape[0] != n:
+            raise ValueError("idx has %d entries, the batch %d items" % (idx.shape[0], n))
+        ok = np.zeros(n, dtype=np.uint8)
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_wire" % self.scheme)(
+            self._handle(), _p(sig), _p(idx), _p(m), ctypes.c_size_t(n), _p(ok)))
+        return ok
+
+    def verify_wire_dev(self, sig, idx, m, ok, workspace, stream=None):
+        """Serialized signatures in device memory (dsv_verify_*_keyed_wire_dev): CUDA tensors sig [n, 64]
+        (double: [n, 96]), idx int32 [n] (read as uint32), m [n, 32]; verdicts into ok, enqueued on `stream`
+        (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
+        keyed_wire_workspace_bytes(scheme, n) bytes."""
+        n, dev = _rows((sig, _SCHEMES[self.scheme][1][0], "sig"), (m, 32, "m"))
+        ip = _idx(idx, n, dev, "idx")
+        if idx.dim() != 1 or idx.shape[0] != n:
+            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_wire_workspace_bytes(self.scheme, n), dev, "workspace")
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_wire_dev" % self.scheme)(
+            self._handle(), _tp(sig, _SCHEMES[self.scheme][1][0]), ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))

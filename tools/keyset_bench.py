@@ -4,6 +4,7 @@
     python tools/keyset_bench.py --one SCHEME K [--reps R]      # one measurement (what the driver runs)
     python tools/keyset_bench.py --rlc [--out FILE] [--log2-ns 18,20] [--ks ...] [--workloads valid,wrong_h8,wrong_h0]
     python tools/keyset_bench.py --soak 10000000 [--out FILE]   # keyed fast accept against the keyed per-signature path
+    python tools/keyset_bench.py --wire [--out FILE] [--log2-ns 20,14] [--ks 1,64,4096]   # the keyed wire form
 
 Each (scheme, k) is measured in a process of its own: n items signed under k keys, inputs in HBM, then
 dsv_verify_<scheme>_keyed_dev and dsv_verify_<scheme>_dev on the gathered keys alternate on one stream,
@@ -16,6 +17,12 @@ and the unkeyed fast accept (verify_*_rlc_dev on the gathered keys), on identica
 three workloads: all valid; one wrong item with the history counters at 8 (a caller whose batches fail now and
 then: sub-groups); one wrong item with the counters at 0 (the first wrong batch after a run of valid ones).
 The counters are set before every timed call; all three paths must return the same verdict vector.
+--wire: serialized signatures against a key set (KeySet.verify_wire_dev), per (scheme, k, n) in one process on
+identical seeded inputs, the paths alternating, each call timed with device events: (a) the keyed wire call,
+(b) the keyed call on the pre-decoded columns, (c) dsv_decompress_points_dev alone on the batch's nonce points,
+(d) the unkeyed wire call with the gathered key records; (a) must equal (b) AND the decode flags, and (d).  At
+k = 64 and the largest n the host forms follow, on pageable arrays, wall-clock: the keyed wire host call, the
+keyed host call on decoded columns, the unkeyed wire host call.  Medians with the min - max spread beside them.
 --soak: calls of 2^20 items (a fresh set of wrong items, none to many, and forced sub-groups per call) through
 both keyed paths; reports how many verdicts differ.
 """
@@ -232,6 +239,111 @@ def measure_rlc(scheme, k, log2_n, reps, workload, warmup=2, bits=0):
     return out
 
 
+def _stats(v):
+    v = sorted(v)
+    return {"median_ms": round(v[len(v) // 2], 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4)}
+
+
+def measure_wire(scheme, k, log2_n, reps, host, warmup=3, host_reps=7):
+    """the keyed wire form against the paths a caller has without it (module docstring: --wire)"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    dev = "cuda:0"
+    n = 1 << log2_n
+    P0, P1, idx, u, R, Rp, m = _signed_batch(E, scheme, k, n, 8765 + k)
+    u[::16, 0] ^= 1  # some false verdicts
+    nonce = [R] + ([Rp] if Rp is not None else [])
+    sig = np.ascontiguousarray(np.concatenate([u] + [E.compress_points(p) for p in nonce], axis=1))
+    rec = E.compress_points(P0) if P1 is None else np.hstack([E.compress_points(P0), E.compress_points(P1)])
+    pk = np.ascontiguousarray(rec[idx])
+    sig[7::4096, 32 + 31] = 0x7F  # a few undecodable nonce points (v >= q)
+    sb = sig.shape[1]
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dsig, dpk, dm, di = T(sig), T(pk), T(m), T(idx.view(np.int32))
+    ks = E.KeySet(scheme, P0, P1)
+    ok = {p: torch.empty(n, dtype=torch.uint8, device=dev) for p in "abcd"}
+    cols = [torch.empty((n, 64), dtype=torch.uint8, device=dev) for _ in nonce]
+    du = dsig[:, :32].contiguous()
+    ws_a = torch.empty(E.keyed_wire_workspace_bytes(scheme, n), dtype=torch.uint8, device=dev)
+    ws_b = torch.empty(E.keyed_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws_d = torch.empty(E.wire_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    flat = dsig.reshape(-1)
+
+    def a():
+        ks.verify_wire_dev(dsig, di, dm, ok["a"], ws_a)
+
+    def c():
+        for j, out in enumerate(cols):
+            E.decompress_points_dev(flat[32 + 32 * j:], out, ok["c"], in_stride=sb, accumulate=j > 0)
+
+    def b():
+        ks.verify_dev(du, *cols, di, dm, ok["b"], ws_b)
+
+    def d():
+        getattr(E, "verify_%s_wire_dev" % scheme)(dsig, dpk, dm, ok["d"], ws_d)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    fns = {"a": a, "c": c, "b": b, "d": d}  # (c before b: b reads the columns c wrote)
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    t = {p: [] for p in fns}
+    for _ in range(reps):
+        for p, f in fns.items():
+            t[p].append(timed(f))
+    torch.cuda.synchronize()
+    v = {p: o.cpu().numpy() for p, o in ok.items()}
+    assert (v["a"] == (v["b"] & v["c"])).all(), "keyed wire differs from the composed path at %d items" % int((v["a"] != (v["b"] & v["c"])).sum())
+    assert (v["a"] == v["d"]).all(), "keyed wire differs from the unkeyed wire call at %d items" % int((v["a"] != v["d"]).sum())
+    assert (v["c"] == 0).sum() == len(range(7, n, 4096)) and 0.9 < v["a"].mean() < 0.95, v["a"].mean()
+    names = {"a": "keyed_wire_dev", "b": "keyed_dev_predecoded", "c": "decompress_dev", "d": "wire_dev"}
+    out = {"scheme": scheme, "k": k, "n": n, "reps": reps, "verdicts_equal": True}
+    for p in "abcd":
+        out[names[p]] = _stats(t[p])
+    med = lambda p: out[names[p]]["median_ms"]
+    out["a_minus_b_minus_c_ms"] = round(med("a") - med("b") - med("c"), 4)
+    out["a_spread_ms"] = round(out[names["a"]]["max_ms"] - out[names["a"]]["min_ms"], 4)
+    out["relation_a_le_b_plus_c_holds"] = bool(out["a_minus_b_minus_c_ms"] <= out["a_spread_ms"])
+    out["wire_dev_over_keyed_wire_dev"] = round(med("d") / med("a"), 3)
+    out["keyed_wire_dev_Mverdicts_s"] = round(n / med("a") / 1e3, 2)
+    if host:
+        uv = [o.cpu().numpy() for o in cols]
+        want = v["a"]
+        uh = np.ascontiguousarray(sig[:, :32])
+        paths = {"keyed_wire_host": lambda: ks.verify_wire(sig, idx, m),
+                 "keyed_host_predecoded": lambda: ks.verify(uh, *uv, idx, m) & v["c"],
+                 "wire_host": lambda: getattr(E, "verify_%s_wire" % scheme)(sig, pk, m)}
+        th = {p: [] for p in paths}
+        for p, f in paths.items():
+            assert (f() == want).all(), p  # (warm-up)
+        for _ in range(host_reps):
+            for p, f in paths.items():
+                t0 = time.perf_counter()
+                got = f()
+                th[p].append((time.perf_counter() - t0) * 1e3)
+                assert (got == want).all(), p
+        for p in paths:
+            out[p] = _stats(th[p])
+            out[p]["Mverdicts_s"] = round(n / out[p]["median_ms"] / 1e3, 2)
+        out["host_reps"] = host_reps
+        out["keyed_wire_host_over_dev_rate"] = round(med("a") / out["keyed_wire_host"]["median_ms"], 3)
+    ks.close()
+    return out
+
+
 def soak(total, log2_n=20, k=64, seed=99):
     """keyed fast accept vs keyed per-signature verdicts over `total` verdicts, all three schemes in turn"""
     import numpy as np
@@ -287,6 +399,8 @@ def main():
     ap.add_argument("--log2-ns", default="18,20")
     ap.add_argument("--workloads", default="valid,wrong_h8,wrong_h0")
     ap.add_argument("--soak", type=int)
+    ap.add_argument("--wire", action="store_true")
+    ap.add_argument("--one-wire", nargs=4, metavar=("SCHEME", "K", "LOG2N", "HOST"))
     ap.add_argument("--bits", type=int, default=0)
     a = ap.parse_args()
     if a.soak:
@@ -295,6 +409,32 @@ def main():
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(row, f, indent=1)
+        return
+    if a.one_wire:
+        s, k, l2, host = a.one_wire
+        print(json.dumps(measure_wire(s, int(k), int(l2), a.reps, host == "1")), flush=True)
+        return
+    if a.wire:
+        rows = []
+        ks = [int(x) for x in (a.ks if a.ks != "1,64,4096,16384" else "1,64,4096").split(",")]
+        l2s = [int(x) for x in (a.log2_ns if a.log2_ns != "18,20" else "20,14").split(",")]
+        for scheme in a.schemes.split(","):
+            for l2 in l2s:
+                for k in ks:
+                    host = "1" if (k == 64 and l2 == max(l2s)) else "0"
+                    cmd = [sys.executable, os.path.abspath(__file__), "--one-wire", scheme, str(k), str(l2), host,
+                           "--reps", str(a.reps)]
+                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+                    if p.returncode != 0:
+                        sys.stderr.write(p.stdout + p.stderr)
+                        raise SystemExit("measurement %s k=%d 2^%d failed with status %d" % (scheme, k, l2, p.returncode))
+                    row = json.loads(p.stdout.strip().splitlines()[-1])
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+                    if a.out:
+                        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                        with open(a.out, "w") as f:
+                            json.dump({"reps": a.reps, "rows": rows}, f, indent=1)
         return
     if a.one_rlc:
         s, k, l2, w = a.one_rlc
