@@ -605,6 +605,51 @@ int dsv_verify_double_keyed_wire(const dsv_keyset *ks, const uint8_t *sig96, con
                                  const uint8_t *m, size_t n, uint8_t *ok);
 int dsv_verify_vargen_keyed_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint32_t *key_idx,
                                  const uint8_t *m, size_t n, uint8_t *ok);
+/* ---- keyed typed-object form: the reference's in-memory objects against a registered key set --
+ * Keys are registered from `PublicKey*` objects where they lie, `Signature*` objects are verified where they lie
+ * by key index: Montgomery limbs and projective points as described under "the reference's IN-MEMORY
+ * representation" above (scalar 32 B; point 96 B = limbs of u || v || z of the JubJubExtended, t1 / t2 never
+ * read).  The key set carries its scheme, so there is one entry point per form.  No kernel of its own: the
+ * normalisation launch of the *_mont forms over the nonce points alone (it converts u and m as well), then the
+ * challenge hash and the keyed kernel — three launches, one stream; in the constructor the same normalisation
+ * over the key points in front of the table build.
+ *   create_mont_cols  cols[0] = PK, cols[1] = PK' (double) / Gen (var-generator): key j's point at base + j *
+ *               stride, stride >= 96 (sizeof of the key object).  A key is valid iff every limb group is < q,
+ *               z != 0 and the normalised point is on the curve (dsv_keyset_key_ok).  The set is the one
+ *               dsv_keyset_create builds from the normalised keys: same key_ok, same table entries.  Runs on
+ *               the current device (it must be initialised) and blocks, like the other constructors.
+ *   Columns     verify: single / var-generator u, R, key_idx, m [4]; double u, R, R', key_idx, m [5]; widths 32,
+ *               96, (96), 4, 32; item i at base + i * stride, stride >= width; key_idx (uint32) 4-byte aligned,
+ *               its stride a multiple of 4.  A violation: DSV_ERR_INVALID_ARGUMENT, "column k: ...".
+ *   Verdicts    ok[i] equals dsv_verify_*_mont's verdict on (u_i, R_i[, R'_i], key[key_idx[i]], m_i) for every
+ *               input the Rust types can hold, and dsv_verify_*_keyed_dev's on the `to_bytes()` /
+ *               `to_hash_inputs()` of the same values.  Limbs not below their modulus, z = 0, an index >= k or
+ *               an invalid key give 0; an index >= k reads no table.
+ *   _dev form   everything the keyed _dev calls promise: a short workspace, a key set of another device (the
+ *               owner of `ok`), a NULL pointer with n > 0: DSV_ERR_INVALID_ARGUMENT, nothing launched, `ok`
+ *               untouched; a dead set: DSV_ERR_NOT_INITIALIZED; n = 0: DSV_OK.  Rp_uvz is required for a double
+ *               set and ignored otherwise.  Enqueue-only, ordered on `stream`, may be captured.
+ *   Workspace   workspace_bytes >= dsv_keyed_mont_workspace_bytes(scheme, n) (device, 256-byte aligned) = the
+ *               normalised columns u (32 B), m (32 B), R (64 B)[, R' (64 B)], the validity bytes (1 B per item),
+ *               the normalisation's prefix products (points * (n + 32) * 36 B), then
+ *               dsv_keyed_workspace_bytes(n); each part rounded up to 256 B; never smaller for a larger n; no GPU
+ *               needed; 0 for an unknown scheme.
+ *   Host form   reads the objects where they lie and runs on the key set's device through the chunked host
+ *               pipeline (one normalisation launch per chunk, hash + keyed kernel per sub-batch; copy and compute
+ *               overlap; dsv_set_host_threads and the two-calls-in-flight rule apply); blocks; a set cannot be
+ *               destroyed or shut down under a running call.
+ *   Submit      as dsv_verify_*_mont_cols_submit: returns at once with a dsv_job for dsv_job_wait / dsv_job_done;
+ *               cols[] is copied, the objects and `ok` must stay valid until the wait returns.  The job holds the
+ *               set from before submit returns: dsv_keyset_destroy and dsv_shutdown* wait for it.  A job whose
+ *               set died before it ran reports DSV_ERR_NOT_INITIALIZED at its wait. */
+int dsv_keyset_create_mont_cols(int scheme, const dsv_column *cols /*[1|2]*/, size_t k, dsv_keyset **out);
+size_t dsv_keyed_mont_workspace_bytes(int scheme, size_t n);
+int dsv_verify_keyed_mont_dev(const dsv_keyset *ks, const void *u, const void *R_uvz,
+                              const void *Rp_uvz /* double only, else NULL */, const void *key_idx, const void *m,
+                              size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream);
+int dsv_verify_keyed_mont_cols(const dsv_keyset *ks, const dsv_column *cols /*[4|5]*/, size_t n, uint8_t *ok);
+int dsv_verify_keyed_mont_cols_submit(const dsv_keyset *ks, const dsv_column *cols /*[4|5]*/, size_t n, uint8_t *ok,
+                                      dsv_job **job);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

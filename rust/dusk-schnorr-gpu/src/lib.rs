@@ -72,6 +72,15 @@ extern "C" {
     fn dsv_verify_single_mont_cols_rlc(cols: *const Column, n: usize, ok: *mut u8, accepted: *mut c_int) -> c_int;
     fn dsv_verify_double_mont_cols_rlc(cols: *const Column, n: usize, ok: *mut u8, accepted: *mut c_int) -> c_int;
     fn dsv_verify_vargen_mont_cols_rlc(cols: *const Column, n: usize, ok: *mut u8, accepted: *mut c_int) -> c_int;
+    // registered key sets over the typed objects (include/dsv.h, "keyed typed-object form"): keys cols[0] = PK,
+    // cols[1] = PK' / Gen (96 B read per point); items: single / var-generator u, R, key_idx, m | double u, R, R',
+    // key_idx, m (widths 32, 96, (96), 4, 32).  The set carries its scheme.
+    fn dsv_keyset_create_mont_cols(scheme: c_int, cols: *const Column, k: usize, out: *mut *mut c_void) -> c_int;
+    fn dsv_keyset_destroy(ks: *mut c_void) -> c_int;
+    fn dsv_keyset_key_ok(ks: *const c_void, out: *mut u8) -> c_int;
+    fn dsv_verify_keyed_mont_cols(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8) -> c_int;
+    fn dsv_verify_keyed_mont_cols_submit(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8,
+                                         job: *mut *mut c_void) -> c_int;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.
@@ -398,6 +407,133 @@ pub unsafe fn verify_batch_var_gen_submit<'a>(sigs: &'a [SignatureVarGen], pks: 
     }
 }
 
+// ---- registered key sets (never compiled here, like the rest of this crate) -------------------------------
+/// Keys registered once, signatures verified by key index: `out[i] == keys[idx[i]].verify(&sigs[i], msgs[i])`,
+/// `false` for an index out of range or an invalid key.  The engine reads the key objects where they lie while
+/// the set is built and the signature objects where they lie in every call (164 B per single item on the bus
+/// against 256, about a third of the arithmetic).  Owns device memory on the GPU that was current at creation;
+/// immutable, `Sync`; dropping it waits for the jobs submitted on it.  Needs the in-memory layout `layout_ok()`
+/// checks (there is no accessor-copy path for key sets: creation fails with `EngineError(-2, ..)` instead).
+pub struct KeySet<K> {
+    ks: *mut c_void,
+    k: usize,
+    _keys: core::marker::PhantomData<K>,
+}
+unsafe impl<K> Send for KeySet<K> {}
+unsafe impl<K> Sync for KeySet<K> {}
+impl<K> Drop for KeySet<K> {
+    fn drop(&mut self) {
+        unsafe { dsv_keyset_destroy(self.ks) };
+    }
+}
+impl<K> KeySet<K> {
+    fn create(scheme: c_int, cols: &[Column], k: usize) -> Result<Self, EngineError> {
+        init_all()?;
+        if !layout_ok() {
+            return Err(EngineError(-2, "dusk-jubjub's in-memory layout is not the one key sets read".into()));
+        }
+        let mut ks = core::ptr::null_mut();
+        check(unsafe { dsv_keyset_create_mont_cols(scheme, cols.as_ptr(), k, &mut ks) })?;
+        Ok(KeySet { ks, k, _keys: core::marker::PhantomData })
+    }
+    pub fn len(&self) -> usize {
+        self.k
+    }
+    /// per key: usable (every coordinate a value of the type, z != 0, the point on the curve)
+    pub fn key_ok(&self) -> Result<Vec<bool>, EngineError> {
+        let mut ok = vec![0u8; self.k];
+        check(unsafe { dsv_keyset_key_ok(self.ks, ok.as_mut_ptr()) })?;
+        Ok(verdicts(ok))
+    }
+    fn run(&self, cols: &[Column], n: usize) -> Result<Vec<bool>, EngineError> {
+        let mut ok = vec![0u8; n];
+        if n != 0 {
+            check(unsafe { dsv_verify_keyed_mont_cols(self.ks, cols.as_ptr(), n, ok.as_mut_ptr()) })?;
+        }
+        Ok(verdicts(ok))
+    }
+    unsafe fn start<'a>(&'a self, cols: &[Column], n: usize) -> Result<BatchJob<'a>, EngineError> {
+        let mut j = BatchJob { job: core::ptr::null_mut(), ok: vec![0u8; n], _soa: None, _borrow: core::marker::PhantomData };
+        if n != 0 {
+            check(dsv_verify_keyed_mont_cols_submit(self.ks, cols.as_ptr(), n, j.ok.as_mut_ptr(), &mut j.job))?;
+        }
+        Ok(j)
+    }
+}
+fn idx_col(idx: &[u32]) -> Column {
+    Column { base: idx.as_ptr() as *const c_void, stride: 4 }
+}
+impl KeySet<PublicKey> {
+    pub fn new(keys: &[PublicKey]) -> Result<Self, EngineError> {
+        let cols = if keys.is_empty() { vec![] } else { vec![col(keys[0].as_ref(), keys)] };
+        Self::create(0, &cols, keys.len())
+    }
+    pub fn verify_batch(&self, sigs: &[Signature], idx: &[u32], msgs: &[BlsScalar]) -> Result<Vec<bool>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok(Vec::new());
+        }
+        self.run(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), idx_col(idx), col(&msgs[0], msgs)], sigs.len())
+    }
+    /// # Safety
+    /// As for [`verify_batch_submit`]: the job must be waited for or dropped, never leaked.
+    pub unsafe fn verify_batch_submit<'a>(&'a self, sigs: &'a [Signature], idx: &'a [u32], msgs: &'a [BlsScalar])
+        -> Result<BatchJob<'a>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return self.start(&[], 0);
+        }
+        self.start(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), idx_col(idx), col(&msgs[0], msgs)], sigs.len())
+    }
+}
+impl KeySet<PublicKeyDouble> {
+    pub fn new(keys: &[PublicKeyDouble]) -> Result<Self, EngineError> {
+        let cols = if keys.is_empty() { vec![] } else { vec![col(keys[0].pk(), keys), col(keys[0].pk_prime(), keys)] };
+        Self::create(1, &cols, keys.len())
+    }
+    pub fn verify_batch(&self, sigs: &[SignatureDouble], idx: &[u32], msgs: &[BlsScalar]) -> Result<Vec<bool>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok(Vec::new());
+        }
+        self.run(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(sigs[0].R_prime(), sigs), idx_col(idx),
+                   col(&msgs[0], msgs)], sigs.len())
+    }
+    /// # Safety
+    /// As for [`verify_batch_submit`].
+    pub unsafe fn verify_batch_submit<'a>(&'a self, sigs: &'a [SignatureDouble], idx: &'a [u32], msgs: &'a [BlsScalar])
+        -> Result<BatchJob<'a>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return self.start(&[], 0);
+        }
+        self.start(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(sigs[0].R_prime(), sigs), idx_col(idx),
+                     col(&msgs[0], msgs)], sigs.len())
+    }
+}
+impl KeySet<PublicKeyVarGen> {
+    pub fn new(keys: &[PublicKeyVarGen]) -> Result<Self, EngineError> {
+        let cols = if keys.is_empty() { vec![] } else { vec![col(keys[0].public_key(), keys), col(keys[0].generator(), keys)] };
+        Self::create(2, &cols, keys.len())
+    }
+    pub fn verify_batch(&self, sigs: &[SignatureVarGen], idx: &[u32], msgs: &[BlsScalar]) -> Result<Vec<bool>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok(Vec::new());
+        }
+        self.run(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), idx_col(idx), col(&msgs[0], msgs)], sigs.len())
+    }
+    /// # Safety
+    /// As for [`verify_batch_submit`].
+    pub unsafe fn verify_batch_submit<'a>(&'a self, sigs: &'a [SignatureVarGen], idx: &'a [u32], msgs: &'a [BlsScalar])
+        -> Result<BatchJob<'a>, EngineError> {
+        assert!(sigs.len() == idx.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return self.start(&[], 0);
+        }
+        self.start(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), idx_col(idx), col(&msgs[0], msgs)], sigs.len())
+    }
+}
 
 /// Batches in flight behind a SAFE interface: every job started through the scope is joined before
 /// `batch_scope` returns (also when the closure panics), so leaking a ticket leaks nothing the engine

@@ -64,12 +64,15 @@ SYMBOLS = [
     "dsv_keyed_wire_workspace_bytes", "dsv_verify_single_keyed_wire_dev", "dsv_verify_double_keyed_wire_dev",
     "dsv_verify_vargen_keyed_wire_dev", "dsv_verify_single_keyed_wire", "dsv_verify_double_keyed_wire",
     "dsv_verify_vargen_keyed_wire",
+    # keyed typed-object form: the reference's in-memory objects against a registered key set
+    "dsv_keyset_create_mont_cols", "dsv_keyed_mont_workspace_bytes", "dsv_verify_keyed_mont_dev",
+    "dsv_verify_keyed_mont_cols", "dsv_verify_keyed_mont_cols_submit",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
                  "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes",
                  "dsv_keyset_bytes", "dsv_keyed_workspace_bytes", "dsv_keyed_rlc_workspace_bytes",
-                 "dsv_keyed_wire_workspace_bytes")
+                 "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes")
 
 
 class Column(ctypes.Structure):
@@ -114,6 +117,7 @@ def load():
         getattr(L, name).argtypes = [ctypes.c_size_t] + ([ctypes.c_int] if name in ("dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes") else [])
     L.dsv_keyset_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_keyed_wire_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.dsv_keyed_mont_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_keyed_rlc_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported

@@ -4,6 +4,7 @@
 // binds), their *_multi forms over all initialised devices, and the submit / wait form.  All of them
 // run the chunked pipeline of dsv_pipeline.h.
 #include "dsv_pipeline.h"
+#include "keyed_mont.h"
 
 namespace dsvh {
 std::atomic<int> g_host_threads{0};
@@ -249,23 +250,27 @@ struct dsv_job {
   int rc = DSV_OK;
   std::string err;
   int kind = 0;
+  const dsv_keyset* ks = nullptr;  // the keyed typed-object form (keyed_mont.h); null: the unkeyed one of `kind`
+  int ncols = 0;
   dsv_column cols[6] = {};
   size_t n = 0;
   uint8_t* ok = nullptr;
 };
-namespace {
-int submit_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, dsv_job** out) {
-  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null job pointer");
-  *out = nullptr;
-  if (int r = check_cols(kind, cols, n, ok, kMont)) return r;
+extern "C++" {
+namespace dsvh {
+// (arguments checked by the caller)
+int submit_cols_job(const dsv_keyset* ks, int kind, const dsv_column* cols, int ncols, size_t n, uint8_t* ok,
+                    dsv_job** out) {
   if (g_primary.load(std::memory_order_acquire) < 0)
     return fail(DSV_ERR_NOT_INITIALIZED, "dsv_init() has not been called");
   dsv_job* j = new (std::nothrow) dsv_job;
   if (!j) return fail(DSV_ERR_HIP, "out of host memory");
   j->kind = kind;
+  j->ks = ks;
+  j->ncols = ncols;
   j->n = n;
   j->ok = ok;
-  for (int k = 0; n && k < layout(kind).points + 2; k++) j->cols[k] = cols[k];
+  for (int k = 0; k < ncols; k++) j->cols[k] = cols[k];
   auto job_count = [](int d) {
     std::lock_guard<std::mutex> lk(g_jobs_mu);
     g_jobs += d;
@@ -274,6 +279,12 @@ int submit_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, ds
   job_count(+1);
   try {
     j->th = std::thread([j, job_count] {
+      // a keyed job holds the key-set registry's shared lock from before submit returns to its last verdict:
+      // dsv_keyset_destroy and dsv_shutdown* (exclusive) wait for the job instead of freeing the set under it.
+      // Nothing the driver does takes that lock again, and dsv_shutdown_device waits for the jobs before it
+      // asks for the registry, holding no lock a driver needs.
+      std::shared_lock<std::shared_mutex> registry(keyset_mutex(), std::defer_lock);
+      if (j->ks) registry.lock();
       {
         std::lock_guard<std::mutex> lk(j->m);
         j->started = true;
@@ -283,8 +294,10 @@ int submit_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, ds
         const int d = t_device >= 0 ? t_device : g_primary.load(std::memory_order_acquire);
         if (d >= 0 && d < kMaxDevices) (void)pin_this_thread(g_ctx[d].numa_cpus);
       }
-      j->rc = verify_host_cols(j->kind, kMont, j->cols, j->n, j->ok, true);
+      j->rc = j->ks ? verify_keyed_mont_cols_locked(j->ks, j->cols, j->n, j->ok)
+                    : verify_host_cols(j->kind, kMont, j->cols, j->n, j->ok, true);
       if (j->rc) j->err = g_err;  // the text lives in this thread's thread-local
+      if (j->ks) registry.unlock();
       j->finished.store(true, std::memory_order_release);
       job_count(-1);
     });
@@ -302,7 +315,16 @@ int submit_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, ds
   *out = j;
   return DSV_OK;
 }
+}  // namespace dsvh
+namespace {
+int submit_mont_cols(int kind, const dsv_column* cols, size_t n, uint8_t* ok, dsv_job** out) {
+  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null job pointer");
+  *out = nullptr;
+  if (int r = check_cols(kind, cols, n, ok, kMont)) return r;
+  return submit_cols_job(nullptr, kind, cols, n ? layout(kind).points + 2 : 0, n, ok, out);
+}
 }  // namespace
+}  // extern "C++"
 int dsv_verify_single_mont_cols_submit(const dsv_column* cols, size_t n, uint8_t* ok, dsv_job** job) { return submit_mont_cols(0, cols, n, ok, job); }
 int dsv_verify_double_mont_cols_submit(const dsv_column* cols, size_t n, uint8_t* ok, dsv_job** job) { return submit_mont_cols(1, cols, n, ok, job); }
 int dsv_verify_vargen_mont_cols_submit(const dsv_column* cols, size_t n, uint8_t* ok, dsv_job** job) { return submit_mont_cols(2, cols, n, ok, job); }

@@ -37,6 +37,8 @@ int keyset_context(const dsv_keyset* ks, Context*& out) {
   return DSV_OK;
 }
 
+}  // namespace
+
 // tables of k keys from device points P0 / P1 (and the decoder's verdicts valid_in); registers the set
 int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
                        size_t k, hipStream_t s, dsv_keyset** out) {
@@ -81,6 +83,7 @@ int current_context(Context*& out) {
   return DSV_OK;
 }
 
+namespace {
 // device buffers + stream of one create call, released on every path
 struct Scratch {
   uint8_t* dev = nullptr;

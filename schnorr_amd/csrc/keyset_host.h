@@ -40,6 +40,12 @@ inline int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items
                            size_t (*need)(size_t n, size_t k, int window_bits)) {
   return check_keyed_dev(ks, ctx, keyed_any_null(in), idx, n, ok, workspace, workspace_bytes, window_bits, need);
 }
+// the calling thread's current device, which must be initialised: where a constructor builds its set
+int current_context(Context*& out);
+// tables of k keys from device points P0 / P1 (affine, 64 B each; P1 null for the single scheme) and an earlier
+// stage's per-key verdicts valid_in (may be null), built on `s`; blocks, registers the set, *out = its handle
+int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
+                       size_t k, hipStream_t s, dsv_keyset** out);
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
 // valid_in (may be null): per-item bytes of an earlier stage (the wire form's decoder), AND-ed in by the hash
 void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,

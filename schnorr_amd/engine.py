@@ -887,6 +887,52 @@ def keyed_wire_workspace_bytes(scheme, n):
     return int(_lib.load().dsv_keyed_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
 
 
+def keyed_mont_workspace_bytes(scheme, n):
+    """dsv_keyed_mont_workspace_bytes: device bytes of KeySet.verify_mont_dev's workspace (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyed_mont_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+
+
+def _keyed_mont_widths(scheme):
+    """widths of a keyed typed batch's columns: u, R[, R'], key_idx, m"""
+    return [32] + [96] * (2 if scheme == "double" else 1) + [4, 32]
+
+
+def _keyed_columns(cols, widths, what):
+    """(n, dsv_column array, the arrays) of strided uint8 [n, width] views — rows strided by the object size,
+    bytes of a row contiguous; a 4-byte column (key_idx) may also be a uint32 [n] array or strided view.  The
+    arrays are returned so that the caller keeps them alive"""
+    if len(cols) != len(widths):
+        raise ValueError("%s takes %d columns" % (what, len(widths)))
+    held = [np.asarray(c) for c in cols]
+    n = held[0].shape[0]
+    arr = (_lib.Column * len(held))()
+    for k, (c, w) in enumerate(zip(held, widths)):
+        as_u32 = w == 4 and c.dtype == np.uint32 and c.shape == (n,)
+        # an empty array has no rows to lay out, and numpy reports its strides as it pleases (0 in recent versions)
+        as_rows = c.dtype == np.uint8 and c.shape == (n, w) and (n == 0 or w == 1 or c.strides[1] == 1)
+        if not (as_u32 or as_rows) or (n > 1 and c.strides[0] < w):
+            raise ValueError("column %d: expected uint8 [n, %d] rows with contiguous bytes%s, got %s %r / strides %r"
+                             % (k, w, " or uint32 [n]" if w == 4 else "", c.dtype, c.shape, c.strides))
+        arr[k].base = c.ctypes.data
+        arr[k].stride = c.strides[0] if n > 1 else max(c.strides[0], w)
+    return n, arr, held
+
+
+class KeyedMontColsJob(MontColsJob):
+    """A keyed typed batch in flight (dsv_verify_keyed_mont_cols_submit): MontColsJob's interface.  Keeps the
+    key set and the column arrays alive until the wait."""
+
+    def __init__(self, keyset, cols):  # noqa: D107 (does not call the base constructor: another entry point)
+        n, arr, held = _keyed_columns(cols, _keyed_mont_widths(keyset.scheme), "submit_mont_cols")
+        self._cols = (keyset, held)
+        self._ok = np.zeros(n, dtype=np.uint8)
+        self._job = ctypes.c_void_p()
+        _lib.check(_lib.load().dsv_verify_keyed_mont_cols_submit(
+            keyset._handle(), arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
+
+
 def keyed_rlc_workspace_bytes(n, k, window_bits=0):
     """dsv_keyed_rlc_workspace_bytes: device bytes of KeySet.verify_rlc_dev's workspace for n items over k keys"""
     b = int(_lib.load().dsv_keyed_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_size_t(k), ctypes.c_int(window_bits)))
@@ -917,16 +963,24 @@ class KeySet:
         ks.verify_dev(u, R, idx, m, ok, workspace) # CUDA tensors; idx int32 [n], read as uint32
         ok = ks.verify_wire(sig, idx, m)           # sig: the reference's signature records, [n, 64] or [n, 96]
         ks.verify_wire_dev(sig, idx, m, ok, workspace)
+        ks = KeySet.from_mont_cols("double", [pk96, pkp96])   # views into `PublicKey*` objects (limbs of u || v || z)
+        ok = ks.verify_mont_cols([u, R96, idx, m])            # views into `Signature*` objects, where they lie
+        job = ks.submit_mont_cols([u, R96, idx, m]); ok = job.wait()
+        ks.verify_mont_dev(u, R96, idx, m, ok, workspace)     # CUDA tensors of limbs
     """
 
-    def __init__(self, scheme, PK, PK2=None, _wire=None):
+    def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None):
         if scheme not in _SCHEME_CODE:
             raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
         self.scheme = scheme
         self._h = ctypes.c_void_p()
         L = _lib.load()
         code = ctypes.c_int(_SCHEME_CODE[scheme])
-        if _wire is not None:
+        if _mont_cols is not None:
+            k, arr, held = _keyed_columns(_mont_cols, [96] * (1 if scheme == "single" else 2), "from_mont_cols")
+            _lib.check(L.dsv_keyset_create_mont_cols(code, arr, ctypes.c_size_t(k), ctypes.byref(self._h)))
+            del held
+        elif _wire is not None:
             rec = _arr(_wire, 32 if scheme == "single" else 64)
             _lib.check(L.dsv_keyset_create_wire(code, _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(self._h)))
         else:
@@ -945,6 +999,13 @@ class KeySet:
     def from_wire(cls, scheme, pk_bytes):
         """from the reference's key records: PublicKey (32 B) / PublicKeyDouble / PublicKeyVarGen (64 B)"""
         return cls(scheme, None, _wire=pk_bytes)
+
+    @classmethod
+    def from_mont_cols(cls, scheme, cols):
+        """from the reference's key OBJECTS where they lie (dsv_keyset_create_mont_cols): cols = [PK] (single),
+        [PK, PK'] (double) or [PK, Gen] (vargen), each a uint8 [k, 96] view of the Montgomery limbs of u || v || z
+        of a JubJubExtended (rows strided by the object size, bytes of a row contiguous)"""
+        return cls(scheme, None, _mont_cols=list(cols))
 
     def _handle(self):
         if self._h.value is None:
@@ -1071,3 +1132,39 @@ class KeySet:
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_wire_dev" % self.scheme)(
             self._handle(), _tp(sig, _SCHEMES[self.scheme][1][0]), ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
             ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))
+
+    def verify_mont_cols(self, cols):
+        """`Signature*` objects where they lie (dsv_verify_keyed_mont_cols): cols = [u, R, idx, m] (double:
+        [u, R, R', idx, m]), uint8 views [n, 32 | 96 | 4 | 32] of Montgomery limbs with strided rows (idx may be a
+        uint32 [n] array or view) -> verdicts [n], through the chunked host pipeline on the set's device."""
+        n, arr, held = _keyed_columns(cols, _keyed_mont_widths(self.scheme), "verify_mont_cols")
+        ok = np.zeros(n, dtype=np.uint8)
+        _lib.check(_lib.load().dsv_verify_keyed_mont_cols(self._handle(), arr, ctypes.c_size_t(n), _p(ok)))
+        del held
+        return ok
+
+    def submit_mont_cols(self, cols):
+        """Asynchronous verify_mont_cols (dsv_verify_keyed_mont_cols_submit): returns a job at once (`wait()` ->
+        verdicts, `done()`); the set cannot be destroyed or shut down under it."""
+        return KeyedMontColsJob(self, cols)
+
+    def verify_mont_dev(self, *args, stream=None):
+        """Montgomery limbs in device memory (dsv_verify_keyed_mont_dev): CUDA tensors (u [n, 32], R [n, 96]
+        [, Rp [n, 96]], idx int32 [n] read as uint32, m [n, 32], ok, workspace); verdicts into ok, enqueued on
+        `stream` (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
+        keyed_mont_workspace_bytes(scheme, n) bytes."""
+        if len(args) < 2:
+            raise ValueError("verify_mont_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, idx, m = self._pts(args[:-2])
+        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
+        n, dev = _rows(*zip([u] + list(pts) + [m], [32] + [96] * len(pts) + [32], names))
+        ip = _idx(idx, n, dev, "idx")
+        if idx.dim() != 1 or idx.shape[0] != n:
+            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_mont_workspace_bytes(self.scheme, n), dev, "workspace")
+        _lib.check(_lib.load().dsv_verify_keyed_mont_dev(
+            self._handle(), _tp(u, 32), _tp(pts[0], 96), _tp(pts[1], 96) if len(pts) == 2 else ctypes.c_void_p(0),
+            ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
+            _stream_ptr(stream, dev)))

@@ -5,6 +5,8 @@
     python tools/keyset_bench.py --rlc [--out FILE] [--log2-ns 18,20] [--ks ...] [--workloads valid,wrong_h8,wrong_h0]
     python tools/keyset_bench.py --soak 10000000 [--out FILE]   # keyed fast accept against the keyed per-signature path
     python tools/keyset_bench.py --wire [--out FILE] [--log2-ns 20,14] [--ks 1,64,4096]   # the keyed wire form
+    python tools/keyset_bench.py --mont [--out FILE] [--log2-ns 20,14] [--ks 1,64,4096]   # the keyed typed-object form
+    python tools/keyset_bench.py --soak-mont 10000000 [--out FILE]   # typed keyed forms against the affine keyed path
 
 Each (scheme, k) is measured in a process of its own: n items signed under k keys, inputs in HBM, then
 dsv_verify_<scheme>_keyed_dev and dsv_verify_<scheme>_dev on the gathered keys alternate on one stream,
@@ -23,6 +25,17 @@ identical seeded inputs, the paths alternating, each call timed with device even
 (d) the unkeyed wire call with the gathered key records; (a) must equal (b) AND the decode flags, and (d).  At
 k = 64 and the largest n the host forms follow, on pageable arrays, wall-clock: the keyed wire host call, the
 keyed host call on decoded columns, the unkeyed wire host call.  Medians with the min - max spread beside them.
+--mont: the reference's in-memory objects against a key set (KeySet.verify_mont_dev), per (scheme, k, n) in one
+process on identical seeded inputs (a signed block of <= 2^14 items, every point re-represented with a random z,
+converted to Montgomery limbs with Python integers and tiled on the device), the paths alternating, each call
+timed with device events: (a) the keyed typed call, (b) the keyed call on the pre-normalised affine columns,
+(c) the unkeyed typed call (dsv_verify_*_mont_dev) with the keys gathered per item, (d) the unkeyed affine call;
+all four verdict vectors must be equal.  D = a - b is what the typed form costs a keyed call, D0 = c - d what it
+costs an unkeyed one (which normalises 2 / 4 / 3 points where the keyed form normalises 1 / 2 / 1).  At k = 64
+and the largest n the host forms follow on records laid out like the Rust structs in pageable memory,
+wall-clock: the keyed typed call, the unkeyed typed call on the same objects with the keys carried per item,
+two keyed jobs in flight, the blocking affine keyed call on pre-converted arrays; and the constructors
+(dsv_keyset_create_mont_cols against dsv_keyset_create) at k = 64 and 16384.
 --soak: calls of 2^20 items (a fresh set of wrong items, none to many, and forced sub-groups per call) through
 both keyed paths; reports how many verdicts differ.
 """
@@ -344,6 +357,247 @@ def measure_wire(scheme, k, log2_n, reps, host, warmup=3, host_reps=7):
     return out
 
 
+def _mont_block(E, scheme, k, block, seed):
+    """a signed block in both forms: canonical affine columns and Montgomery limbs of the same values with a
+    random z per point (tests/mont_cases.py: Python integers), for the items and for the k keys"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import harness as H
+    import mont_cases as MC
+    import pymodel as M
+
+    P0, P1, idx, u, R, Rp, m = _signed_batch(E, scheme, k, block, seed)
+    rng = np.random.default_rng(seed + 1)
+    limbs = lambda pts: MC.to_limbs_py(H.projective(pts, rng)[0], M.Q)
+    aff = {"u": u, "R": R, "Rp": Rp, "m": m, "P0": P0, "P1": P1}
+    typed = {"u": MC.to_limbs_py(u, M.R_ORDER), "m": MC.to_limbs_py(m, M.Q), "R": limbs(R),
+             "Rp": limbs(Rp) if Rp is not None else None, "P0": limbs(P0), "P1": limbs(P1) if P1 is not None else None}
+    return idx, aff, typed
+
+
+def _records(scheme, typed, keys_of_item, n):
+    """the Rust structs in pageable memory: n signature records, n key records (the keys carried per item, what
+    the unkeyed typed call reads) -> (column views of the signatures, of the per-item keys)"""
+    import numpy as np
+
+    import mont_cases as MC
+
+    pts = [typed["R"]] + ([typed["Rp"]] if scheme == "double" else [])
+    sigs, pks, msgs, views = MC.as_records(scheme, [typed["u"]] + pts + keys_of_item + [typed["m"]])
+    block = len(msgs)
+    times = -(-n // block)
+    if times > 1:
+        sigs, pks, msgs = np.tile(sigs, times)[:n], np.tile(pks, times)[:n], np.tile(msgs, (times, 1))[:n]
+    raw = lambda rec: rec.view(np.uint8).reshape(len(rec), rec.dtype.itemsize)
+    field = lambda rec, path: (lambda off: raw(rec)[:, off:off + 96])(
+        sum(t.fields[f][1] for t, f in path))
+    st, pt = sigs.dtype, pks.dtype
+    sig_views = [raw(sigs)[:, :32], field(sigs, [(st, "R")])] + ([field(sigs, [(st, "R_prime")])] if scheme == "double" else [])
+    key_views = [field(pks, [(pt, nm)]) for nm in pt.names]
+    return sigs, pks, np.ascontiguousarray(msgs), sig_views, key_views
+
+
+def measure_mont(scheme, k, log2_n, reps, host, warmup=3, host_reps=7):
+    """the keyed typed-object form against the paths a caller has without it (module docstring: --mont)"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    dev = "cuda:0"
+    n = 1 << log2_n
+    block = min(n, 1 << 14)
+    idx, aff, typed = _mont_block(E, scheme, k, block, 4321 + k)
+    idx = idx.copy()
+    idx[::16] = (idx[::16] + 1) % k if k > 1 else k  # some false verdicts: another key (one key: out of range)
+    times = n // block
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    tile = lambda a: T(a).repeat(*([times] + [1] * (a.ndim - 1))) if times > 1 else T(a)
+    two = scheme != "single"
+    pts_t = [tile(typed["R"])] + ([tile(typed["Rp"])] if scheme == "double" else [])
+    pts_a = [tile(aff["R"])] + ([tile(aff["Rp"])] if scheme == "double" else [])
+    keys_t = [tile(typed["P0"][idx % k])] + ([tile(typed["P1"][idx % k])] if two else [])
+    keys_a = [tile(aff["P0"][idx % k])] + ([tile(aff["P1"][idx % k])] if two else [])
+    un_t, un_a = pts_t + keys_t, pts_a + keys_a  # canonical order: the signature's points, then the key's
+    di = tile(idx.view(np.int32))
+    ut, mt, ua, ma = tile(typed["u"]), tile(typed["m"]), tile(aff["u"]), tile(aff["m"])
+    ks = E.KeySet.from_mont_cols(scheme, [typed["P0"]] + ([typed["P1"]] if two else []))
+    ok = {p: torch.empty(n, dtype=torch.uint8, device=dev) for p in "abcd"}
+    ws = {"a": E.keyed_mont_workspace_bytes(scheme, n), "b": E.keyed_workspace_bytes(n), "c": E.mont_workspace_bytes(n),
+          "d": E.workspace_bytes(n)}
+    ws = {p: torch.empty(b, dtype=torch.uint8, device=dev) for p, b in ws.items()}
+    fns = {"a": lambda: ks.verify_mont_dev(ut, *pts_t, di, mt, ok["a"], ws["a"]),
+           "b": lambda: ks.verify_dev(ua, *pts_a, di, ma, ok["b"], ws["b"]),
+           "c": lambda: getattr(E, "verify_%s_mont_dev" % scheme)(ut, *un_t, mt, ok["c"], ws["c"]),
+           "d": lambda: getattr(E, "verify_%s_dev" % scheme)(ua, *un_a, ma, ok["d"], ws["d"])}
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    t = {p: [] for p in fns}
+    for _ in range(reps):
+        for p, f in fns.items():
+            t[p].append(timed(f))
+    torch.cuda.synchronize()
+    v = {p: o.cpu().numpy() for p, o in ok.items()}
+    in_range = np.tile(idx, times) < k
+    for p in "bcd":
+        same = v["a"] == v[p] if p == "b" else (v["a"][in_range] == v[p][in_range])  # (c, d read key idx % k)
+        assert same.all(), "path %s differs from the keyed typed call at %d items" % (p, int((~same).sum()))
+    assert 0.9 < v["a"].mean() < 0.95 or k == 1, v["a"].mean()
+    names = {"a": "keyed_mont_dev", "b": "keyed_dev_prenormalised", "c": "mont_dev", "d": "affine_dev"}
+    out = {"scheme": scheme, "k": k, "n": n, "reps": reps, "verdicts_equal": True}
+    for p in "abcd":
+        out[names[p]] = _stats(t[p])
+    med = lambda p: out[names[p]]["median_ms"]
+    out["D_ms"] = round(med("a") - med("b"), 4)
+    out["D0_ms"] = round(med("c") - med("d"), 4)
+    out["a_spread_ms"] = round(out[names["a"]]["max_ms"] - out[names["a"]]["min_ms"], 4)
+    out["relation_D_le_D0_plus_spread_holds"] = bool(out["D_ms"] <= out["D0_ms"] + out["a_spread_ms"])
+    out["mont_dev_over_keyed_mont_dev"] = round(med("c") / med("a"), 3)
+    out["keyed_mont_dev_Mverdicts_s"] = round(n / med("a") / 1e3, 2)
+    if host:
+        want = v["a"]
+        idx_n = np.tile(idx, times)
+        per_item = [typed["P0"][idx % k]] + ([typed["P1"][idx % k]] if two else [])
+        sigs, pks, msgs, sig_views, key_views = _records(scheme, typed, per_item, n)
+        keyed_cols = sig_views + [idx_n, msgs]
+        unkeyed_cols = sig_views + key_views + [msgs]
+        host_aff = [np.tile(a, (times, 1)) for a in [aff["u"], aff["R"]] + ([aff["Rp"]] if scheme == "double" else [])]
+        m_aff = np.tile(aff["m"], (times, 1))
+
+        def two_jobs():
+            j0, j1 = ks.submit_mont_cols(keyed_cols), ks.submit_mont_cols(keyed_cols)
+            a0, a1 = j0.wait(), j1.wait()
+            assert (a0 == a1).all()
+            return a0
+
+        paths = {"keyed_mont_cols": lambda: ks.verify_mont_cols(keyed_cols),
+                 "mont_cols": lambda: E.verify_mont_cols(scheme, unkeyed_cols),
+                 "keyed_mont_cols_two_jobs": two_jobs,
+                 "keyed_affine_host": lambda: ks.verify(*host_aff, idx_n, m_aff)}
+        th = {p: [] for p in paths}
+        for p, f in paths.items():
+            got = f()  # (warm-up)
+            assert (got[in_range] == want[in_range]).all(), p
+        for _ in range(host_reps):
+            for p, f in paths.items():
+                t0 = time.perf_counter()
+                got = f()
+                th[p].append((time.perf_counter() - t0) * 1e3)
+                assert (got[in_range] == want[in_range]).all(), p
+        for p in paths:
+            out[p] = _stats(th[p])
+            items = 2 * n if p.endswith("two_jobs") else n
+            out[p]["Mverdicts_s"] = round(items / out[p]["median_ms"] / 1e3, 2)
+        out["host_reps"] = host_reps
+        un = out["mont_cols"]
+        out["keyed_host_minus_unkeyed_host_ms"] = round(out["keyed_mont_cols"]["median_ms"] - un["median_ms"], 4)
+        out["unkeyed_host_spread_ms"] = round(un["max_ms"] - un["min_ms"], 4)
+        out["relation_keyed_host_not_slower_holds"] = bool(
+            out["keyed_host_minus_unkeyed_host_ms"] <= out["unkeyed_host_spread_ms"])
+        out["mont_cols_over_keyed_mont_cols"] = round(un["median_ms"] / out["keyed_mont_cols"]["median_ms"], 3)
+    ks.close()
+    return out
+
+
+def measure_mont_build(kk, reps=3):
+    """dsv_keyset_create_mont_cols against dsv_keyset_create (single scheme): blocking wall-clock per set"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    _, aff, typed = _mont_block(E, "single", kk, 64, 777 + kk)
+    out = {"k": kk, "reps": reps}
+    for name, make in (("create_mont_cols", lambda: E.KeySet.from_mont_cols("single", [typed["P0"]])),
+                       ("create", lambda: E.KeySet("single", aff["P0"]))):
+        ts = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            ks = make()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            assert (ks.key_ok() == 1).all()
+            ks.close()
+        out[name] = _stats(ts[1:])
+        out[name]["us_per_key"] = round(out[name]["median_ms"] * 1e3 / kk, 2)
+    return out
+
+
+def soak_mont(total, log2_n=20, k=64, seed=2026):
+    """the typed keyed _dev and host forms against the affine keyed _dev call over `total` verdicts, the three
+    schemes in turn, fresh wrong items (another key's index, indices out of range) per call"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from schnorr_amd import engine as E
+
+    E.init(0)
+    dev = "cuda:0"
+    n = 1 << log2_n
+    block = 1 << 14
+    times = n // block
+    rng = np.random.default_rng(seed)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    tile = lambda a: T(a).repeat(*([times] + [1] * (a.ndim - 1)))
+    done, calls, differ_dev, differ_host, zeros = 0, 0, 0, 0, 0
+    sets = {}
+    while done < total:
+        scheme = SCHEMES[calls % 3]
+        if scheme not in sets:
+            idx, aff, typed = _mont_block(E, scheme, k, block, seed + calls)
+            two = scheme != "single"
+            pts = ["R"] + (["Rp"] if scheme == "double" else [])
+            sets[scheme] = {
+                "ks": E.KeySet.from_mont_cols(scheme, [typed["P0"]] + ([typed["P1"]] if two else [])),
+                "idx": np.tile(idx, times),
+                "typed": [tile(typed["u"])] + [tile(typed[p]) for p in pts] + [tile(typed["m"])],
+                "aff": [tile(aff["u"])] + [tile(aff[p]) for p in pts] + [tile(aff["m"])],
+                "host": [np.tile(typed["u"], (times, 1))] + [np.tile(typed[p], (times, 1)) for p in pts] +
+                        [np.tile(typed["m"], (times, 1))]}
+        s = sets[scheme]
+        ks = s["ks"]
+        idx = s["idx"].copy()
+        wrong = int(rng.choice([0, 1, 3, 1000, 100000]))
+        at = rng.integers(0, n, size=wrong)
+        idx[at] = (idx[at] + 1 + rng.integers(0, k - 1, size=wrong)) % k
+        far = rng.integers(0, n, size=int(rng.choice([0, 2, 50])))
+        idx[far] = rng.choice([k, k + 1, (1 << 32) - 1], size=len(far))
+        di = T(idx.view(np.int32))
+        ok_t = torch.empty(n, dtype=torch.uint8, device=dev)
+        ok_a = torch.empty(n, dtype=torch.uint8, device=dev)
+        ks.verify_mont_dev(*s["typed"][:-1], di, s["typed"][-1], ok_t,
+                           torch.empty(E.keyed_mont_workspace_bytes(scheme, n), dtype=torch.uint8, device=dev))
+        ks.verify_dev(*s["aff"][:-1], di, s["aff"][-1], ok_a,
+                      torch.empty(E.keyed_workspace_bytes(n), dtype=torch.uint8, device=dev))
+        host = ks.verify_mont_cols(s["host"][:-1] + [idx, s["host"][-1]])
+        torch.cuda.synchronize()
+        ref = ok_a.cpu().numpy()
+        differ_dev += int((ok_t.cpu().numpy() != ref).sum())
+        differ_host += int((host != ref).sum())
+        zeros += int((ref == 0).sum())
+        done += n
+        calls += 1
+    for v in sets.values():
+        v["ks"].close()
+    return {"verdicts": done, "calls": calls, "false_verdicts": zeros, "differ_dev": differ_dev,
+            "differ_host": differ_host, "k": k, "n": n}
+
+
 def soak(total, log2_n=20, k=64, seed=99):
     """keyed fast accept vs keyed per-signature verdicts over `total` verdicts, all three schemes in turn"""
     import numpy as np
@@ -402,7 +656,47 @@ def main():
     ap.add_argument("--wire", action="store_true")
     ap.add_argument("--one-wire", nargs=4, metavar=("SCHEME", "K", "LOG2N", "HOST"))
     ap.add_argument("--bits", type=int, default=0)
+    ap.add_argument("--mont", action="store_true")
+    ap.add_argument("--one-mont", nargs=4, metavar=("SCHEME", "K", "LOG2N", "HOST"))
+    ap.add_argument("--one-mont-build", type=int, metavar="K")
+    ap.add_argument("--build-ks", default="64,16384")
+    ap.add_argument("--soak-mont", type=int)
     a = ap.parse_args()
+    if a.soak_mont:
+        row = soak_mont(a.soak_mont)
+        print(json.dumps(row), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(row, f, indent=1)
+        return
+    if a.one_mont:
+        s, k, l2, host = a.one_mont
+        print(json.dumps(measure_mont(s, int(k), int(l2), a.reps, host == "1")), flush=True)
+        return
+    if a.one_mont_build:
+        print(json.dumps(measure_mont_build(a.one_mont_build)), flush=True)
+        return
+    if a.mont:
+        rows, builds = [], []
+        ks = [int(x) for x in (a.ks if a.ks != "1,64,4096,16384" else "1,64,4096").split(",")]
+        l2s = [int(x) for x in (a.log2_ns if a.log2_ns != "18,20" else "20,14").split(",")]
+        jobs = [("row", ["--one-mont", scheme, str(k), str(l2), "1" if (k == 64 and l2 == max(l2s)) else "0"])
+                for scheme in a.schemes.split(",") for l2 in l2s for k in ks]
+        jobs += [("build", ["--one-mont-build", x]) for x in a.build_ks.split(",") if x]
+        for kind, args in jobs:
+            cmd = [sys.executable, os.path.abspath(__file__)] + args + ["--reps", str(a.reps)]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+            if p.returncode != 0:
+                sys.stderr.write(p.stdout + p.stderr)
+                raise SystemExit("measurement %s failed with status %d" % (" ".join(args), p.returncode))
+            row = json.loads(p.stdout.strip().splitlines()[-1])
+            print(json.dumps(row), flush=True)
+            (rows if kind == "row" else builds).append(row)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as f:
+                    json.dump({"reps": a.reps, "rows": rows, "set_construction": builds}, f, indent=1)
+        return
     if a.soak:
         row = soak(a.soak)
         print(json.dumps(row), flush=True)
