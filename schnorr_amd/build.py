@@ -146,6 +146,33 @@ def build_probe(force=False, verbose=False):
     return out
 
 
+RLC_PROBE_SRC = os.path.join(ROOT, "tests", "gpu_probe", "rlc_probe.hip")
+
+
+def rlc_probe_path():
+    return os.path.join(HERE, "libdsv_rlcprobe.so")
+
+
+def build_rlc_probe(force=False, verbose=False):
+    """schnorr_amd/libdsv_rlcprobe.so: the test-only fast-accept probe (tests/gpu_probe/rlc_probe.hip) — one
+    group's aggregate under a chosen weight key, through the engine's own launchers: host code only, linked
+    against libdsv.so beside it (run-time path $ORIGIN), compiled with the engine's FLAGS / ARCH; not part of
+    libdsv.so (git-ignored, travels to the GPU box like it)"""
+    out = rlc_probe_path()
+    lib = build()
+    deps = _deps() + [RLC_PROBE_SRC, lib]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps if os.path.exists(d)):
+        return out
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise RuntimeError("hipcc not found: cannot build the fast-accept probe")
+    cmd = [hipcc] + FLAGS + ["-shared", "-I", CSRC, RLC_PROBE_SRC, "-o", out, "-L", HERE, "-ldsv", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def _includes(path, seen):
     """the translation unit and every local header it includes, transitively"""
     import re

@@ -37,6 +37,9 @@
 #include "rlc.h"
 #include "host_sync.h"
 
+namespace dsv {
+struct KeyedRlcBuffers;  // keyed_rlc.h
+}
 namespace dsvh {
 
 using namespace dsv;
@@ -409,6 +412,8 @@ int rlc_clear_accepted(int* accepted);
 int rlc_history(Context& ctx);  // the device's history counter (-1: no pinned memory to be had)
 // pieces of the fast accept's control that the keyed one (dsv_keyed_rlc.hip) shares
 void carve_rlc_buffers(Stager& st, const RlcPlan& p, RlcBuffers& b);
+// the keyed one's per-key buffers (keyed_rlc.h), carved from `st` behind the bucket buffers (dsv_keyed_rlc.hip)
+void carve_keyed_rlc_buffers(Stager& st, const RlcPlan& p, int scheme, size_t k, KeyedRlcBuffers& kb);
 size_t rlc_group_items(size_t n);
 int rlc_split_groups(size_t cnt, int window_bits);
 RlcPlan rlc_group_plan(int scheme, size_t cnt, int window_bits, int groups, bool keyed = false);

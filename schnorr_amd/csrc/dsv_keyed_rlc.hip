@@ -14,6 +14,17 @@
 using namespace dsvh;
 
 extern "C++" {
+namespace dsvh {
+// ksum, touched, bad back to back: one memset (launch_keyed_rlc_prep)
+void carve_keyed_rlc_buffers(Stager& st, const RlcPlan& p, int scheme, size_t k, KeyedRlcBuffers& kb) {
+  const size_t G = p.groups;
+  kb.ksum = reinterpret_cast<unsigned long long*>(st.take(G * k * (size_t)keyed_scalars(scheme) * 8 * 8));
+  kb.touched = reinterpret_cast<u32*>(st.take(G * k * sizeof(u32)));
+  kb.bad = reinterpret_cast<u32*>(st.take(k * sizeof(u32)));
+  kb.partial = reinterpret_cast<u32*>(st.take(G * keyed_term_blocks(k) * 36 * sizeof(u32)));
+  kb.terms = reinterpret_cast<u32*>(st.take(G * 36 * sizeof(u32)));
+}
+}  // namespace dsvh
 namespace {
 // Below this many items of a group (automatic window bits) the aggregate does not pay for its latency-bound
 // tail (~0.9 ms whatever the batch): the group goes to the keyed per-signature kernel as it is.  Measured (DESIGN.md
@@ -36,13 +47,7 @@ KeyedCarve carve_keyed_rlc(void* ws, size_t nmax, size_t cnt, const RlcPlan& p, 
   r.flags_area = reinterpret_cast<u32*>(st.take(kRlcFlagBlocks * kRlcGroupFlagWords * sizeof(u32)));
   r.b.flags = r.flags_area;
   carve_rlc_buffers(st, p, r.b);
-  const size_t G = p.groups;
-  // ksum, touched, bad back to back: one memset (launch_keyed_rlc_prep)
-  r.kb.ksum = reinterpret_cast<unsigned long long*>(st.take(G * k * (size_t)keyed_scalars(scheme) * 8 * 8));
-  r.kb.touched = reinterpret_cast<u32*>(st.take(G * k * sizeof(u32)));
-  r.kb.bad = reinterpret_cast<u32*>(st.take(k * sizeof(u32)));
-  r.kb.partial = reinterpret_cast<u32*>(st.take(G * keyed_term_blocks(k) * 36 * sizeof(u32)));
-  r.kb.terms = reinterpret_cast<u32*>(st.take(G * 36 * sizeof(u32)));
+  carve_keyed_rlc_buffers(st, p, scheme, k, r.kb);
   r.bytes = keyed_ws_bytes(nmax) + st.off;
   return r;
 }
