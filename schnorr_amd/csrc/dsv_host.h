@@ -331,6 +331,7 @@ constexpr SchemeLayout kSchemes[3] = {
     {3, 64, 64, 0, -1, 1, -1, 2, false},
 };
 inline const SchemeLayout& layout(int scheme) { return kSchemes[scheme]; }
+inline bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
 // One call's items: u (32 B), the points in canonical order, m (32 B) per item; pt_bytes apart per
 // item (64: affine, 96: projective / Montgomery limbs).  Unused slots are null and stay null.
 struct Items {

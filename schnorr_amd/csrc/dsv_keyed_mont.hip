@@ -9,9 +9,9 @@
 
 namespace dsvh {
 
-KeyedMontCols carve_keyed_mont(Stager& x, int scheme, size_t n) {
-  const int np = keyed_mont_points(scheme);
-  KeyedMontCols w;
+KeyedCols carve_keyed_mont(Stager& x, int scheme, size_t n) {
+  const int np = keyed_sig_points(scheme);
+  KeyedCols w;
   w.u = x.take(n * 32);
   w.m = x.take(n * 32);
   w.R = x.take(n * 64);
@@ -22,8 +22,8 @@ KeyedMontCols carve_keyed_mont(Stager& x, int scheme, size_t n) {
 }
 
 void normalize_keyed_mont(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m,
-                          size_t n, const KeyedMontCols& w, hipStream_t stream, int per_lane, int block) {
-  const int np = keyed_mont_points(scheme);
+                          size_t n, const KeyedCols& w, hipStream_t stream, int per_lane, int block) {
+  const int np = keyed_sig_points(scheme);
   NormalizeArgs a = {};
   a.in[0] = R;
   a.out[0] = w.R;
@@ -57,47 +57,7 @@ int check_keyed_mont_cols(const dsv_keyset* ks, const dsv_column* cols, size_t n
 
 namespace {
 
-bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
 size_t keyed_mont_ws_bytes(int scheme, size_t n) { return keyed_mont_cols_bytes(scheme, n) + keyed_ws_bytes(n); }
-template <int SCHEME>
-size_t keyed_mont_need(size_t n, size_t, int) { return keyed_mont_ws_bytes(SCHEME, n); }
-constexpr size_t (*kKeyedMontNeed[3])(size_t, size_t, int) = {keyed_mont_need<0>, keyed_mont_need<1>,
-                                                              keyed_mont_need<2>};
-
-int verify_keyed_mont_dev(const dsv_keyset* ks, const void* u, const void* R, const void* Rp, const void* idx,
-                          const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int r = check_n(n)) return r;
-  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
-  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  const int scheme = ks->scheme;
-  Context* cp = nullptr;
-  if (int r = check_set(ks, scheme, n, cp)) return r;
-  if (n == 0) return DSV_OK;
-  const bool inputs_null = !u || !R || (keyed_mont_points(scheme) == 2 && !Rp) || !m;
-  if (int r = check_keyed_dev(ks, cp, inputs_null, idx, n, ok, workspace, workspace_bytes, 0, kKeyedMontNeed[scheme]))
-    return r;
-  Context& ctx = *cp;
-  DSV_ON_DEVICE(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  Stager x(static_cast<uint8_t*>(workspace));
-  const KeyedMontCols w = carve_keyed_mont(x, scheme, n);
-  normalize_keyed_mont(scheme, (const uint8_t*)u, (const uint8_t*)R, (const uint8_t*)Rp, (const uint8_t*)m, n, w, s);
-  enqueue_keyed(ctx, ks, w.items(scheme), (const uint32_t*)idx, n, (uint8_t*)ok, x.take(keyed_ws_bytes(n)), s,
-                w.valid);
-  HIP_TRY(hipGetLastError());
-  return DSV_OK;
-}
-
-// device buffers + stream of one create call, released on every path
-struct Scratch {
-  uint8_t* dev = nullptr;
-  hipStream_t s = nullptr;
-  ~Scratch() {
-    if (s) (void)hipStreamSynchronize(s);
-    if (dev) (void)hipFree(dev);
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
 
 }  // namespace
 
@@ -110,7 +70,7 @@ int verify_keyed_mont_cols_locked(const dsv_keyset* ks, const dsv_column* cols, 
   Context* cp = nullptr;
   if (int r = check_set(ks, scheme, n, cp)) return r;
   if (n == 0) return DSV_OK;
-  const int np = keyed_mont_points(scheme), nc = keyed_mont_columns(scheme);
+  const int np = keyed_sig_points(scheme), nc = keyed_mont_columns(scheme);
   HostIn ins[kMaxHostIn];
   for (int c = 0; c < nc; c++)
     ins[c] = HostIn{static_cast<const uint8_t*>(cols[c].base), keyed_mont_width(scheme, c), cols[c].stride};
@@ -119,7 +79,7 @@ int verify_keyed_mont_cols_locked(const dsv_keyset* ks, const dsv_column* cols, 
   return run_pipelined(
       *cp, ins, (size_t)nc, ok, n, prep_item_bytes, 0,
       [=](const void* const* d, size_t c, Stager& x, hipStream_t st, Staged& g) {
-        const KeyedMontCols w = carve_keyed_mont(x, scheme, c);
+        const KeyedCols w = carve_keyed_mont(x, scheme, c);
         normalize_keyed_mont(scheme, (const uint8_t*)d[0], (const uint8_t*)d[1],
                              np == 2 ? (const uint8_t*)d[2] : nullptr, (const uint8_t*)d[np + 2], c, w, st,
                              cp->norm_per_lane, cp->norm_block);  // ONE launch
@@ -147,46 +107,39 @@ using namespace dsvh;
 extern "C" {
 
 int dsv_keyset_create_mont_cols(int scheme, const dsv_column* cols, size_t k, dsv_keyset** out) {
-  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null output handle");
-  *out = nullptr;
-  if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
-  if (k > 0xffffffffu) return fail(DSV_ERR_TOO_LARGE, "%zu keys: indices are 32-bit", k);
   const int np = keyset_points(scheme);
-  if (k && !cols) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  for (int p = 0; k && p < np; p++) {
-    if (!cols[p].base) return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: null pointer", p);
-    if (cols[p].stride < 96) return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: stride %zu < 96", p, cols[p].stride);
-  }
-  Context* cp = nullptr;
-  if (int r = current_context(cp)) return r;
-  Context& ctx = *cp;
-  DSV_ON_DEVICE(ctx);
-  std::vector<uint8_t> dense;  // the key points gathered out of the objects (outlives the transfer: x syncs)
-  Scratch x;
-  const uint8_t* P[2] = {nullptr, nullptr};
-  uint8_t* valid = nullptr;
-  if (k) {
-    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
-    // device scratch: the affine points (np x k x 64 B), the objects' limbs (np x k x 96 B), the
-    // normalisation's verdicts and its prefix products
-    const size_t off_in = align_up((size_t)np * k * 64, 256), off_valid = off_in + align_up((size_t)np * k * 96, 256),
-                 off_prefix = off_valid + align_up(k, 256);
-    HIP_TRY(hipMalloc(&x.dev, off_prefix + align_up(normalize_prefix_bytes(k, np), 256)));
-    dense.resize((size_t)np * k * 96);
-    NormalizeArgs a = {};
-    for (int p = 0; p < np; p++) {
-      copy_strided_plain(dense.data() + (size_t)p * k * 96, static_cast<const uint8_t*>(cols[p].base), cols[p].stride,
-                         96, k);
-      P[p] = x.dev + (size_t)p * k * 64;
-      a.in[p] = x.dev + off_in + (size_t)p * k * 96;
-      a.out[p] = x.dev + (size_t)p * k * 64;
-    }
-    HIP_TRY(hipMemcpyAsync(x.dev + off_in, dense.data(), dense.size(), hipMemcpyHostToDevice, x.s));
-    valid = x.dev + off_valid;
-    launch_normalize_uvz(a, np, k, valid, reinterpret_cast<u32*>(x.dev + off_prefix), x.s);
-    HIP_TRY(hipGetLastError());
-  }
-  return create_from_device(ctx, scheme, P[0], P[1], valid, k, x.s, out);
+  // behind the points: the objects' limbs (np x k x 96 B), the normalisation's verdicts and its prefix products
+  const size_t off_valid = align_up((size_t)np * k * 96, 256), off_prefix = off_valid + align_up(k, 256);
+  // the key points gathered out of the objects (outlives the transfer: create_keyset's scratch syncs its stream
+  // before create_keyset returns)
+  std::vector<uint8_t> dense;
+  return create_keyset(
+      scheme, k, out,
+      [=] {
+        if (!cols) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+        for (int p = 0; p < np; p++) {
+          if (!cols[p].base) return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: null pointer", p);
+          if (cols[p].stride < 96)
+            return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: stride %zu < 96", p, cols[p].stride);
+        }
+        return (int)DSV_OK;
+      },
+      off_prefix + align_up(normalize_prefix_bytes(k, np), 256),
+      [=, &dense](Context&, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid) {
+        dense.resize((size_t)np * k * 96);
+        NormalizeArgs a = {};
+        for (int p = 0; p < np; p++) {
+          copy_strided_plain(dense.data() + (size_t)p * k * 96, static_cast<const uint8_t*>(cols[p].base),
+                             cols[p].stride, 96, k);
+          a.in[p] = own + (size_t)p * k * 96;
+          a.out[p] = P + (size_t)p * k * 64;
+        }
+        HIP_TRY(hipMemcpyAsync(own, dense.data(), dense.size(), hipMemcpyHostToDevice, s));
+        valid = own + off_valid;
+        launch_normalize_uvz(a, np, k, valid, reinterpret_cast<u32*>(own + off_prefix), s);
+        HIP_TRY(hipGetLastError());
+        return (int)DSV_OK;
+      });
 }
 
 size_t dsv_keyed_mont_workspace_bytes(int scheme, size_t n) {
@@ -196,7 +149,17 @@ size_t dsv_keyed_mont_workspace_bytes(int scheme, size_t n) {
 int dsv_verify_keyed_mont_dev(const dsv_keyset* ks, const void* u, const void* R_uvz, const void* Rp_uvz,
                               const void* key_idx, const void* m, size_t n, void* ok, void* workspace,
                               size_t workspace_bytes, void* stream) {
-  return verify_keyed_mont_dev(ks, u, R_uvz, Rp_uvz, key_idx, m, n, ok, workspace, workspace_bytes, stream);
+  return run_keyed_dev(
+      ks, -1, [=](int scheme) { return !u || !R_uvz || (keyed_sig_points(scheme) == 2 && !Rp_uvz) || !m; },
+      [=](int scheme) { return keyed_mont_cols_bytes(scheme, n); }, key_idx, n, ok, workspace, workspace_bytes, stream,
+      [=](const Context&, int scheme, Stager& x, hipStream_t s, Items& in, const uint8_t*& valid_in) {
+        const KeyedCols w = carve_keyed_mont(x, scheme, n);
+        normalize_keyed_mont(scheme, (const uint8_t*)u, (const uint8_t*)R_uvz, (const uint8_t*)Rp_uvz,
+                             (const uint8_t*)m, n, w, s);
+        in = w.items(scheme);
+        valid_in = w.valid;
+        return (int)DSV_OK;
+      });
 }
 
 int dsv_verify_keyed_mont_cols(const dsv_keyset* ks, const dsv_column* cols, size_t n, uint8_t* ok) {

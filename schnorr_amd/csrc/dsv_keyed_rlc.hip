@@ -140,8 +140,9 @@ int verify_keyed_rlc_dev(const dsv_keyset* ks, const Items& in, const void* idx,
   if (int r = check_set(ks, in.scheme, n, cp)) return r;
   if (int r = refuse_capture(s, "the keyed fast accept")) return r;
   if (n == 0) return rlc_clear_accepted(accepted);
-  if (int r = check_keyed_dev(ks, cp, in, idx, n, ok, workspace, workspace_bytes, window_bits,
-                              dsv_keyed_rlc_workspace_bytes))
+  // (0 bytes for window bits out of range: check_keyed_dev looks at the bits first)
+  if (int r = check_keyed_dev(ks, cp, keyed_any_null(in), idx, ok, workspace, workspace_bytes, window_bits,
+                              dsv_keyed_rlc_workspace_bytes(n, ks->k, window_bits)))
     return r;
   Context& ctx = *cp;
   DSV_ON_DEVICE(ctx);
@@ -167,7 +168,7 @@ size_t dsv_keyed_rlc_workspace_bytes(size_t n, size_t k, int window_bits) {
 
 // out[24]: the fields of dsv_rlc_plan_info, of the keyed plan; out[23] = workspace bytes of this plan for k keys
 int dsv_keyed_rlc_plan_info(int scheme, size_t n, size_t k, int window_bits, int groups, uint64_t* out) {
-  if (!out || scheme < 0 || scheme > 2 || n == 0 || n > kRlcMaxGroup || groups < 0 || groups > kRlcMaxSub)
+  if (!out || !scheme_ok(scheme) || n == 0 || n > kRlcMaxGroup || groups < 0 || groups > kRlcMaxSub)
     return fail(DSV_ERR_INVALID_ARGUMENT, "bad argument");
   if (int r = check_rlc_bits(window_bits)) return r;
   const RlcPlan p = rlc_group_plan(scheme, n, window_bits, groups, true);

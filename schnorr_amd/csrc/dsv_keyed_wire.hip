@@ -7,11 +7,11 @@
 
 namespace dsvh {
 
-KeyedWireCols carve_keyed_wire(Stager& x, int scheme, size_t n) {
-  KeyedWireCols w;
+KeyedCols carve_keyed_wire(Stager& x, int scheme, size_t n) {
+  KeyedCols w = {};
   w.u = x.take(n * 32);
   w.R = x.take(n * 64);
-  w.Rp = keyed_wire_points(scheme) == 2 ? x.take(n * 64) : nullptr;
+  w.Rp = keyed_sig_points(scheme) == 2 ? x.take(n * 64) : nullptr;
   w.valid = x.take(n);
   return w;
 }
@@ -24,16 +24,11 @@ void decode_keyed_wire(const Context& ctx, int scheme, const uint8_t* sig, size_
 
 namespace {
 
-bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
 size_t keyed_wire_ws_bytes(int scheme, size_t n) { return keyed_wire_cols_bytes(scheme, n) + keyed_ws_bytes(n); }
-template <int SCHEME>
-size_t keyed_wire_need(size_t n, size_t, int) { return keyed_wire_ws_bytes(SCHEME, n); }
-constexpr size_t (*kKeyedWireNeed[3])(size_t, size_t, int) = {keyed_wire_need<0>, keyed_wire_need<1>,
-                                                              keyed_wire_need<2>};
 
 // decode -> hash -> keyed kernel for cnt records; every pointer device memory of ctx's device
 void enqueue_keyed_wire(const Context& ctx, const dsv_keyset* ks, const uint8_t* sig, const uint32_t* idx,
-                        const void* m, size_t cnt, uint8_t* ok, const KeyedWireCols& w, void* keyed_ws,
+                        const void* m, size_t cnt, uint8_t* ok, const KeyedCols& w, void* keyed_ws,
                         hipStream_t s) {
   const Items in = w.items(ks->scheme, m);
   decode_keyed_wire(ctx, ks->scheme, sig, cnt, in, w.valid, s);
@@ -42,21 +37,17 @@ void enqueue_keyed_wire(const Context& ctx, const dsv_keyset* ks, const uint8_t*
 
 int verify_keyed_wire_dev(const dsv_keyset* ks, int scheme, const void* sig, const void* idx, const void* m,
                           size_t n, void* ok, void* workspace, size_t workspace_bytes, void* stream) {
-  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  Context* cp = nullptr;
-  if (int r = check_set(ks, scheme, n, cp)) return r;
-  if (n == 0) return DSV_OK;
-  if (int r = check_keyed_dev(ks, cp, !sig || !m, idx, n, ok, workspace, workspace_bytes, 0, kKeyedWireNeed[scheme]))
-    return r;
-  if ((uintptr_t)sig & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");
-  Context& ctx = *cp;
-  DSV_ON_DEVICE(ctx);
-  Stager x(static_cast<uint8_t*>(workspace));
-  const KeyedWireCols w = carve_keyed_wire(x, scheme, n);
-  enqueue_keyed_wire(ctx, ks, (const uint8_t*)sig, (const uint32_t*)idx, m, n, (uint8_t*)ok, w,
-                     x.take(keyed_ws_bytes(n)), (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return DSV_OK;
+  return run_keyed_dev(
+      ks, scheme, [=](int) { return !sig || !m; }, [=](int) { return keyed_wire_cols_bytes(scheme, n); }, idx, n, ok,
+      workspace, workspace_bytes, stream,
+      [=](const Context& ctx, int, Stager& x, hipStream_t s, Items& in, const uint8_t*& valid_in) {
+        if ((uintptr_t)sig & 15) return fail(DSV_ERR_INVALID_ARGUMENT, "records must be 16-byte aligned");
+        const KeyedCols w = carve_keyed_wire(x, scheme, n);
+        in = w.items(scheme, m);
+        valid_in = w.valid;
+        decode_keyed_wire(ctx, scheme, (const uint8_t*)sig, n, in, w.valid, s);
+        return (int)DSV_OK;
+      });
 }
 
 // host arrays: the shared pipeline on the key set's device; per sub-batch the decoded columns come from the

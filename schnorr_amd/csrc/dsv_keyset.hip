@@ -16,8 +16,6 @@ std::vector<dsv_keyset*> g_keysets;
 constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
 constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
 
-bool scheme_ok(int scheme) { return scheme >= 0 && scheme <= 2; }
-
 void free_sets_of(int device) {  // (exclusive lock held)
   for (dsv_keyset* ks : g_keysets) {
     if (ks->device != device || !ks->alive) continue;
@@ -36,8 +34,6 @@ int keyset_context(const dsv_keyset* ks, Context*& out) {
   out = &g_ctx[ks->device];
   return DSV_OK;
 }
-
-}  // namespace
 
 // tables of k keys from device points P0 / P1 (and the decoder's verdicts valid_in); registers the set
 int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
@@ -83,7 +79,6 @@ int current_context(Context*& out) {
   return DSV_OK;
 }
 
-namespace {
 // device buffers + stream of one create call, released on every path
 struct Scratch {
   uint8_t* dev = nullptr;
@@ -95,14 +90,16 @@ struct Scratch {
   }
 };
 
-int create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, bool is_wire, const uint8_t* wire, size_t k,
-           dsv_keyset** out) {
+}  // namespace
+
+int create_keyset(int scheme, size_t k, dsv_keyset** out, const std::function<int()>& check_pointers,
+                  size_t own_bytes, const KeysetStage& stage) {
   if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null output handle");
   *out = nullptr;
   if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
   if (k > kMaxKeys) return fail(DSV_ERR_TOO_LARGE, "%zu keys: indices are 32-bit", k);
-  const int np = keyset_points(scheme);
-  if (k && (is_wire ? !wire : (!pk_uv || (np == 2 && !pk2_uv)))) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (k)
+    if (int r = check_pointers()) return r;
   Context* cp = nullptr;
   if (int r = current_context(cp)) return r;
   Context& ctx = *cp;
@@ -111,41 +108,27 @@ int create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, bool is_wire
   const uint8_t* P[2] = {nullptr, nullptr};
   uint8_t* valid = nullptr;
   if (k) {
+    const int np = keyset_points(scheme);
     HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
-    // device scratch: the affine points (np x k x 64 B), then for wire records the records and the
-    // decoder's verdicts
-    const size_t rec = 32 * (size_t)np;
-    const size_t off_in = align_up((size_t)np * k * 64, 256), off_valid = off_in + align_up(k * rec, 256);
-    HIP_TRY(hipMalloc(&x.dev, is_wire ? off_valid + align_up(k, 256) : off_in));
+    // device scratch: the affine points (np x k x 64 B), then what the form stages them from
+    const size_t off_own = align_up((size_t)np * k * 64, 256);
+    HIP_TRY(hipMalloc(&x.dev, off_own + own_bytes));
     for (int p = 0; p < np; p++) P[p] = x.dev + (size_t)p * k * 64;
-    if (is_wire) {
-      valid = x.dev + off_valid;
-      HIP_TRY(hipMemcpyAsync(x.dev + off_in, wire, k * rec, hipMemcpyHostToDevice, x.s));
-      for (int p = 0; p < np; p++)
-        if (int r = decompress_on(ctx, x.dev + off_in + 32 * p, rec, k, (void*)P[p], valid, p > 0, x.s)) return r;
-    } else {
-      HIP_TRY(hipMemcpyAsync((void*)P[0], pk_uv, k * 64, hipMemcpyHostToDevice, x.s));
-      if (np == 2) HIP_TRY(hipMemcpyAsync((void*)P[1], pk2_uv, k * 64, hipMemcpyHostToDevice, x.s));
-    }
+    if (int r = stage(ctx, x.dev, x.dev + off_own, x.s, valid)) return r;
   }
   return create_from_device(ctx, scheme, P[0], P[1], valid, k, x.s, out);
 }
 
-
-size_t keyed_need(size_t n, size_t, int) { return keyed_ws_bytes(n); }
-
-int verify_keyed_dev(const dsv_keyset* ks, const Items& in, const void* idx, size_t n, void* ok, void* workspace,
+namespace {
+// the affine form: the caller's columns as they are, no preparation launch
+int verify_keyed_dev(const dsv_keyset* ks, const Items& items, const void* idx, size_t n, void* ok, void* workspace,
                      size_t workspace_bytes, void* stream) {
-  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
-  Context* cp = nullptr;
-  if (int r = check_set(ks, in.scheme, n, cp)) return r;
-  if (n == 0) return DSV_OK;
-  if (int r = check_keyed_dev(ks, cp, in, idx, n, ok, workspace, workspace_bytes, 0, keyed_need)) return r;
-  Context& ctx = *cp;
-  DSV_ON_DEVICE(ctx);
-  enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, workspace, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return DSV_OK;
+  return run_keyed_dev(
+      ks, items.scheme, [&](int) { return keyed_any_null(items); }, [](int) { return (size_t)0; }, idx, n, ok,
+      workspace, workspace_bytes, stream, [&](const Context&, int, Stager&, hipStream_t, Items& in, const uint8_t*&) {
+        in = items;
+        return (int)DSV_OK;
+      });
 }
 
 // host arrays: chunks through the context's staging, on its null stream
@@ -157,7 +140,7 @@ int verify_keyed_host(const dsv_keyset* ks, const Items& in, const uint32_t* idx
   if (keyed_any_null(in) || !idx || !ok) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   Context& ctx = *cp;
   DSV_HOST_LOCK();
-  const int np = in.scheme == 1 ? 2 : 1;  // the signature's points
+  const int np = keyed_sig_points(in.scheme);
   const size_t chunk = n < kKeyedHostChunk ? n : kKeyedHostChunk;
   const size_t per_item = 32 + 32 + 4 + 1 + 64 * (size_t)np;
   if (int r = ensure_stage(ctx, chunk * per_item + keyed_ws_bytes(chunk) + 8 * 256)) return r;
@@ -190,18 +173,16 @@ int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx) {
   if (int r = check_n(n)) return r;
   if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
   if (int r = keyset_context(ks, ctx)) return r;
-  if (ks->scheme != scheme)
+  if (scheme >= 0 && ks->scheme != scheme)
     return fail(DSV_ERR_INVALID_ARGUMENT, "key set of scheme %d used with scheme %d", ks->scheme, scheme);
   return DSV_OK;
 }
-int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, size_t n,
-                    const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
-                    size_t (*need)(size_t n, size_t k, int window_bits)) {
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, const void* ok,
+                    const void* workspace, size_t workspace_bytes, int window_bits, size_t need) {
   if (inputs_null || !idx || !ok || !workspace) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   if (int r = check_rlc_bits(window_bits)) return r;
-  const size_t bytes = need(n, ks->k, window_bits);
-  if (workspace_bytes < bytes)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, bytes);
+  if (workspace_bytes < need)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
   Context* octx = nullptr;
   if (int r = device_context(ok, octx)) return r;
   if (octx != ctx)
@@ -236,10 +217,30 @@ size_t dsv_keyset_bytes(int scheme, size_t k) { return scheme_ok(scheme) ? keyse
 size_t dsv_keyed_workspace_bytes(size_t n) { return keyed_ws_bytes(n); }
 
 int dsv_keyset_create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t k, dsv_keyset** out) {
-  return create(scheme, pk_uv, pk2_uv, false, nullptr, k, out);
+  const bool two = keyset_points(scheme) == 2;
+  return create_keyset(
+      scheme, k, out,
+      [=] { return !pk_uv || (two && !pk2_uv) ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; }, 0,
+      [=](Context&, uint8_t* P, uint8_t*, hipStream_t s, uint8_t*&) {
+        HIP_TRY(hipMemcpyAsync(P, pk_uv, k * 64, hipMemcpyHostToDevice, s));
+        if (two) HIP_TRY(hipMemcpyAsync(P + k * 64, pk2_uv, k * 64, hipMemcpyHostToDevice, s));
+        return (int)DSV_OK;
+      });
 }
 int dsv_keyset_create_wire(int scheme, const uint8_t* pk_bytes, size_t k, dsv_keyset** out) {
-  return create(scheme, nullptr, nullptr, true, pk_bytes, k, out);
+  // behind the points: the records, then the decoder's verdicts
+  const int np = keyset_points(scheme);
+  const size_t rec = 32 * (size_t)np, off_valid = align_up(k * rec, 256);
+  return create_keyset(
+      scheme, k, out, [=] { return !pk_bytes ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; },
+      off_valid + align_up(k, 256),
+      [=](Context& ctx, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid) {
+        valid = own + off_valid;
+        HIP_TRY(hipMemcpyAsync(own, pk_bytes, k * rec, hipMemcpyHostToDevice, s));
+        for (int p = 0; p < np; p++)
+          if (int r = decompress_on(ctx, own + 32 * p, rec, k, P + (size_t)p * k * 64, valid, p > 0, s)) return r;
+        return (int)DSV_OK;
+      });
 }
 
 int dsv_keyset_destroy(dsv_keyset* ks) {

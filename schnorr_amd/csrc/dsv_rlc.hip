@@ -482,7 +482,7 @@ size_t dsv_rlc_workspace_bytes(size_t n, int window_bits) {
 // entries, buckets, points of tmp[0], points of tmp[1], coarse_bits, rows, row_stride, bins, bin_cap,
 // sub-groups, items per sub-group, workspace bytes of this plan
 int dsv_rlc_plan_info(int scheme, size_t n, int window_bits, int groups, uint64_t* out) {
-  if (!out || scheme < 0 || scheme > 2 || n == 0 || n > kRlcMaxGroup || groups < 0 || groups > kRlcMaxSub)
+  if (!out || !scheme_ok(scheme) || n == 0 || n > kRlcMaxGroup || groups < 0 || groups > kRlcMaxSub)
     return fail(DSV_ERR_INVALID_ARGUMENT, "bad argument");
   if (int r = check_rlc_bits(window_bits)) return r;
   const RlcPlan p = rlc_group_plan(scheme, n, window_bits, groups);

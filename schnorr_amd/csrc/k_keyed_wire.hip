@@ -70,7 +70,7 @@ void launch_keyed_wire_decode(int scheme, const uint8_t* sig, size_t n, uint8_t*
                               uint8_t* valid, const uint32_t* ts_cancel, const uint8_t* ts_hash, hipStream_t s) {
   if (n == 0) return;
   const TsTables ts{ts_cancel, ts_hash};
-  const dim3 grid(grid_for(n * (size_t)keyed_wire_points(scheme), kKeyedWireBlock)), block(kKeyedWireBlock);
+  const dim3 grid(grid_for(n * (size_t)keyed_sig_points(scheme), kKeyedWireBlock)), block(kKeyedWireBlock);
   if (scheme == 0)
     hipLaunchKernelGGL(k_keyed_wire_decode<0>, grid, block, 0, s, sig, n, u, R_uv, Rp_uv, valid, ts);
   else if (scheme == 1)

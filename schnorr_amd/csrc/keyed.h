@@ -25,6 +25,8 @@ static_assert(kKeyWindows * kKeyBits == 256, "the recoding covers 256 bits");
 
 // points per key: single PK; double PK, PK'; var-generator PK, Gen
 inline int keyset_points(int scheme) { return scheme == 0 ? 1 : 2; }
+// nonce points per signature: single / var-generator R; double R, R'
+inline int keyed_sig_points(int scheme) { return scheme == 1 ? 2 : 1; }
 // device bytes of a key set: the tables, then one validity byte per key (rounded up to 256)
 inline size_t keyset_table_bytes(int scheme, size_t k) { return (size_t)keyset_points(scheme) * k * kKeyPointBytes; }
 inline size_t keyset_total_bytes(int scheme, size_t k) {

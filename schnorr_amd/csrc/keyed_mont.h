@@ -12,33 +12,26 @@
 
 namespace dsvh {
 
-// nonce points of a signature object (single / var-generator: R; double: R, R')
-inline int keyed_mont_points(int scheme) { return scheme == 1 ? 2 : 1; }
 // columns of a keyed typed batch: u, R [, R'], key_idx, m
-inline int keyed_mont_columns(int scheme) { return 3 + keyed_mont_points(scheme); }
+inline int keyed_mont_columns(int scheme) { return 3 + keyed_sig_points(scheme); }
 // width of column c
 inline size_t keyed_mont_width(int scheme, int c) {
-  const int np = keyed_mont_points(scheme);
+  const int np = keyed_sig_points(scheme);
   return c == 0 || c == np + 2 ? 32 : (c <= np ? 96 : 4);
 }
 
 // what the normalisation launch writes for n items, in this order (dsv_keyed_mont_workspace_bytes): u, m, R,
 // R' (double scheme only), valid, the kernel's prefix scratch; each part rounded up to 256 B
 inline size_t keyed_mont_cols_bytes(int scheme, size_t n) {
-  const int np = keyed_mont_points(scheme);
+  const int np = keyed_sig_points(scheme);
   return 2 * align_up(n * 32, 256) + (size_t)np * align_up(n * 64, 256) + align_up(n, 256) +
          align_up(normalize_prefix_bytes(n, np), 256);
 }
-struct KeyedMontCols {
-  uint8_t *u, *m, *R, *Rp, *valid;
-  u32* prefix;
-  Items items(int scheme) const { return make_items(scheme, u, {R, Rp}, m); }
-};
-KeyedMontCols carve_keyed_mont(Stager& x, int scheme, size_t n);
+KeyedCols carve_keyed_mont(Stager& x, int scheme, size_t n);
 // u, m: n x 32 B Montgomery limbs; R [, Rp]: n x 96 B limbs of u || v || z (device memory) -> w, one launch on
 // `stream`; per_lane / block: the launch shape (0: the kernel's defaults)
 void normalize_keyed_mont(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m,
-                          size_t n, const KeyedMontCols& w, hipStream_t stream, int per_lane = 0, int block = 0);
+                          size_t n, const KeyedCols& w, hipStream_t stream, int per_lane = 0, int block = 0);
 
 // argument checks of a keyed column batch, before the set is looked at: n, the set pointer, then every
 // column's pointer, stride and (key_idx) alignment ("column k: ...").  The scheme is read under the

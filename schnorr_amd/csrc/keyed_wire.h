@@ -12,13 +12,9 @@ namespace dsv {
 
 constexpr int kKeyedWireBlock = 256;
 
-// nonce points per signature record (single / var-generator: R; double: R, R'); the record is 32 B of u and
-// 32 B per point
-inline int keyed_wire_points(int scheme) { return scheme == 1 ? 2 : 1; }
-
 // ---- k_keyed_wire.hip --------------------------------------------------------------------------
-// n records at sig + i * (32 + 32 * keyed_wire_points(scheme)), 16-byte aligned.  u[i] = the record's first
-// 32 bytes as they lie; R_uv[i] (Rp_uv[i], double scheme only) = affine canonical u || v of the decompressed nonce
+// n records (32 B of u, then 32 B per nonce point) at sig + i * (32 + 32 * keyed_sig_points(scheme)), 16-byte
+// aligned.  u[i] = the record's first 32 bytes as they lie; R_uv[i] (Rp_uv[i], double scheme only) = affine canonical u || v of the decompressed nonce
 // point, k_decompress's bytes for every input; valid[i] = every nonce point of record i decodes (written
 // once, never read).  One lane per point, the two points of a double item in adjacent lanes.
 void launch_keyed_wire_decode(int scheme, const uint8_t* sig, size_t n, uint8_t* u, uint8_t* R_uv, uint8_t* Rp_uv,

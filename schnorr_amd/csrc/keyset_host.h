@@ -25,43 +25,78 @@ inline bool keyed_any_null(const Items& in) { return !in.u || !in.R() || (in.sch
 inline size_t keyed_ws_bytes(size_t n) { return align_up(n * 32, 256) + align_up(n, 256); }
 // live key sets: verify calls read under the shared lock, create / destroy / shutdown write under the exclusive one
 std::shared_mutex& keyset_mutex();
-// (shared lock held) n is in range; ks is live, of `scheme`, on an initialised device: ctx = its context
+// (shared lock held) n is in range; ks is live, of `scheme` (negative: whatever the set's own is), on an
+// initialised device: ctx = its context
 int check_set(const dsv_keyset* ks, int scheme, size_t n, Context*& ctx);
 // (shared lock held, check_set passed, n > 0) the rest of a keyed _dev call's checks, in this order: null
-// pointers, the window bits (0 for the per-signature form), workspace_bytes >= need(n, ks->k, window_bits), `ok`
-// on the set's device (ctx: the set's context)
+// pointers, the window bits (0 for the per-signature forms), workspace_bytes >= need, `ok` on the set's device
+// (ctx: the set's context)
 // inputs_null: one of the call's input pointers other than idx is null (affine items: keyed_any_null; the wire
 // form: the records or m)
-int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, size_t n,
-                    const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
-                    size_t (*need)(size_t n, size_t k, int window_bits));
-inline int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, const Items& in, const void* idx, size_t n,
-                           const void* ok, const void* workspace, size_t workspace_bytes, int window_bits,
-                           size_t (*need)(size_t n, size_t k, int window_bits)) {
-  return check_keyed_dev(ks, ctx, keyed_any_null(in), idx, n, ok, workspace, workspace_bytes, window_bits, need);
-}
-// the calling thread's current device, which must be initialised: where a constructor builds its set
-int current_context(Context*& out);
-// tables of k keys from device points P0 / P1 (affine, 64 B each; P1 null for the single scheme) and an earlier
-// stage's per-key verdicts valid_in (may be null), built on `s`; blocks, registers the set, *out = its handle
-int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
-                       size_t k, hipStream_t s, dsv_keyset** out);
+int check_keyed_dev(const dsv_keyset* ks, const Context* ctx, bool inputs_null, const void* idx, const void* ok,
+                    const void* workspace, size_t workspace_bytes, int window_bits, size_t need);
 // challenge hash, then the keyed kernel; every pointer device memory of ctx's device
 // valid_in (may be null): per-item bytes of an earlier stage (the wire form's decoder), AND-ed in by the hash
 void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, const uint32_t* idx, size_t n,
                    uint8_t* ok, void* workspace, hipStream_t s, const uint8_t* valid_in = nullptr);
 
+// The body of the per-signature keyed _dev calls (affine, wire, typed objects), enqueue-only on `stream` under the
+// registry's shared lock.  scheme: the entry point's, or negative for the set's own.  A form supplies
+//   inputs_null(scheme)   one of its input pointers other than idx is null,
+//   cols_bytes(scheme)    the workspace bytes of its preparation step, in front of keyed_ws_bytes(n),
+//   prep(ctx, scheme, x, s, in, valid_in)   carves those bytes from x, enqueues the preparation launch on s, and
+//                         leaves the keyed call's items and the per-item verdicts its hash ANDs in (null: none);
+//                         a non-zero return ends the call with nothing more enqueued.
+template <class Null, class Bytes, class Prep>
+int run_keyed_dev(const dsv_keyset* ks, int scheme, Null inputs_null, Bytes cols_bytes, const void* idx, size_t n,
+                  void* ok, void* workspace, size_t workspace_bytes, void* stream, Prep prep) {
+  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
+  Context* cp = nullptr;
+  if (int r = check_set(ks, scheme, n, cp)) return r;
+  if (n == 0) return DSV_OK;
+  scheme = ks->scheme;
+  if (int r = check_keyed_dev(ks, cp, inputs_null(scheme), idx, ok, workspace, workspace_bytes, 0,
+                              cols_bytes(scheme) + keyed_ws_bytes(n)))
+    return r;
+  Context& ctx = *cp;
+  DSV_ON_DEVICE(ctx);
+  const hipStream_t s = (hipStream_t)stream;
+  Stager x(static_cast<uint8_t*>(workspace));
+  Items in;
+  const uint8_t* valid_in = nullptr;
+  if (int r = prep(ctx, scheme, x, s, in, valid_in)) return r;
+  enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, x.take(keyed_ws_bytes(n)), s, valid_in);
+  HIP_TRY(hipGetLastError());
+  return DSV_OK;
+}
+
+// One constructor call (dsv_keyset.hip), on the calling thread's current device: the checks in this order — null
+// `out`, unknown scheme, k > 2^32 - 1, then for k > 0 the form's own check_pointers() — a stream and a device
+// scratch of its own (the affine points P[p] at p * k * 64, then own_bytes of the form's from the next 256-byte
+// boundary), the form's staging, the table build; blocks, registers the set, *out = its handle.
+// stage(ctx, P, own, s, valid) (k > 0): brings the keys' affine points to P on stream s, working in `own`;
+// valid = the per-key verdicts of its decoding for the table build to AND in (left null: none).
+using KeysetStage = std::function<int(Context& ctx, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid)>;
+int create_keyset(int scheme, size_t k, dsv_keyset** out, const std::function<int()>& check_pointers,
+                  size_t own_bytes, const KeysetStage& stage);
+
+// ---- decoded or normalised columns of a keyed batch: what a preparation launch leaves for the keyed call -----
+struct KeyedCols {
+  uint8_t *u, *m;  // m null: the caller's
+  uint8_t *R, *Rp, *valid;
+  u32* prefix;     // the normalisation's scratch; null for the wire form
+  Items items(int scheme, const void* caller_m = nullptr) const {
+    return make_items(scheme, u, {R, Rp}, m ? m : caller_m);
+  }
+};
+
 // ---- the keyed wire form (dsv_keyed_wire.hip, keyed_wire.h) -----------------------------------------------
 // the decoder's outputs for n records, in this order (dsv_keyed_wire_workspace_bytes): u, R, R' (double scheme
 // only), valid; each part rounded up to 256 B
 inline size_t keyed_wire_cols_bytes(int scheme, size_t n) {
-  return align_up(n * 32, 256) + (size_t)keyed_wire_points(scheme) * align_up(n * 64, 256) + align_up(n, 256);
+  return align_up(n * 32, 256) + (size_t)keyed_sig_points(scheme) * align_up(n * 64, 256) + align_up(n, 256);
 }
-struct KeyedWireCols {
-  uint8_t *u, *R, *Rp, *valid;
-  Items items(int scheme, const void* m) const { return make_items(scheme, u, {R, Rp}, m); }
-};
-KeyedWireCols carve_keyed_wire(Stager& x, int scheme, size_t n);
+KeyedCols carve_keyed_wire(Stager& x, int scheme, size_t n);
 // n signature records (device memory, 16-byte aligned) -> out.u, out.R() [, out.Rp()] and valid, one launch on
 // `stream`; a step of its own so that it can stand in front of the keyed fast accept as well
 void decode_keyed_wire(const Context& ctx, int scheme, const uint8_t* sig, size_t n, const Items& out, uint8_t* valid,

@@ -346,6 +346,104 @@ def test_dev_semantics(engine):
             ks.verify_dev(du, dR, di, dm, ok, ws[:10])
 
 
+# ---- the constructors' contract ---------------------------------------------------------------------------
+def _zeros_dev(nbytes):
+    return torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
+
+
+@pytest.mark.parametrize("scheme", (0, 1, 2))
+@pytest.mark.parametrize("form", ("affine", "wire", "mont"))
+def test_constructor_contract(engine, form, scheme):
+    """dsv_keyset_create / _create_wire / _create_mont_cols through the C ABI: the order of the argument checks
+    (output handle, scheme, key count, the form's pointers), and the empty set every form can build"""
+    from schnorr_amd import _lib
+
+    L = _lib.load()
+    INVALID, TOO_LARGE = -2, -5
+    np_keys = 1 if scheme == 0 else 2
+    vp, sz, null = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p(None)
+    host = np.zeros(2 * 96 * 2, np.uint8)  # a readable host buffer; no case below reads it
+    hp = vp(host.ctypes.data)
+
+    def create(sch, data, k, out):
+        """data: the form's pointer arguments (affine: pk_uv, pk2_uv; wire: records; mont: cols)"""
+        fn = {"affine": L.dsv_keyset_create, "wire": L.dsv_keyset_create_wire,
+              "mont": L.dsv_keyset_create_mont_cols}[form]
+        return fn(ctypes.c_int(sch), *data, sz(k), out)
+
+    def cols(*pairs):
+        return ((_lib.Column * 2)(*[_lib.Column(b, s) for b, s in pairs]),)
+
+    no_data = {"affine": (null, null), "wire": (null,), "mont": (null,)}[form]
+    h = vp(0xDEAD0)
+    # null output handle
+    assert create(scheme, no_data, 0, None) == INVALID
+    # unknown scheme: the handle is cleared first
+    assert create(3, no_data, 0, ctypes.byref(h)) == INVALID
+    assert not h.value
+    # the key count is checked before the pointers
+    assert create(scheme, no_data, 1 << 32, ctypes.byref(h)) == TOO_LARGE
+    # null data pointers with k > 0
+    if form == "affine":
+        bad = [((null, hp), None)] if scheme == 0 else [((hp, null), None)]
+    elif form == "wire":
+        bad = [((null,), None)]
+    else:
+        last = np_keys - 1  # the scheme's last key column ("column 1" for the two-point schemes)
+        good = [(host.ctypes.data, 96)] * 2
+        hole, short = list(good), list(good)
+        hole[last] = (None, 96)
+        short[last] = (host.ctypes.data, 95)
+        bad = [((null,), None), (cols(*hole), "column %d" % last), (cols(*short), "stride")]
+    for data, text in bad:
+        h = vp(0xDEAD0)
+        assert create(scheme, data, 2, ctypes.byref(h)) == INVALID, (form, scheme, text)
+        assert not h.value
+        if text:
+            msg = L.dsv_last_error().decode()
+            assert text in msg, msg
+    # the empty set
+    h = vp(0xDEAD0)
+    assert create(scheme, no_data, 0, ctypes.byref(h)) == 0, L.dsv_last_error().decode()
+    assert h.value and h.value != 0xDEAD0
+    sch, k, nbytes, dev = ctypes.c_int(-1), sz(99), sz(99), ctypes.c_int(-1)
+    assert L.dsv_keyset_info(h, ctypes.byref(sch), ctypes.byref(k), ctypes.byref(nbytes), ctypes.byref(dev)) == 0
+    assert (sch.value, k.value, nbytes.value, dev.value) == (scheme, 0, 0, torch.cuda.current_device())
+    assert L.dsv_keyset_key_ok(h, None) == 0
+    # the form's per-signature _dev call on it: n = 0, then three items whose indices are all out of range
+    n = 3
+    ns = 2 if scheme == 1 else 1  # nonce points of a signature
+    idx = torch.from_numpy(np.array([0, 1, 0xFFFFFFFF], np.uint32).view(np.int32)).to(DEV)
+    m = _zeros_dev(n * 32)
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: vp(t.data_ptr())
+    if form == "affine":
+        fn = (L.dsv_verify_single_keyed_dev, L.dsv_verify_double_keyed_dev, L.dsv_verify_vargen_keyed_dev)[scheme]
+        u, pts = _zeros_dev(n * 32), [_zeros_dev(n * 64) for _ in range(ns)]
+        ws_bytes = L.dsv_keyed_workspace_bytes(n)
+        head = [h, p(u)] + [p(t) for t in pts] + [p(idx), p(m)]
+    elif form == "wire":
+        fn = (L.dsv_verify_single_keyed_wire_dev, L.dsv_verify_double_keyed_wire_dev,
+              L.dsv_verify_vargen_keyed_wire_dev)[scheme]
+        sig = _zeros_dev(n * (32 + 32 * ns))
+        ws_bytes = L.dsv_keyed_wire_workspace_bytes(scheme, n)
+        head = [h, p(sig), p(idx), p(m)]
+    else:
+        fn = L.dsv_verify_keyed_mont_dev
+        u, R, Rp = _zeros_dev(n * 32), _zeros_dev(n * 96), _zeros_dev(n * 96)
+        ws_bytes = L.dsv_keyed_mont_workspace_bytes(scheme, n)
+        head = [h, p(u), p(R), p(Rp) if ns == 2 else null, p(idx), p(m)]
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+    ok = _poison(n)
+    assert fn(*head, sz(0), p(ok), p(ws), sz(ws_bytes), stream) == 0
+    torch.cuda.synchronize()
+    assert (ok.cpu().numpy() == POISON).all()
+    assert fn(*head, sz(n), p(ok), p(ws), sz(ws_bytes), stream) == 0, L.dsv_last_error().decode()
+    torch.cuda.synchronize()
+    assert ok.cpu().numpy().tolist() == [0, 0, 0]
+    assert L.dsv_keyset_destroy(h) == 0
+
+
 # ---- lifetime ---------------------------------------------------------------------------------------------
 def test_lifetime(engine):
     b1 = _batch(engine, "single", 37, 4099)
