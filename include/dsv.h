@@ -650,6 +650,67 @@ int dsv_verify_keyed_mont_dev(const dsv_keyset *ks, const void *u, const void *R
 int dsv_verify_keyed_mont_cols(const dsv_keyset *ks, const dsv_column *cols /*[4|5]*/, size_t n, uint8_t *ok);
 int dsv_verify_keyed_mont_cols_submit(const dsv_keyset *ks, const dsv_column *cols /*[4|5]*/, size_t n, uint8_t *ok,
                                       dsv_job **job);
+/* ---- key sets by key VALUE: look the keys up on the device, closed-set verify ----------
+ * Callers hold (signature, public key, message) triples, not indices.  Every key set carries an index over its
+ * own keys — built by all three constructors behind the tables, in a device allocation of its own:
+ * dsv_keyset_bytes and dsv_keyset_info's `bytes` do not count it, dsv_keyset_index_bytes(scheme, k) does (no GPU
+ * needed; 0 for an unknown scheme or k = 0) = the keys' canonical affine bytes (64 B per point, key-major, rounded
+ * up to 256) + an open-addressing table of `cap` uint32 slots (rounded up to 256), cap = the smallest power of two
+ * >= max(64, 2k), linear probing from a home slot (dsv_debug_keyset_home_slot; an unsalted hash of the key's
+ * 32-bit words) that wraps.  A match is always a comparison of all the key's bytes; the hash only picks where the
+ * walk starts, and no walk is longer than the number of registered keys plus one.
+ *   Keys        key_a = PK (64 B affine u || v per item), key_b = PK' (double) / Gen (var-generator); key_b is
+ *               ignored and may be NULL for a single set.
+ *   Lookup      key_idx_out[i] = the LOWEST index of a VALID registered key (dsv_keyset_key_ok: 1) whose bytes
+ *               equal item i's key bytes, else DSV_KEY_NONE.  A key registered but invalid never matches, nor do
+ *               other encodings of a registered key's residues (u + q), its negation, or a registered PK paired
+ *               with another key's second point.  misses (may be NULL): _dev form one 4-byte-aligned uint32 on
+ *               the set's device, zeroed on the stream and then SET to the number of DSV_KEY_NONE items; host
+ *               form a size_t.
+ *   Verify      ok[i] = [item i's key bytes are those of a valid registered key] & (the unkeyed entry point's
+ *               verdict on (u, R[, R'], key, m)) = dsv_verify_*_keyed_dev's verdict at the looked-up index, and 0
+ *               on a miss (DSV_KEY_NONE >= k reads no table).  A MISS IS A REJECTION, NOT AN ERROR: this is verify
+ *               against a closed set — a signature under a key that is not in the set does not pass, however
+ *               valid it is under its own key.  The set carries its scheme: one entry point per residency; Rp_uv
+ *               is required for a double set and ignored otherwise.
+ *   _dev forms  the checks of the keyed _dev calls in their order: a dead set DSV_ERR_NOT_INITIALIZED; n = 0
+ *               DSV_OK with nothing enqueued; a NULL pointer with n > 0 (key_b of a two-point set included), a
+ *               short workspace, outputs that are not on the set's device: DSV_ERR_INVALID_ARGUMENT, nothing
+ *               launched, `ok` untouched.  Enqueue-only on `stream`, never synchronise, may be captured: the
+ *               lookup, the challenge hash, the keyed kernel — three kernel launches, in front of them one 4-byte
+ *               memset node when `misses` is given; on an empty set (k = 0) two fills stand in for the lookup
+ *               kernel (every index DSV_KEY_NONE, misses = n).
+ *   Alignment   the lookup kernel reads a key in 16-byte loads: the device key columns must be 16-byte aligned
+ *               (DSV_ERR_INVALID_ARGUMENT otherwise, nothing launched); key_idx_out and misses 4-byte aligned.
+ *               The host forms stage the columns themselves and accept any alignment.
+ *   Workspace   dsv_keyed_lookup_workspace_bytes(n) = the index column (4 B per item, rounded up to 256) +
+ *               dsv_keyed_workspace_bytes(n); device, 256-byte aligned; no GPU needed.
+ *   Host forms  take host arrays, stage in chunks on the key set's device and block.
+ *   Before dsv_init there is no handle to give: a call of this group with a NULL handle then returns
+ *   DSV_ERR_NOT_INITIALIZED (afterwards a NULL handle is DSV_ERR_INVALID_ARGUMENT, as for every keyed call). */
+#define DSV_KEY_NONE 0xFFFFFFFFu
+size_t dsv_keyset_index_bytes(int scheme, size_t k);
+int dsv_keyset_lookup_dev(const dsv_keyset *ks, const void *key_a, const void *key_b, size_t n, void *key_idx_out,
+                          void *misses, void *stream);
+int dsv_keyset_lookup(const dsv_keyset *ks, const uint8_t *key_a, const uint8_t *key_b, size_t n,
+                      uint32_t *key_idx_out, size_t *misses);
+size_t dsv_keyed_lookup_workspace_bytes(size_t n);
+int dsv_verify_keyed_lookup_dev(const dsv_keyset *ks, const void *u, const void *R_uv,
+                                const void *Rp_uv /* double only, else NULL */, const void *key_a,
+                                const void *key_b /* NULL for single */, const void *m, size_t n, void *ok,
+                                void *workspace, size_t workspace_bytes, void *stream, void *misses);
+int dsv_verify_keyed_lookup(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *Rp_uv,
+                            const uint8_t *key_a, const uint8_t *key_b, const uint8_t *m, size_t n, uint8_t *ok,
+                            size_t *misses);
+/* introspection: the home slot of a key in the index of a set of k keys (no GPU needed; all ones for an unknown
+ * scheme, k = 0 or a NULL key): with words = the 32-bit little-endian words of key_a, then those of key_b,
+ *   h = 0;  for w in words: h = (h ^ w) * 0x9E3779B1;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;
+ *   h *= 0xC2B2AE35;  h ^= h >> 16   (mod 2^32);  home = h & (cap - 1) */
+uint64_t dsv_debug_keyset_home_slot(int scheme, size_t k, const uint8_t *key_a, const uint8_t *key_b);
+/* introspection: out[0] = capacity, [1] = occupied slots (= distinct valid keys), [2] = occupied slots whose key
+ * is not in its home slot, [3] = the longest probe of a registered key (slots read to find it; 1 = at home);
+ * all 0 for an empty set */
+int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

@@ -67,12 +67,17 @@ SYMBOLS = [
     # keyed typed-object form: the reference's in-memory objects against a registered key set
     "dsv_keyset_create_mont_cols", "dsv_keyed_mont_workspace_bytes", "dsv_verify_keyed_mont_dev",
     "dsv_verify_keyed_mont_cols", "dsv_verify_keyed_mont_cols_submit",
+    # key sets by key value: the index over a set's keys, lookup, closed-set verify
+    "dsv_keyset_index_bytes", "dsv_keyset_lookup_dev", "dsv_keyset_lookup", "dsv_keyed_lookup_workspace_bytes",
+    "dsv_verify_keyed_lookup_dev", "dsv_verify_keyed_lookup", "dsv_debug_keyset_home_slot",
+    "dsv_debug_keyset_index_stats",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
                  "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes",
                  "dsv_keyset_bytes", "dsv_keyed_workspace_bytes", "dsv_keyed_rlc_workspace_bytes",
-                 "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes")
+                 "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes",
+                 "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes")
 
 
 class Column(ctypes.Structure):
@@ -119,9 +124,12 @@ def load():
     L.dsv_keyed_wire_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_keyed_mont_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_keyed_rlc_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
+    L.dsv_keyset_index_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.dsv_debug_keyset_home_slot.restype = ctypes.c_uint64
+    L.dsv_debug_keyset_home_slot.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
-        if name not in ("dsv_version", "dsv_last_error") + _SIZE_T_FUNCS:
+        if name not in ("dsv_version", "dsv_last_error", "dsv_debug_keyset_home_slot") + _SIZE_T_FUNCS:
             fn.restype = ctypes.c_int
     _lib = L
     return L

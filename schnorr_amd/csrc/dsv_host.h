@@ -10,6 +10,7 @@
 //   dsv_rlc.hip       the batch fast accept: control of k_rlc.hip, every *_rlc entry point
 //   dsv_inputs.hip    signing / key derivation / StdRng inputs (input generation), debug probes
 //   dsv_keyset.hip    registered key sets: per-key tables, verify by key index (keyed.h)
+//   dsv_keyed_lookup.hip  key sets by key value: the index over a set's keys, lookup, closed-set verify (keyed_lookup.h)
 // The host pipeline itself (run_pipelined, run_multi) is a template: dsv_pipeline.h.
 // Nothing here is part of the C ABI (include/dsv.h); everything lives in namespace dsvh.
 #pragma once

@@ -16,12 +16,20 @@ std::vector<dsv_keyset*> g_keysets;
 constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
 constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
 
+// the tables and the index of a set (its device selected)
+void free_device_memory(dsv_keyset* ks) {
+  if (ks->tables) (void)hipFree(ks->tables);
+  if (ks->index) (void)hipFree(ks->index);
+  ks->tables = nullptr;
+  ks->key_ok = nullptr;
+  ks->index = nullptr;
+  ks->slots = nullptr;
+}
+
 void free_sets_of(int device) {  // (exclusive lock held)
   for (dsv_keyset* ks : g_keysets) {
     if (ks->device != device || !ks->alive) continue;
-    if (ks->tables) (void)hipFree(ks->tables);
-    ks->tables = nullptr;
-    ks->key_ok = nullptr;
+    free_device_memory(ks);
     ks->alive = false;
   }
 }
@@ -49,17 +57,24 @@ int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_
     ks->key_ok = reinterpret_cast<uint8_t*>(ks->tables) + keyset_table_bytes(scheme, k);
     launch_build_key_tables(P0, P1, valid_in, keyset_points(scheme), k, ks->tables, ks->key_ok, s);
     HIP_TRY(hipGetLastError());
+    // the index over the keys' bytes, behind the table build (it reads key_ok)
+    HIP_TRY(hipMalloc(&ks->index, keyset_index_total_bytes(scheme, k)));
+    ks->slots = reinterpret_cast<uint32_t*>(ks->index + keyset_index_keys_bytes(scheme, k));
+    ks->slot_mask = keyset_index_cap(k) - 1;
+    HIP_TRY(launch_build_key_index(P0, P1, ks->key_ok, keyset_points(scheme), k, ks->index, ks->slots,
+                                   ks->slot_mask, s));
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return DSV_OK;
   }();
   std::unique_lock<std::shared_mutex> lk(g_ks_mu);
   if (rc == DSV_OK && !ctx.ready.load(std::memory_order_acquire)) {
-    if (ks->tables) (void)hipFree(ks->tables);
+    free_device_memory(ks);
     delete ks;
     return fail(DSV_ERR_NOT_INITIALIZED, "device %d was shut down", ctx.device);
   }
   if (rc != DSV_OK) {
-    if (ks->tables) (void)hipFree(ks->tables);
+    free_device_memory(ks);
     delete ks;
     return rc;
   }
@@ -254,7 +269,7 @@ int dsv_keyset_destroy(dsv_keyset* ks) {
     DeviceGuard guard(ks->device);
     if (guard.err != hipSuccess) rc = fail(DSV_ERR_HIP, "cannot select device %d", ks->device);
     (void)hipDeviceSynchronize();  // work in flight may still read the tables
-    (void)hipFree(ks->tables);
+    free_device_memory(ks);
   }
   delete ks;
   return rc;

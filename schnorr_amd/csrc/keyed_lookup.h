@@ -1,0 +1,68 @@
+// keyed_lookup.h — the index of a registered key set over its own keys (dsv_keyset_lookup*,
+// dsv_verify_keyed_lookup*, include/dsv.h): what turns the key COLUMNS of a batch — the
+// canonical affine bytes callers hold — into the key_idx column every keyed entry point takes.
+//
+// One device allocation per set, apart from the tables (keyed.h):
+//   keys   np * 64 B per key, key-major (PK | PK' for the double scheme, PK | Gen for the var-generator
+//          scheme), the bytes the set was built from; rounded up to 256 B
+//   slots  `cap` uint32, open addressing: a slot holds a key index or kSlotEmpty; cap = the smallest power
+//          of two >= max(64, 2k), so the table is at most half full; rounded up to 256 B
+// Only keys with key_ok == 1 are inserted (their bytes are canonical: every coordinate < q), equal keys share
+// one slot that holds the lowest of their indices.  Probing is linear from the key's home slot and wraps.
+// The hash picks the home slot only: a match is always a comparison of all np * 64 bytes.  It is not salted —
+// whoever registers the keys chooses the clusters — and no probe sequence is longer than the number of
+// distinct valid keys plus one (the table is never full, and a probe stops at the first empty slot).
+#pragma once
+#include "keyed.h"
+
+namespace dsv {
+
+constexpr uint32_t kSlotEmpty = 0xffffffffu;  // also the index of a miss (DSV_KEY_NONE)
+constexpr int kLookupBlock = 256;
+constexpr unsigned kMaxLookupGrid = 4096;
+
+inline size_t lookup_round256(size_t x) { return (x + 255) / 256 * 256; }
+// slots of a set of k keys (k < 2^32: at most 2^33)
+inline size_t keyset_index_cap(size_t k) {
+  size_t cap = 64;
+  while (cap < 2 * k) cap <<= 1;
+  return cap;
+}
+inline size_t keyset_index_keys_bytes(int scheme, size_t k) {
+  return lookup_round256((size_t)keyset_points(scheme) * 64 * k);
+}
+inline size_t keyset_index_total_bytes(int scheme, size_t k) {
+  return k ? keyset_index_keys_bytes(scheme, k) + lookup_round256(4 * keyset_index_cap(k)) : 0;
+}
+
+// the hash of a key's 16 * np little-endian words; home slot = hash & (cap - 1)
+struct KeyHash {
+  uint32_t h = 0;
+  __host__ __device__ void word(uint32_t w) { h = (h ^ w) * 0x9E3779B1u; }
+  __host__ __device__ uint32_t finish() const {
+    uint32_t x = h;
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+  }
+};
+
+// ---- k_keyed_lookup.hip ------------------------------------------------------------------------
+// The index of k keys from the affine points P0 / P1 (null for one-point keys) the tables were built from
+// and the table build's key_ok (earlier on `s`): copies the key bytes into `keys` and inserts the valid keys
+// into `slots` (mask + 1 of them, a power of two; filled with kSlotEmpty on `s` by this launcher first).  One
+// lane per key.  The first error of the fill, if any, is returned; the launch's own surfaces through
+// hipGetLastError() like every launcher's.
+hipError_t launch_build_key_index(const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints,
+                                  size_t k, uint8_t* keys, uint32_t* slots, size_t mask, hipStream_t s);
+// key_idx[i] = the index in the slot of item i's key bytes (key_a[i] | key_b[i], 64 B each, 16-byte aligned;
+// key_b null for one-point keys), else kSlotEmpty; misses (may be null): zeroed on `s`, then the number of
+// items that got kSlotEmpty.  One lane per item, grid-stride.
+hipError_t launch_key_lookup(const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
+                             const uint8_t* keys, const uint32_t* slots, size_t mask, uint32_t* key_idx,
+                             uint32_t* misses, hipStream_t s);
+
+}  // namespace dsv

@@ -4,6 +4,7 @@
 #include <shared_mutex>
 
 #include "dsv_host.h"
+#include "keyed_lookup.h"
 #include "keyed_wire.h"
 
 struct dsv_keyset {
@@ -13,6 +14,10 @@ struct dsv_keyset {
   size_t bytes = 0;
   uint32_t* tables = nullptr;  // one allocation: the tables, then key_ok
   uint8_t* key_ok = nullptr;
+  // the index over the set's own keys (keyed_lookup.h), an allocation of its own: the keys' bytes, then the slots
+  uint8_t* index = nullptr;
+  uint32_t* slots = nullptr;
+  size_t slot_mask = 0;  // capacity - 1
   bool alive = false;
 };
 

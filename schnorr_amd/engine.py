@@ -894,6 +894,39 @@ def keyed_mont_workspace_bytes(scheme, n):
     return int(_lib.load().dsv_keyed_mont_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
 
 
+def keyset_index_bytes(scheme, k):
+    """dsv_keyset_index_bytes: device bytes of the index over a key set's own keys (KeySet.lookup; no GPU needed);
+    not part of keyset_bytes"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyset_index_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
+
+
+def keyed_lookup_workspace_bytes(n):
+    """dsv_keyed_lookup_workspace_bytes: device bytes of KeySet.verify_lookup_dev's workspace (no GPU needed)"""
+    return int(_lib.load().dsv_keyed_lookup_workspace_bytes(ctypes.c_size_t(n)))
+
+
+KEY_NONE = 0xFFFFFFFF  # DSV_KEY_NONE: the index of a key that is not in the set
+
+
+def keyset_home_slot(scheme, k, key_a, key_b=None):
+    """dsv_debug_keyset_home_slot: where the probe for a key (64 bytes per point) starts in the index of a set of
+    k keys (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    if (key_b is None) != (scheme == "single"):
+        raise ValueError("scheme %s takes %s" % (scheme, "key_a only" if scheme == "single" else "key_a and key_b"))
+    a = _arr(key_a, 64)
+    b = _arr(key_b, 64) if key_b is not None else None
+    if a.shape[0] != 1 or (b is not None and b.shape[0] != 1):
+        raise ValueError("one key at a time")
+    return int(_lib.load().dsv_debug_keyset_home_slot(
+        ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k), _p(a), _p(b) if b is not None else ctypes.c_void_p(0)))
+
+
 def _keyed_mont_widths(scheme):
     """widths of a keyed typed batch's columns: u, R[, R'], key_idx, m"""
     return [32] + [96] * (2 if scheme == "double" else 1) + [4, 32]
@@ -967,6 +1000,9 @@ class KeySet:
         ok = ks.verify_mont_cols([u, R96, idx, m])            # views into `Signature*` objects, where they lie
         job = ks.submit_mont_cols([u, R96, idx, m]); ok = job.wait()
         ks.verify_mont_dev(u, R96, idx, m, ok, workspace)     # CUDA tensors of limbs
+        idx, misses = ks.lookup(PK)                # by key VALUE: uint32 [n], KEY_NONE where PK is not in the set
+        ok, misses = ks.verify_lookup(u, R, PK, m) # closed-set verify; double: (u, R, Rp, PK, PKp, m); vargen:
+        ks.verify_lookup_dev(u, R, PK, m, ok, workspace)      # (u, R, PK, Gen, m)
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None):
@@ -1168,3 +1204,101 @@ class KeySet:
             self._handle(), _tp(u, 32), _tp(pts[0], 96), _tp(pts[1], 96) if len(pts) == 2 else ctypes.c_void_p(0),
             ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
             _stream_ptr(stream, dev)))
+
+    # ---- by key value: the index over the set's own keys -----------------------------------------------------
+    def _key_cols(self, keys, what):
+        """(key_a[, key_b]) by scheme"""
+        want = 1 if self.scheme == "single" else 2
+        if len(keys) != want:
+            raise ValueError("%s key set: %s takes %s" % (
+                self.scheme, what, "key_a" if want == 1 else "key_a and key_b (PK' / Gen)"))
+        return list(keys)
+
+    def index_stats(self):
+        """dsv_debug_keyset_index_stats: dict(capacity, occupied, displaced, longest_probe) of the set's index"""
+        out = (ctypes.c_uint64 * 4)()
+        _lib.check(_lib.load().dsv_debug_keyset_index_stats(self._handle(), out))
+        return dict(zip(("capacity", "occupied", "displaced", "longest_probe"), (int(v) for v in out)))
+
+    def lookup(self, *keys):
+        """host arrays key_a [n, 64] (two-point sets: key_a, key_b) -> (idx uint32 [n], misses): the lowest index of
+        a valid registered key with these bytes, KEY_NONE where there is none"""
+        cols = [_arr(c, 64) for c in self._key_cols(keys, "lookup")]
+        n = _same_n(*cols)
+        idx = np.zeros(n, dtype=np.uint32)
+        misses = ctypes.c_size_t()
+        _lib.check(_lib.load().dsv_keyset_lookup(
+            self._handle(), _p(cols[0]), _p(cols[1]) if len(cols) == 2 else ctypes.c_void_p(0), ctypes.c_size_t(n),
+            _p(idx), ctypes.byref(misses)))
+        return idx, misses.value
+
+    @staticmethod
+    def _key_ptr(t, name):
+        """a key column of the _dev forms: uint8 [n, 64], 16-byte aligned (the lookup reads it in 16-byte loads)"""
+        if _t(t, 64, name).data_ptr() % 16:
+            raise ValueError("%s: key columns must be 16-byte aligned" % name)
+        return ctypes.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _misses_ptr(misses, dev):
+        if misses is None:
+            return ctypes.c_void_p(0)
+        return _idx(misses, 1, dev, "misses")
+
+    def lookup_dev(self, *args, misses=None, stream=None):
+        """CUDA tensors (key_a[, key_b], idx_out): idx_out int32 [n], written as uint32 (KEY_NONE = -1); misses
+        (optional): a 32-bit CUDA tensor whose first element is set to the number of KEY_NONE items.  Enqueued on
+        `stream` (default: torch's current stream of the batch's device); does not synchronise."""
+        if len(args) < 1:
+            raise ValueError("lookup_dev takes the key columns, then idx_out")
+        cols, out = self._key_cols(args[:-1], "lookup_dev"), args[-1]
+        n, dev = _rows(*zip(cols, [64] * len(cols), ["key_a", "key_b"]))
+        op = _idx(out, n, dev, "idx_out")
+        if out.dim() != 1 or out.shape[0] != n:
+            raise ValueError("idx_out: expected [n] = [%d], got %r" % (n, tuple(out.shape)))
+        _lib.check(_lib.load().dsv_keyset_lookup_dev(
+            self._handle(), self._key_ptr(cols[0], "key_a"),
+            self._key_ptr(cols[1], "key_b") if len(cols) == 2 else ctypes.c_void_p(0), ctypes.c_size_t(n), op, self._misses_ptr(misses, dev), _stream_ptr(stream, dev)))
+
+    def _by_value(self, args, what):
+        """(u, R[, Rp], key_a[, key_b], m) split by scheme -> u, nonce points, key columns, m"""
+        ns, nk = (2 if self.scheme == "double" else 1), (1 if self.scheme == "single" else 2)
+        if len(args) != 2 + ns + nk:
+            raise ValueError("%s key set: %s takes (%s)" % (
+                self.scheme, what, ", ".join(_SCHEMES[self.scheme][0])))
+        return args[0], list(args[1:1 + ns]), list(args[1 + ns:-1]), args[-1]
+
+    def verify_lookup(self, *args):
+        """Closed-set verify by key value (dsv_verify_keyed_lookup): host arrays (u, R, PK, m) — double (u, R, Rp,
+        PK, PKp, m), vargen (u, R, PK, Gen, m), the unkeyed entry points' arguments — -> (verdicts [n], misses).
+        An item whose key is not a valid registered key of the set is rejected."""
+        u, pts, keys, m = self._by_value(args, "verify_lookup")
+        u, m = _arr(u, 32), _arr(m, 32)
+        pts, keys = [_arr(p, 64) for p in pts], [_arr(c, 64) for c in keys]
+        n = _same_n(u, m, *pts, *keys)
+        ok = np.zeros(n, dtype=np.uint8)
+        misses = ctypes.c_size_t()
+        null = ctypes.c_void_p(0)
+        _lib.check(_lib.load().dsv_verify_keyed_lookup(
+            self._handle(), _p(u), _p(pts[0]), _p(pts[1]) if len(pts) == 2 else null, _p(keys[0]),
+            _p(keys[1]) if len(keys) == 2 else null, _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
+        return ok, misses.value
+
+    def verify_lookup_dev(self, *args, misses=None, stream=None):
+        """CUDA tensors (u, R[, Rp], key_a[, key_b], m, ok, workspace): verify_lookup's verdicts into ok, enqueued
+        on `stream` (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
+        keyed_lookup_workspace_bytes(n) bytes; misses as for lookup_dev."""
+        if len(args) < 2:
+            raise ValueError("verify_lookup_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, keys, m = self._by_value(args[:-2], "verify_lookup_dev")
+        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
+        n, dev = _rows(*zip([u] + pts + keys + [m], [32] + [64] * (len(pts) + len(keys)) + [32], names))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_lookup_workspace_bytes(n), dev, "workspace")
+        null = ctypes.c_void_p(0)
+        _lib.check(_lib.load().dsv_verify_keyed_lookup_dev(
+            self._handle(), _tp(u, 32), _tp(pts[0], 64), _tp(pts[1], 64) if len(pts) == 2 else null,
+            self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
+            ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
