@@ -711,6 +711,38 @@ uint64_t dsv_debug_keyset_home_slot(int scheme, size_t k, const uint8_t *key_a, 
  * is not in its home slot, [3] = the longest probe of a registered key (slots read to find it; 1 = at home);
  * all 0 for an empty set */
 int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
+/* ---- key sets as a key cache: open-set verify by key value -----------------------------
+ * The caller that verifies (signature, public key, message) triples as they arrive, most under a few busy keys
+ * and some under keys it has never seen.  Same arguments as dsv_verify_keyed_lookup[_dev]; what differs is what a
+ * miss means:
+ *   Verify      ok[i] = what dsv_verify_single_dev / dsv_verify_double_dev writes for the same columns, for every
+ *               input.  An item whose key bytes are those of a valid registered key is decided by that key's
+ *               tables; every other item (an unregistered key, a registered but invalid one, another encoding of
+ *               a registered key) is decided by the unkeyed equation, in the same call.  Registering a key changes
+ *               how fast a verdict arrives and never the verdict.  misses: as for the closed-set call — the number
+ *               of items that took the unkeyed path.
+ *   Schemes     single and double sets; a var-generator set is DSV_ERR_INVALID_ARGUMENT (nothing launched).
+ *   _dev form   checks, error codes and alignment rules of dsv_verify_keyed_lookup_dev.  Enqueue-only on `stream`,
+ *               one straight chain, never synchronises, may be captured: the lookup, the challenge hash over all n
+ *               (once, for both paths), the keyed kernel over all n (a miss reads no table and gets 0), a 4-byte
+ *               memset node and the miss list (the positions of the DSV_KEY_NONE items, one atomic per wave), and
+ *               the unkeyed equation over that list, which overwrites the 0 of exactly the listed items.  The last
+ *               launch is sized for n items and reads the list's length on the device: a workgroup past the end
+ *               returns at once, so the host never learns the number of misses.  An empty set (k = 0): every
+ *               item takes the unkeyed path.
+ *   Workspace   dsv_keyed_open_workspace_bytes(n) = dsv_keyed_lookup_workspace_bytes(n) + the miss list (4 B per
+ *               item, rounded up to 256) + 256 (its length) + the unkeyed kernel's per-lane window tables
+ *               (min(ceil(n / 64), 4096) * 64 lanes * 3888 B); device, 256-byte aligned; no GPU needed.
+ *   Host form   host arrays, staged in chunks of 2^18 items on the key set's device; blocks; *misses is the sum
+ *               over the chunks. */
+size_t dsv_keyed_open_workspace_bytes(size_t n);
+int dsv_verify_keyed_open_dev(const dsv_keyset *ks, const void *u, const void *R_uv,
+                              const void *Rp_uv /* double only, else NULL */, const void *key_a,
+                              const void *key_b /* NULL for single */, const void *m, size_t n, void *ok,
+                              void *workspace, size_t workspace_bytes, void *stream, void *misses);
+int dsv_verify_keyed_open(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *Rp_uv,
+                          const uint8_t *key_a, const uint8_t *key_b, const uint8_t *m, size_t n, uint8_t *ok,
+                          size_t *misses);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

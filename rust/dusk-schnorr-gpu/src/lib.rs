@@ -81,6 +81,17 @@ extern "C" {
     fn dsv_verify_keyed_mont_cols(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8) -> c_int;
     fn dsv_verify_keyed_mont_cols_submit(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8,
                                          job: *mut *mut c_void) -> c_int;
+    // key sets as a key cache (include/dsv.h, "open-set verify by key value"): canonical affine bytes (u, m 32 B;
+    // points 64 B), single and double sets.  The unkeyed verdicts for every input; an item under a valid
+    // registered key is decided by the key's tables, every other item by the unkeyed equation in the same call.
+    // Raw exports: nothing in this crate holds canonical affine columns yet.
+    pub fn dsv_keyed_open_workspace_bytes(n: usize) -> usize;
+    pub fn dsv_verify_keyed_open_dev(ks: *const c_void, u: *const c_void, r_uv: *const c_void, rp_uv: *const c_void,
+                                     key_a: *const c_void, key_b: *const c_void, m: *const c_void, n: usize,
+                                     ok: *mut c_void, workspace: *mut c_void, workspace_bytes: usize,
+                                     stream: *mut c_void, misses: *mut c_void) -> c_int;
+    pub fn dsv_verify_keyed_open(ks: *const c_void, u: *const u8, r_uv: *const u8, rp_uv: *const u8, key_a: *const u8,
+                                 key_b: *const u8, m: *const u8, n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.

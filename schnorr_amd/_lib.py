@@ -71,13 +71,15 @@ SYMBOLS = [
     "dsv_keyset_index_bytes", "dsv_keyset_lookup_dev", "dsv_keyset_lookup", "dsv_keyed_lookup_workspace_bytes",
     "dsv_verify_keyed_lookup_dev", "dsv_verify_keyed_lookup", "dsv_debug_keyset_home_slot",
     "dsv_debug_keyset_index_stats",
+    # key sets as a key cache: open-set verify by key value (misses take the unkeyed equation in the same call)
+    "dsv_keyed_open_workspace_bytes", "dsv_verify_keyed_open_dev", "dsv_verify_keyed_open",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
                  "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes",
                  "dsv_keyset_bytes", "dsv_keyed_workspace_bytes", "dsv_keyed_rlc_workspace_bytes",
                  "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes",
-                 "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes")
+                 "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes", "dsv_keyed_open_workspace_bytes")
 
 
 class Column(ctypes.Structure):

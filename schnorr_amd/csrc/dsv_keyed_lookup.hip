@@ -6,9 +6,6 @@
 #include "keyset_host.h"
 
 namespace dsvh {
-namespace {
-
-constexpr size_t kLookupHostChunk = (size_t)1 << 18;
 
 // a call without a handle before dsv_init: there is no handle to give yet, so it is told that nothing is up
 // (a handle, live or dead, goes through check_set like every keyed call)
@@ -52,6 +49,8 @@ int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, s
   HIP_TRY(hipGetLastError());
   return DSV_OK;
 }
+
+namespace {
 
 uint32_t home_hash_host(int np, const uint8_t* key_a, const uint8_t* key_b) {
   KeyHash h;

@@ -1,0 +1,154 @@
+// k_keyed_open.hip — the miss branch of the open-set verify by key value (keyed_open.h): the list of the items
+// whose key the lookup did not find, and the unkeyed equation of k_verify_fixed_half (k_verify.hip) over that
+// list.
+#include "common.h"
+#include "halfgcd.h"
+#include "keyed_open.h"
+
+namespace dsv {
+
+// ------------------------------------------------------------------------------------------
+// One lane per item, grid-stride in whole waves (every lane of a wave makes the same number of trips, so the
+// ballot sees all 64): a wave that holds misses reserves their places with ONE atomic, a lane's place is the
+// reserved base plus the number of misses in the lanes below it.  At most n places are ever reserved.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kMissBlock)
+k_miss_list(const u32* __restrict__ key_idx, size_t n, u32* __restrict__ list, u32* __restrict__ count) {
+  const u32 lane = threadIdx.x & (u32)(warpSize - 1);
+#pragma unroll 1
+  for (size_t base = (size_t)blockIdx.x * kMissBlock + (threadIdx.x - lane); base < n;
+       base += (size_t)gridDim.x * kMissBlock) {
+    const size_t i = base + lane;
+    const bool miss = i < n && key_idx[i] == kSlotEmpty;
+    const unsigned long long wave = __ballot(miss);
+    if (wave == 0) continue;
+    u32 first = 0;
+    if (lane == (u32)__builtin_ctzll(wave)) first = atomicAdd(count, (u32)__popcll(wave));
+    first = __shfl(first, __builtin_ctzll(wave));
+    if (miss) list[first + (u32)__popcll(wave & ((1ull << lane) - 1ull))] = (u32)i;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The verdict of item i: valid[i] & [every chain's equation holds]; tbl: the lane's window table.  This is the
+// body of k_verify_fixed_half's loop (k_verify.hip, where the method is described), statement for statement, and
+// it is a COPY on purpose: with the body moved into a forced-inline function that both kernels call, the
+// compiled k_verify_fixed_half<1> and <2> came out with another register allocation (same budget, other
+// instruction text), and the headline kernel is not to change for this one.  A change to either
+// body belongs in both.
+// ------------------------------------------------------------------------------------------
+template <int NCHAIN>
+DSV_DEV bool listed_item_ok(const uint8_t* u, const uint8_t* c, const ChainOperands& op0, const ChainOperands& op1,
+                            const uint8_t* valid, size_t i, u32* tbl) {
+  bool good = valid[i] != 0;
+  u32 ya[8], yb[8], w[8];
+  bool b_neg;
+  int top;
+  {
+    u32 cs[8], a[8], b[8];
+    load_words8(cs, c, i);
+    half_scalars(a, b, b_neg, cs);
+    // signed 2-bit digits of a and |b| (the sign of the R term goes into the point: -R below)
+    recode_signed2(ya, a);
+    recode_signed2(yb, b);
+    u32 nz[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) nz[k] = (ya[k] ^ 0x55555555u) | (yb[k] ^ 0x55555555u);
+    top = top_digit2(nz);
+    u32 us[8];
+    load_words8(us, u, i);
+    const bool u_ok = words_lt(us, kR32);
+    good &= u_ok;
+    if (!u_ok) us[7] &= 0x0fffffffu;  // keep fr_mul's inputs below r-ish; verdict is 0 anyway
+    fr_mul(w, b, us);                 // |b| * u mod r
+    if (b_neg) {                      // (b*u) mod r with b < 0
+      const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      u32 t[8];
+      fr_sub(t, zero, w);
+#pragma unroll
+      for (int k = 0; k < 8; k++) w[k] = t[k];
+    }
+  }
+#pragma unroll 1
+  for (int h = 0; h < NCHAIN; h++) {
+    const ChainOperands op = h ? op1 : op0;
+    {
+      Fe pku, pkv, ru, rv;
+      good &= load_fq(pku, op.PK_uv, 2 * i);
+      good &= load_fq(pkv, op.PK_uv, 2 * i + 1);
+      good &= load_fq_signed(ru, op.R_uv, 2 * i, !b_neg);  // the chain adds -|b| * R unless b < 0
+      good &= load_fq(rv, op.R_uv, 2 * i + 1);
+      build_joint_table(tbl, pku, pkv, ru, rv);
+    }
+    // T = a*PK + |b|*(-+R) (+ w*G below): one joint entry per 2-bit window, loaded one window ahead
+    Ext acc = ext_from_niels(load_var_entry(tbl, joint_digit(ya, yb, top)));
+    {
+      RawNiels e = load_var_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
+#pragma unroll 1
+      for (int k = top - 1; k >= 0; k--) {
+        acc = ext_mul4(acc);
+        const Niels cur = finish_var_entry(e);
+        e = load_var_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
+        acc = ext_add_niels(acc, cur);
+      }
+    }
+    // T + w*G == O  (T == O  <=>  u == 0 and v == z, decided inside the last addition)
+    good &= fixed_base_accumulate_is_identity(acc, w, op.table);
+  }
+  return good;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_verify_fixed_half over list[0 .. min(*count, n)): lane j verifies item list[j] — every column at that row —
+// and overwrites its verdict; the per-lane window tables are addressed by workgroup and lane as there.  The
+// launch is sized for n items: a workgroup past the end of the list returns before it touches anything else.
+// ------------------------------------------------------------------------------------------
+template <int NCHAIN>
+__global__ void __launch_bounds__(kVerifyBlock, kWavesVerify)
+k_verify_listed(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c, ChainOperands op0, ChainOperands op1,
+                const uint8_t* __restrict__ valid, size_t n, uint8_t* __restrict__ ok,
+                u32* __restrict__ var_tables, const u32* __restrict__ list, const u32* __restrict__ count) {
+  size_t listed = *count;
+  if (listed > n) listed = n;
+  if ((size_t)blockIdx.x * kVerifyBlock >= listed) return;
+  u32* tbl = var_tables + ((size_t)blockIdx.x * kVerifyBlock + threadIdx.x) * kJointLaneWords;
+#pragma unroll 1
+  for (size_t base = (size_t)blockIdx.x * kVerifyBlock; base < listed;
+       base += (size_t)gridDim.x * kVerifyBlock) {
+    const size_t j = base + threadIdx.x;
+    const u32 i = j < listed ? list[j] : kSlotEmpty;  // the list is only ever dereferenced where k_miss_list wrote it
+    if (i >= n) continue;                             // (n <= DSV_MAX_BATCH = 2^28: kSlotEmpty is no row)
+    const bool good = listed_item_ok<NCHAIN>(u, c, op0, op1, valid, i, tbl);
+    // The row is read from the list AGAIN for the store, through a lane number the compiler cannot see through,
+    // so that it does not stay in a register across the window loop: the kernel this one mirrors rebuilds its
+    // row from the workgroup's base and the lane, this one has only the list — and with the row kept live it
+    // spilled more registers than k_verify_fixed_half (tests/test_keyset_open_abi.py).  Four bytes, an L2 hit.
+    u32 lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));
+    ok[list[base + lane]] = good ? 1 : 0;
+  }
+}
+
+hipError_t launch_miss_list(const uint32_t* key_idx, size_t n, uint32_t* list, uint32_t* count, hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(count, 0, 4, s);
+  if (e != hipSuccess) return e;
+  if (n == 0) return hipSuccess;
+  const unsigned g = grid_for(n, kMissBlock);
+  hipLaunchKernelGGL(k_miss_list, dim3(g < kMaxMissGrid ? g : kMaxMissGrid), dim3(kMissBlock), 0, s, key_idx, n,
+                     list, count);
+  return hipSuccess;
+}
+
+void launch_verify_listed(int nchain, const uint8_t* u, const uint8_t* c, ChainOperands op0, ChainOperands op1,
+                          const uint8_t* valid, size_t n, uint8_t* ok, uint32_t* var_tables, const uint32_t* list,
+                          const uint32_t* count, hipStream_t s) {
+  const dim3 grid(verify_grid(n)), block(kVerifyBlock);
+  if (nchain == 2)
+    hipLaunchKernelGGL(k_verify_listed<2>, grid, block, 0, s, u, c, op0, op1, valid, n, ok, var_tables, list,
+                       count);
+  else
+    hipLaunchKernelGGL(k_verify_listed<1>, grid, block, 0, s, u, c, op0, op1, valid, n, ok, var_tables, list,
+                       count);
+}
+
+}  // namespace dsv

@@ -5,6 +5,7 @@
 
 #include "dsv_host.h"
 #include "keyed_lookup.h"
+#include "keyed_open.h"
 #include "keyed_wire.h"
 
 struct dsv_keyset {
@@ -52,9 +53,11 @@ void enqueue_keyed(const Context& ctx, const dsv_keyset* ks, const Items& in, co
 //   prep(ctx, scheme, x, s, in, valid_in)   carves those bytes from x, enqueues the preparation launch on s, and
 //                         leaves the keyed call's items and the per-item verdicts its hash ANDs in (null: none);
 //                         a non-zero return ends the call with nothing more enqueued.
-template <class Null, class Bytes, class Prep>
+//   after(ctx, s, w)      (optional) enqueues on s what follows the keyed kernel; w: the c / valid the challenge
+//                         hash wrote (the open-set form's miss branch reads them).
+template <class Null, class Bytes, class Prep, class After>
 int run_keyed_dev(const dsv_keyset* ks, int scheme, Null inputs_null, Bytes cols_bytes, const void* idx, size_t n,
-                  void* ok, void* workspace, size_t workspace_bytes, void* stream, Prep prep) {
+                  void* ok, void* workspace, size_t workspace_bytes, void* stream, Prep prep, After after) {
   std::shared_lock<std::shared_mutex> rl(keyset_mutex());
   Context* cp = nullptr;
   if (int r = check_set(ks, scheme, n, cp)) return r;
@@ -70,9 +73,16 @@ int run_keyed_dev(const dsv_keyset* ks, int scheme, Null inputs_null, Bytes cols
   Items in;
   const uint8_t* valid_in = nullptr;
   if (int r = prep(ctx, scheme, x, s, in, valid_in)) return r;
-  enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, x.take(keyed_ws_bytes(n)), s, valid_in);
+  void* keyed_ws = x.take(keyed_ws_bytes(n));
+  enqueue_keyed(ctx, ks, in, (const uint32_t*)idx, n, (uint8_t*)ok, keyed_ws, s, valid_in);
   HIP_TRY(hipGetLastError());
-  return DSV_OK;
+  return after(ctx, s, carve(keyed_ws, n));
+}
+template <class Null, class Bytes, class Prep>
+int run_keyed_dev(const dsv_keyset* ks, int scheme, Null inputs_null, Bytes cols_bytes, const void* idx, size_t n,
+                  void* ok, void* workspace, size_t workspace_bytes, void* stream, Prep prep) {
+  return run_keyed_dev(ks, scheme, inputs_null, cols_bytes, idx, n, ok, workspace, workspace_bytes, stream, prep,
+                       [](const Context&, hipStream_t, const Workspace&) { return (int)DSV_OK; });
 }
 
 // One constructor call (dsv_keyset.hip), on the calling thread's current device: the checks in this order — null
@@ -106,5 +116,19 @@ KeyedCols carve_keyed_wire(Stager& x, int scheme, size_t n);
 // `stream`; a step of its own so that it can stand in front of the keyed fast accept as well
 void decode_keyed_wire(const Context& ctx, int scheme, const uint8_t* sig, size_t n, const Items& out, uint8_t* valid,
                        hipStream_t stream);
+
+// ---- the by-value forms (dsv_keyed_lookup.hip; dsv_keyed_open.hip builds on them) --------------------------
+constexpr size_t kLookupHostChunk = (size_t)1 << 18;  // items per chunk of the host forms
+// a call without a handle before dsv_init is told that nothing is up (a handle, live or dead, goes through
+// check_set like every keyed call)
+int library_up(const dsv_keyset* ks);
+bool keys_null(int scheme, const void* key_a, const void* key_b);
+// the lookup kernel reads a key in 16-byte loads
+int check_key_alignment(int scheme, const void* key_a, const void* key_b);
+// misses (may be null): a 4-byte-aligned word on the set's device (ctx: the set's context)
+int check_misses(const dsv_keyset* ks, const Context* ctx, const void* misses);
+// the lookup of n items on s; every pointer device memory of the set's device.  An empty set: everything misses.
+int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
+                   uint32_t* misses, hipStream_t s);
 
 }  // namespace dsvh

@@ -907,6 +907,11 @@ def keyed_lookup_workspace_bytes(n):
     return int(_lib.load().dsv_keyed_lookup_workspace_bytes(ctypes.c_size_t(n)))
 
 
+def keyed_open_workspace_bytes(n):
+    """dsv_keyed_open_workspace_bytes: device bytes of KeySet.verify_open_dev's workspace (no GPU needed)"""
+    return int(_lib.load().dsv_keyed_open_workspace_bytes(ctypes.c_size_t(n)))
+
+
 KEY_NONE = 0xFFFFFFFF  # DSV_KEY_NONE: the index of a key that is not in the set
 
 
@@ -1003,6 +1008,8 @@ class KeySet:
         idx, misses = ks.lookup(PK)                # by key VALUE: uint32 [n], KEY_NONE where PK is not in the set
         ok, misses = ks.verify_lookup(u, R, PK, m) # closed-set verify; double: (u, R, Rp, PK, PKp, m); vargen:
         ks.verify_lookup_dev(u, R, PK, m, ok, workspace)      # (u, R, PK, Gen, m)
+        ok, misses = ks.verify_open(u, R, PK, m)   # open-set verify (single, double): the unkeyed verdicts, a
+        ks.verify_open_dev(u, R, PK, m, ok, workspace)        # registered key only makes them arrive sooner
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None):
@@ -1298,6 +1305,43 @@ class KeySet:
         wsp = _bytes_out(workspace, keyed_lookup_workspace_bytes(n), dev, "workspace")
         null = ctypes.c_void_p(0)
         _lib.check(_lib.load().dsv_verify_keyed_lookup_dev(
+            self._handle(), _tp(u, 32), _tp(pts[0], 64), _tp(pts[1], 64) if len(pts) == 2 else null,
+            self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
+            ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
+
+    def verify_open(self, *args):
+        """Open-set verify by key value (dsv_verify_keyed_open; single and double sets): host arrays (u, R, PK, m) —
+        double (u, R, Rp, PK, PKp, m), the unkeyed entry points' arguments — -> (verdicts [n], misses).  The
+        verdicts are the unkeyed entry point's for every input: the set is a key cache.  An item whose key is not
+        a valid registered key is decided by the unkeyed equation in the same call; misses counts those."""
+        u, pts, keys, m = self._by_value(args, "verify_open")
+        u, m = _arr(u, 32), _arr(m, 32)
+        pts, keys = [_arr(p, 64) for p in pts], [_arr(c, 64) for c in keys]
+        n = _same_n(u, m, *pts, *keys)
+        ok = np.zeros(n, dtype=np.uint8)
+        misses = ctypes.c_size_t()
+        null = ctypes.c_void_p(0)
+        _lib.check(_lib.load().dsv_verify_keyed_open(
+            self._handle(), _p(u), _p(pts[0]), _p(pts[1]) if len(pts) == 2 else null, _p(keys[0]),
+            _p(keys[1]) if len(keys) == 2 else null, _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
+        return ok, misses.value
+
+    def verify_open_dev(self, *args, misses=None, stream=None):
+        """CUDA tensors (u, R[, Rp], key_a[, key_b], m, ok, workspace): verify_open's verdicts into ok, enqueued
+        on `stream` (default: torch's current stream of the batch's device) as one chain of launches; does not
+        synchronise and may be captured.  workspace: >= keyed_open_workspace_bytes(n) bytes; misses as for
+        lookup_dev."""
+        if len(args) < 2:
+            raise ValueError("verify_open_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, keys, m = self._by_value(args[:-2], "verify_open_dev")
+        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
+        n, dev = _rows(*zip([u] + pts + keys + [m], [32] + [64] * (len(pts) + len(keys)) + [32], names))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_open_workspace_bytes(n), dev, "workspace")
+        null = ctypes.c_void_p(0)
+        _lib.check(_lib.load().dsv_verify_keyed_open_dev(
             self._handle(), _tp(u, 32), _tp(pts[0], 64), _tp(pts[1], 64) if len(pts) == 2 else null,
             self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
             ctypes.c_size_t(n), okp, wsp,
