@@ -529,7 +529,10 @@ int dsv_stdrng_vargen_inputs_dev(uint64_t seed, size_t first_item, size_t n, voi
  *                 64 B), decoded by the device decoder of the *_wire entry points (same accepted encodings).
  * Contract:
  *   Ownership   a key set belongs to the device that was current when it was created (it must be
- *               initialised); it is immutable after creation, and any number of concurrent calls may read it.
+ *               initialised).  Its device memory is allocated once and never moves; any number of concurrent
+ *               calls may read it.  It changes in one way only: dsv_keyset_append registers further keys behind
+ *               the ones it holds ("key sets that grow", below).  A call sees the set as it was when the call was
+ *               enqueued (or captured).
  *   Verdicts    ok[i] equals the unkeyed entry point's verdict on (u, R, PK[key_idx[i]], m) for every input
  *               the reference's types can hold.
  *   Key indices key_idx is uint32 per item; an index >= k gives ok = 0 and never a fault.
@@ -551,7 +554,52 @@ int dsv_keyset_create(int scheme, const uint8_t *pk_uv, const uint8_t *pk2_uv, s
 int dsv_keyset_create_wire(int scheme, const uint8_t *pk_bytes, size_t k, dsv_keyset **out);
 int dsv_keyset_destroy(dsv_keyset *ks);
 int dsv_keyset_info(const dsv_keyset *ks, int *scheme, size_t *k, size_t *bytes, int *device);
+/* key_ok: one byte per registered key.  dsv_keyset_key_ok writes k bytes, k as the call finds it: right for a set
+ * that nobody appends to meanwhile.  For a set that may grow between the caller's reading of k and this call use
+ * dsv_keyset_key_ok_n: it writes the first min(k, room) bytes, never more than `room`, and reports in *k_out (may
+ * be NULL) the k those bytes belong to — size `out` by the set's capacity, which never changes. */
 int dsv_keyset_key_ok(const dsv_keyset *ks, uint8_t *out /* k bytes */);
+int dsv_keyset_key_ok_n(const dsv_keyset *ks, uint8_t *out /* room bytes */, size_t room, size_t *k_out);
+/* ---- key sets that grow: reserved capacity, keys appended to a live set ---------------
+ * The admission half of the key cache (dsv_verify_keyed_open*): when a new key turns busy it is registered in
+ * place, at the cost of its own table, instead of a second set over all k + 1 keys.
+ *   create_reserved  dsv_keyset_create with room for `capacity` >= k keys: both device allocations (the tables
+ *               with key_ok, the index) are made for `capacity` keys — dsv_keyset_bytes(scheme, capacity) and
+ *               dsv_keyset_index_bytes(scheme, capacity); dsv_keyset_info's `bytes` reports the former; the index
+ *               has the slots of a set of `capacity` keys (dsv_debug_keyset_home_slot(scheme, capacity, ...)).
+ *               k may be 0 (the key pointers may then be NULL).  Checks in this order: NULL `out`, unknown scheme
+ *               (DSV_ERR_INVALID_ARGUMENT), capacity < k (DSV_ERR_INVALID_ARGUMENT), capacity > 2^32 - 2
+ *               (DSV_ERR_TOO_LARGE: indices are 32-bit and DSV_KEY_NONE is taken), then those of dsv_keyset_create.
+ *               The three plain constructors build sets with capacity == k.
+ *   append      m more keys in the constructor's form (append: affine host bytes; append_wire: key records;
+ *               append_mont_cols: `PublicKey*` objects), validated and recorded as at creation (an undecodable
+ *               or invalid key gets key_ok = 0 and takes an index all the same).  On DSV_OK they have the indices
+ *               *first_index .. *first_index + m - 1, *first_index = the k before the call (first_index may be
+ *               NULL), and dsv_keyset_info reports k + m.  Builds the tables of the new keys only and inserts them
+ *               into the index that is there: no registered key moves, an index handed out earlier stays valid, a
+ *               key that was registered already (or is given twice) still looks up to its lowest index.  Blocks;
+ *               runs on a stream of its own on the set's device, whatever device is current.  Once it has
+ *               returned, every keyed call enqueued afterwards, on any stream of the set's device, sees the new
+ *               keys.  Appends to one set are serialised; verify calls on the set go on beside an append.
+ *   Errors      NULL handle, or NULL keys with m > 0: DSV_ERR_INVALID_ARGUMENT.  A dead set (its device shut
+ *               down): DSV_ERR_NOT_INITIALIZED.  m = 0: DSV_OK, nothing launched.  k + m > capacity:
+ *               DSV_ERR_TOO_LARGE, nothing launched, the set unchanged (so every m > 0 on a set of a plain
+ *               constructor).  On any error the set keeps its k and every verdict under it.
+ *   Calls in flight and captured graphs (the stale-k rule)   No device pointer of a set ever changes, and an
+ *               append writes only table, key_ok and key-byte rows >= the old k and index slots that were empty.
+ *               A keyed call carries the k it was enqueued with, a captured graph the k of its capture, for ever:
+ *               an index >= that k gives ok = 0, and the lookup reads an index slot that holds a newer key as
+ *               empty.  So such a call decides exactly as it would have before the append — the closed-set forms
+ *               reject items under newer keys, the open-set form sends them down the unkeyed path and returns the
+ *               same verdict.  To use the new keys from a graph, capture it again.
+ *   Sizes       workspaces that depend on k (dsv_keyed_rlc_workspace_bytes) are checked against the k the call
+ *               sees: size them for `capacity`.
+ * Not here: eviction and replacement of keys. */
+int dsv_keyset_create_reserved(int scheme, const uint8_t *pk_uv, const uint8_t *pk2_uv, size_t k, size_t capacity,
+                               dsv_keyset **out);
+int dsv_keyset_append(dsv_keyset *ks, const uint8_t *pk_uv, const uint8_t *pk2_uv, size_t m, uint32_t *first_index);
+int dsv_keyset_append_wire(dsv_keyset *ks, const uint8_t *pk_bytes, size_t m, uint32_t *first_index);
+int dsv_keyset_capacity(const dsv_keyset *ks, size_t *capacity);
 size_t dsv_keyed_workspace_bytes(size_t n);
 int dsv_verify_single_keyed_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
                                 const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
@@ -643,6 +691,8 @@ int dsv_verify_vargen_keyed_wire(const dsv_keyset *ks, const uint8_t *sig64, con
  *               set from before submit returns: dsv_keyset_destroy and dsv_shutdown* wait for it.  A job whose
  *               set died before it ran reports DSV_ERR_NOT_INITIALIZED at its wait. */
 int dsv_keyset_create_mont_cols(int scheme, const dsv_column *cols /*[1|2]*/, size_t k, dsv_keyset **out);
+/* dsv_keyset_append for key objects (cols as for create_mont_cols; "key sets that grow" above) */
+int dsv_keyset_append_mont_cols(dsv_keyset *ks, const dsv_column *cols /*[1|2]*/, size_t m, uint32_t *first_index);
 size_t dsv_keyed_mont_workspace_bytes(int scheme, size_t n);
 int dsv_verify_keyed_mont_dev(const dsv_keyset *ks, const void *u, const void *R_uvz,
                               const void *Rp_uvz /* double only, else NULL */, const void *key_idx, const void *m,
@@ -654,7 +704,7 @@ int dsv_verify_keyed_mont_cols_submit(const dsv_keyset *ks, const dsv_column *co
  * Callers hold (signature, public key, message) triples, not indices.  Every key set carries an index over its
  * own keys — built by all three constructors behind the tables, in a device allocation of its own:
  * dsv_keyset_bytes and dsv_keyset_info's `bytes` do not count it, dsv_keyset_index_bytes(scheme, k) does (no GPU
- * needed; 0 for an unknown scheme or k = 0) = the keys' canonical affine bytes (64 B per point, key-major, rounded
+ * needed; 0 for an unknown scheme or k = 0; a reserved set: of its capacity) = the keys' canonical affine bytes (64 B per point, key-major, rounded
  * up to 256) + an open-addressing table of `cap` uint32 slots (rounded up to 256), cap = the smallest power of two
  * >= max(64, 2k), linear probing from a home slot (dsv_debug_keyset_home_slot; an unsalted hash of the key's
  * 32-bit words) that wraps.  A match is always a comparison of all the key's bytes; the hash only picks where the
@@ -677,8 +727,8 @@ int dsv_verify_keyed_mont_cols_submit(const dsv_keyset *ks, const dsv_column *co
  *               DSV_OK with nothing enqueued; a NULL pointer with n > 0 (key_b of a two-point set included), a
  *               short workspace, outputs that are not on the set's device: DSV_ERR_INVALID_ARGUMENT, nothing
  *               launched, `ok` untouched.  Enqueue-only on `stream`, never synchronise, may be captured: the
- *               lookup, the challenge hash, the keyed kernel — three kernel launches, in front of them one 4-byte
- *               memset node when `misses` is given; on an empty set (k = 0) two fills stand in for the lookup
+ *               lookup, the challenge hash, the keyed kernel — three kernel launches, in front of them a one-lane
+ *               kernel that zeroes `misses` when it is given; on an empty set (k = 0) two fills stand in for the lookup
  *               kernel (every index DSV_KEY_NONE, misses = n).
  *   Alignment   the lookup kernel reads a key in 16-byte loads: the device key columns must be 16-byte aligned
  *               (DSV_ERR_INVALID_ARGUMENT otherwise, nothing launched); key_idx_out and misses 4-byte aligned.
@@ -707,7 +757,7 @@ int dsv_verify_keyed_lookup(const dsv_keyset *ks, const uint8_t *u, const uint8_
  *   h = 0;  for w in words: h = (h ^ w) * 0x9E3779B1;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;
  *   h *= 0xC2B2AE35;  h ^= h >> 16   (mod 2^32);  home = h & (cap - 1) */
 uint64_t dsv_debug_keyset_home_slot(int scheme, size_t k, const uint8_t *key_a, const uint8_t *key_b);
-/* introspection: out[0] = capacity, [1] = occupied slots (= distinct valid keys), [2] = occupied slots whose key
+/* introspection: out[0] = slots of the index, [1] = occupied slots (= distinct valid keys), [2] = occupied slots whose key
  * is not in its home slot, [3] = the longest probe of a registered key (slots read to find it; 1 = at home);
  * all 0 for an empty set */
 int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
@@ -724,8 +774,8 @@ int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
  *   Schemes     single and double sets; a var-generator set is DSV_ERR_INVALID_ARGUMENT (nothing launched).
  *   _dev form   checks, error codes and alignment rules of dsv_verify_keyed_lookup_dev.  Enqueue-only on `stream`,
  *               one straight chain, never synchronises, may be captured: the lookup, the challenge hash over all n
- *               (once, for both paths), the keyed kernel over all n (a miss reads no table and gets 0), a 4-byte
- *               memset node and the miss list (the positions of the DSV_KEY_NONE items, one atomic per wave), and
+ *               (once, for both paths), the keyed kernel over all n (a miss reads no table and gets 0), a one-lane
+ *               kernel that zeroes the list's length and the miss list (the positions of the DSV_KEY_NONE items, one atomic per wave), and
  *               the unkeyed equation over that list, which overwrites the 0 of exactly the listed items.  The last
  *               launch is sized for n items and reads the list's length on the device: a workgroup past the end
  *               returns at once, so the host never learns the number of misses.  An empty set (k = 0): every

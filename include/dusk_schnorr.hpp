@@ -812,9 +812,11 @@ inline BatchJob verify_batch_var_gen_submit(const std::vector<SignatureVarGen>& 
 // `keys.verify_batch(sigs, idx, msgs)` verifies signature i against key idx[i]: the `Signature*` objects are
 // read where they lie as well, 164 B per single item on the bus instead of 256, about a third of the
 // arithmetic (dsv_verify_keyed_mont_cols).  Same verdicts as `pks[idx[i]].verify(sigs[i], msgs[i])`; an index
-// out of range or an invalid key (key_ok() == 0: z = 0, off the curve) gives false.  The set is immutable and
-// may be used from several threads; it owns device memory, so it moves but does not copy.  The key vector is
-// only read during construction.
+// out of range or an invalid key (key_ok() == 0: z = 0, off the curve) gives false.  The set may be used from
+// several threads; it owns device memory, so it moves but does not copy.  The key vector is only read during
+// construction.  `KeySet keys(pks, capacity);` reserves room for `capacity` keys, and `keys.append(more)` then
+// registers further keys in place (dsv_keyset_append_mont_cols): it returns the index of the first of them, no
+// registered key moves, and batches submitted before the append returned keep the set they were submitted with.
 namespace detail {
 template <class Key>
 struct KeyedTraits;
@@ -860,17 +862,30 @@ class BasicKeySet {
 
  public:
   using Sig = typename T::Sig;
-  explicit BasicKeySet(const std::vector<Key>& keys) : k_(keys.size()) {
+  explicit BasicKeySet(const std::vector<Key>& keys) {
     detail::ensure_init();
     dsv_column cols[2] = {};
-    if (k_) T::key_cols(keys.data(), cols);
-    detail::check(dsv_keyset_create_mont_cols(T::scheme, cols, k_, &ks_), "dsv_keyset_create_mont_cols");
+    if (!keys.empty()) T::key_cols(keys.data(), cols);
+    detail::check(dsv_keyset_create_mont_cols(T::scheme, cols, keys.size(), &ks_), "dsv_keyset_create_mont_cols");
   }
-  BasicKeySet(BasicKeySet&& o) noexcept : ks_(o.ks_), k_(o.k_) { o.ks_ = nullptr; }
+  // room for `capacity` >= keys.size() keys: append() registers the others later, in place
+  BasicKeySet(const std::vector<Key>& keys, size_t capacity) {
+    detail::ensure_init();
+    if (capacity < keys.size()) throw std::invalid_argument("KeySet: capacity below the number of keys");
+    detail::check(dsv_keyset_create_reserved(T::scheme, nullptr, nullptr, 0, capacity, &ks_),
+                  "dsv_keyset_create_reserved");
+    try {
+      (void)append(keys);
+    } catch (...) {
+      drop();
+      throw;
+    }
+  }
+  BasicKeySet(BasicKeySet&& o) noexcept : ks_(o.ks_) { o.ks_ = nullptr; }
   BasicKeySet& operator=(BasicKeySet&& o) noexcept {
     if (this != &o) {
       drop();
-      ks_ = o.ks_, k_ = o.k_;
+      ks_ = o.ks_;
       o.ks_ = nullptr;
     }
     return *this;
@@ -878,11 +893,32 @@ class BasicKeySet {
   BasicKeySet(const BasicKeySet&) = delete;
   BasicKeySet& operator=(const BasicKeySet&) = delete;
   ~BasicKeySet() { drop(); }  // (waits for the jobs submitted on the set)
-  size_t size() const { return k_; }
+  size_t size() const {
+    size_t k = 0;
+    if (ks_) detail::check(dsv_keyset_info(ks_, nullptr, &k, nullptr, nullptr), "dsv_keyset_info");
+    return k;
+  }
+  size_t capacity() const {
+    size_t c = 0;
+    if (ks_) detail::check(dsv_keyset_capacity(ks_, &c), "dsv_keyset_capacity");
+    return c;
+  }
+  // registers `keys` behind the ones the set holds and returns the index of the first of them (size() before the
+  // call); throws when the set has no room for them, and the set is then unchanged.  Blocks.
+  uint32_t append(const std::vector<Key>& keys) {
+    dsv_column cols[2] = {};
+    if (!keys.empty()) T::key_cols(keys.data(), cols);
+    uint32_t first = 0;
+    detail::check(dsv_keyset_append_mont_cols(ks_, cols, keys.size(), &first), "dsv_keyset_append_mont_cols");
+    return first;
+  }
   // per key: 1 = usable; 0 = a coordinate the Rust types cannot hold, z = 0 or a point off the curve
   std::vector<uint8_t> key_ok() const {
-    std::vector<uint8_t> ok(k_);
-    detail::check(dsv_keyset_key_ok(ks_, ok.data()), "dsv_keyset_key_ok");
+    // sized by the capacity, which never changes: another thread's append may raise k between two calls
+    std::vector<uint8_t> ok(capacity());
+    size_t k = 0;
+    detail::check(dsv_keyset_key_ok_n(ks_, ok.data(), ok.size(), &k), "dsv_keyset_key_ok_n");
+    ok.resize(k < ok.size() ? k : ok.size());
     return ok;
   }
   // the engine's verdict bytes (1 = true); idx[i]: the key of item i
@@ -928,7 +964,6 @@ class BasicKeySet {
     ks_ = nullptr;
   }
   dsv_keyset* ks_ = nullptr;
-  size_t k_ = 0;
 };
 using KeySet = BasicKeySet<PublicKey>;
 using KeySetDouble = BasicKeySet<PublicKeyDouble>;

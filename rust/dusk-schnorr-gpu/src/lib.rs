@@ -92,6 +92,19 @@ extern "C" {
                                      stream: *mut c_void, misses: *mut c_void) -> c_int;
     pub fn dsv_verify_keyed_open(ks: *const c_void, u: *const u8, r_uv: *const u8, rp_uv: *const u8, key_a: *const u8,
                                  key_b: *const u8, m: *const u8, n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    // key sets that grow (include/dsv.h, "key sets that grow"): a set with reserved capacity (affine host bytes,
+    // k may be 0 with null key pointers) and keys appended to a live set in place, in the three key forms;
+    // *first_index (may be null) = the index of the first appended key.  Raw exports.
+    pub fn dsv_keyset_create_reserved(scheme: c_int, pk_uv: *const u8, pk2_uv: *const u8, k: usize, capacity: usize,
+                                      out: *mut *mut c_void) -> c_int;
+    pub fn dsv_keyset_append(ks: *mut c_void, pk_uv: *const u8, pk2_uv: *const u8, m: usize,
+                             first_index: *mut u32) -> c_int;
+    pub fn dsv_keyset_append_wire(ks: *mut c_void, pk_bytes: *const u8, m: usize, first_index: *mut u32) -> c_int;
+    // (cols: a dsv_column array, [1] single / [2] double, var-generator, as for dsv_keyset_create_mont_cols)
+    pub fn dsv_keyset_append_mont_cols(ks: *mut c_void, cols: *const c_void, m: usize, first_index: *mut u32) -> c_int;
+    pub fn dsv_keyset_capacity(ks: *const c_void, capacity: *mut usize) -> c_int;
+    // key_ok of a set that may grow meanwhile: at most `room` bytes, *k_out = the k they belong to
+    pub fn dsv_keyset_key_ok_n(ks: *const c_void, out: *mut u8, room: usize, k_out: *mut usize) -> c_int;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.

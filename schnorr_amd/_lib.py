@@ -73,6 +73,9 @@ SYMBOLS = [
     "dsv_debug_keyset_index_stats",
     # key sets as a key cache: open-set verify by key value (misses take the unkeyed equation in the same call)
     "dsv_keyed_open_workspace_bytes", "dsv_verify_keyed_open_dev", "dsv_verify_keyed_open",
+    # key sets that grow: reserved capacity, keys appended to a live set
+    "dsv_keyset_create_reserved", "dsv_keyset_append", "dsv_keyset_append_wire", "dsv_keyset_append_mont_cols",
+    "dsv_keyset_capacity", "dsv_keyset_key_ok_n",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",

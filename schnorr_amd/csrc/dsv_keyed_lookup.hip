@@ -41,11 +41,13 @@ int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, s
                    uint32_t* misses, hipStream_t s) {
   if (ks->k == 0) {
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx), (int)kSlotEmpty, n, s));
-    if (misses) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(misses), (int)n, 1, s));
+    if (misses) launch_store_word(misses, (uint32_t)n, s);
+    HIP_TRY(hipGetLastError());
     return DSV_OK;
   }
   HIP_TRY(launch_key_lookup(static_cast<const uint8_t*>(key_a), static_cast<const uint8_t*>(key_b),
-                            keyset_points(ks->scheme), n, ks->index, ks->slots, ks->slot_mask, idx, misses, s));
+                            keyset_points(ks->scheme), n, ks->index, ks->slots, ks->slot_mask, ks->k, idx, misses,
+                            s));
   HIP_TRY(hipGetLastError());
   return DSV_OK;
 }
@@ -218,11 +220,12 @@ int dsv_debug_keyset_index_stats(const dsv_keyset* ks, uint64_t out[4]) {
   Context* cp = nullptr;
   if (int r = check_set(ks, -1, 0, cp)) return r;
   out[0] = out[1] = out[2] = out[3] = 0;
-  if (ks->k == 0) return DSV_OK;
+  const size_t k = ks->k;  // (an append may be filling rows and slots from k on: they are not this call's)
+  if (k == 0) return DSV_OK;
   DSV_ON_DEVICE(*cp);
   const int np = keyset_points(ks->scheme);
   const size_t cap = ks->slot_mask + 1, key_bytes = 64 * (size_t)np;
-  std::vector<uint8_t> keys(ks->k * key_bytes);
+  std::vector<uint8_t> keys(k * key_bytes);
   std::vector<uint32_t> slots(cap);
   HIP_TRY(hipMemcpy(keys.data(), ks->index, keys.size(), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(slots.data(), ks->slots, cap * 4, hipMemcpyDeviceToHost));
@@ -230,8 +233,9 @@ int dsv_debug_keyset_index_stats(const dsv_keyset* ks, uint64_t out[4]) {
   for (size_t slot = 0; slot < cap; slot++) {
     const uint32_t occ = slots[slot];
     if (occ == kSlotEmpty) continue;
+    if (occ >= ks->capacity) return fail(DSV_ERR_HIP, "slot %zu holds %u of %zu keys", slot, occ, ks->capacity);
+    if (occ >= k) continue;  // a key newer than this call: an empty slot, as the lookup reads it
     out[1]++;
-    if (occ >= ks->k) return fail(DSV_ERR_HIP, "slot %zu holds %u of %zu keys", slot, occ, ks->k);
     const uint8_t* kb = keys.data() + occ * key_bytes;
     const size_t home = home_hash_host(np, kb, kb + 64) & ks->slot_mask;
     const uint64_t probes = ((slot - home) & ks->slot_mask) + 1;  // slots read to find it

@@ -100,6 +100,42 @@ int verify_keyed_mont_cols_locked(const dsv_keyset* ks, const dsv_column* cols, 
       });
 }
 
+// the typed-object key form: m `PublicKey*` objects gathered out of their columns, normalised in front of the
+// table build
+KeysetForm keyset_form_mont_cols(int scheme, const dsv_column* cols, size_t m) {
+  const int np = keyset_points(scheme);
+  // behind the points: the objects' limbs (np x m x 96 B), the normalisation's verdicts and its prefix products
+  const size_t off_valid = align_up((size_t)np * m * 96, 256), off_prefix = off_valid + align_up(m, 256);
+  return {[=] {
+            if (!cols) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+            for (int p = 0; p < np; p++) {
+              if (!cols[p].base) return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: null pointer", p);
+              if (cols[p].stride < 96)
+                return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: stride %zu < 96", p, cols[p].stride);
+            }
+            return (int)DSV_OK;
+          },
+          off_prefix + align_up(normalize_prefix_bytes(m, np), 256),
+          // dense: the key points gathered out of the objects (outlives the transfer: the form lives until the
+          // call has synchronised its stream)
+          [=, dense = std::vector<uint8_t>()](Context&, uint8_t* P, uint8_t* own, hipStream_t s,
+                                              uint8_t*& valid) mutable {
+            dense.resize((size_t)np * m * 96);
+            NormalizeArgs a = {};
+            for (int p = 0; p < np; p++) {
+              copy_strided_plain(dense.data() + (size_t)p * m * 96, static_cast<const uint8_t*>(cols[p].base),
+                                 cols[p].stride, 96, m);
+              a.in[p] = own + (size_t)p * m * 96;
+              a.out[p] = P + (size_t)p * m * 64;
+            }
+            HIP_TRY(hipMemcpyAsync(own, dense.data(), dense.size(), hipMemcpyHostToDevice, s));
+            valid = own + off_valid;
+            launch_normalize_uvz(a, np, m, valid, reinterpret_cast<u32*>(own + off_prefix), s);
+            HIP_TRY(hipGetLastError());
+            return (int)DSV_OK;
+          }};
+}
+
 }  // namespace dsvh
 
 using namespace dsvh;
@@ -107,39 +143,10 @@ using namespace dsvh;
 extern "C" {
 
 int dsv_keyset_create_mont_cols(int scheme, const dsv_column* cols, size_t k, dsv_keyset** out) {
-  const int np = keyset_points(scheme);
-  // behind the points: the objects' limbs (np x k x 96 B), the normalisation's verdicts and its prefix products
-  const size_t off_valid = align_up((size_t)np * k * 96, 256), off_prefix = off_valid + align_up(k, 256);
-  // the key points gathered out of the objects (outlives the transfer: create_keyset's scratch syncs its stream
-  // before create_keyset returns)
-  std::vector<uint8_t> dense;
-  return create_keyset(
-      scheme, k, out,
-      [=] {
-        if (!cols) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-        for (int p = 0; p < np; p++) {
-          if (!cols[p].base) return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: null pointer", p);
-          if (cols[p].stride < 96)
-            return fail(DSV_ERR_INVALID_ARGUMENT, "column %d: stride %zu < 96", p, cols[p].stride);
-        }
-        return (int)DSV_OK;
-      },
-      off_prefix + align_up(normalize_prefix_bytes(k, np), 256),
-      [=, &dense](Context&, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid) {
-        dense.resize((size_t)np * k * 96);
-        NormalizeArgs a = {};
-        for (int p = 0; p < np; p++) {
-          copy_strided_plain(dense.data() + (size_t)p * k * 96, static_cast<const uint8_t*>(cols[p].base),
-                             cols[p].stride, 96, k);
-          a.in[p] = own + (size_t)p * k * 96;
-          a.out[p] = P + (size_t)p * k * 64;
-        }
-        HIP_TRY(hipMemcpyAsync(own, dense.data(), dense.size(), hipMemcpyHostToDevice, s));
-        valid = own + off_valid;
-        launch_normalize_uvz(a, np, k, valid, reinterpret_cast<u32*>(own + off_prefix), s);
-        HIP_TRY(hipGetLastError());
-        return (int)DSV_OK;
-      });
+  return create_keyset(scheme, k, k, false, out, keyset_form_mont_cols(scheme, cols, k));
+}
+int dsv_keyset_append_mont_cols(dsv_keyset* ks, const dsv_column* cols, size_t m, uint32_t* first_index) {
+  return append_keyset(ks, m, first_index, [=](int scheme) { return keyset_form_mont_cols(scheme, cols, m); });
 }
 
 size_t dsv_keyed_mont_workspace_bytes(int scheme, size_t n) {

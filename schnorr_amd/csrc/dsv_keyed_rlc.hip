@@ -76,6 +76,7 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const Items& in, const uint
   const size_t group = rlc_group_items(n);
   const int force_groups = rlc_forced_groups();
   const u32 history = *reinterpret_cast<volatile u32*>(history_words);  // (written by the verdict kernels; never waited for)
+  // (the caller holds the registry's shared lock: one k for the whole call, whatever an append does meanwhile)
   const KeyedRlcKeys keys{ks->tables, ks->key_ok, ks->k};
   RlcVerdictArgs va = {};
   u32* flags_area = nullptr;
@@ -91,7 +92,7 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const Items& in, const uint
     }
     const int G = force_groups > 0 ? force_groups : (history > 0 ? rlc_split_groups(cnt, window_bits) : 1);
     const RlcPlan plan = rlc_group_plan(scheme, cnt, window_bits, G, true);
-    KeyedCarve cv = carve_keyed_rlc(workspace, group, cnt, plan, scheme, ks->k);
+    KeyedCarve cv = carve_keyed_rlc(workspace, group, cnt, plan, scheme, keys.k);
     flags_area = cv.flags_area;
     cv.b.flags = cv.flags_area + (2 * g) * kRlcGroupFlagWords;
     va.subs[g] = (uint8_t)plan.groups;
@@ -126,7 +127,7 @@ int keyed_rlc_on(Context& ctx, const dsv_keyset* ks, const Items& in, const uint
     HIP_TRY(hipGetLastError());
   }
   if (!flags_area)  // (every group went to the per-signature kernel: the flag blocks' place does not depend on the plan)
-    flags_area = carve_keyed_rlc(workspace, group, group, rlc_group_plan(scheme, group, 8, 1, true), scheme, ks->k).flags_area;
+    flags_area = carve_keyed_rlc(workspace, group, group, rlc_group_plan(scheme, group, 8, 1, true), scheme, keys.k).flags_area;
   launch_rlc_verdict(flags_area, va, accepted_dev, history_words, s);
   HIP_TRY(hipGetLastError());
   return DSV_OK;

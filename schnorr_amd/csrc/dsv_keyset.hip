@@ -1,6 +1,7 @@
 // dsv_keyset.hip — registered key sets (include/dsv.h: dsv_keyset_*, dsv_verify_*_keyed*): creation from
-// affine points or wire records, the registry that dsv_shutdown_device empties, and the keyed verify entry
-// points (k_challenge unchanged, then k_verify_keyed; keyed.h).
+// affine points or wire records, with or without reserved capacity, appending keys to a live set, the registry
+// that dsv_shutdown_device empties, and the keyed verify entry points (k_challenge unchanged, then
+// k_verify_keyed; keyed.h).
 #include <algorithm>
 #include <shared_mutex>
 
@@ -9,7 +10,7 @@
 namespace dsvh {
 namespace {
 // live key sets; verify calls read under the shared lock, create / destroy / shutdown write under the
-// exclusive one
+// exclusive one; an append builds its rows under the shared lock and raises k under the exclusive one
 std::shared_mutex g_ks_mu;
 std::vector<dsv_keyset*> g_keysets;
 
@@ -43,36 +44,105 @@ int keyset_context(const dsv_keyset* ks, Context*& out) {
   return DSV_OK;
 }
 
-// tables of k keys from device points P0 / P1 (and the decoder's verdicts valid_in); registers the set
-int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_t* P1, const uint8_t* valid_in,
-                       size_t k, hipStream_t s, dsv_keyset** out) {
+// the calling thread's current device, which must be initialised
+int current_context(Context*& out) {
+  if (g_primary.load(std::memory_order_acquire) < 0) return fail(DSV_ERR_NOT_INITIALIZED, "dsv_init() has not been called");
+  int d = -1;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices || !g_ctx[d].ready.load(std::memory_order_acquire))
+    return fail(DSV_ERR_NOT_INITIALIZED, "the current device %d is not initialised", d);
+  out = &g_ctx[d];
+  return DSV_OK;
+}
+
+// device buffers + stream of one create / append call, released on every path
+struct Scratch {
+  uint8_t* dev = nullptr;
+  hipStream_t s = nullptr;
+  ~Scratch() {
+    if (s) (void)hipStreamSynchronize(s);
+    if (dev) (void)hipFree(dev);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+// The one body that registers keys: the m keys of `form` become rows first .. first + m - 1 of ks — their affine
+// points staged into a scratch of this call's (np x m x 64 B, then the form's own bytes from the next 256-byte
+// boundary), their tables and key_ok bytes built, their bytes and slots added to the index — on a stream of the
+// call's own (x.s; x.dev: the scratch), synchronised before it returns.  Writes only rows >= first and slots that
+// are empty.  ks->k is the caller's to raise.  (ks's device memory held: a new set, or the registry's shared lock.)
+int register_keys(Context& ctx, dsv_keyset* ks, size_t first, size_t m, const KeysetForm& form, Scratch& x) {
+  if (m == 0) return DSV_OK;
+  const int scheme = ks->scheme, np = keyset_points(scheme);
+  const size_t off_own = align_up((size_t)np * m * 64, 256);
+  HIP_TRY(hipMalloc(&x.dev, off_own + form.own_bytes));
+  const uint8_t* P0 = x.dev;
+  const uint8_t* P1 = np == 2 ? x.dev + m * 64 : nullptr;
+  uint8_t* valid = nullptr;
+  if (int r = form.stage(ctx, x.dev, x.dev + off_own, x.s, valid)) return r;
+  launch_build_key_tables(P0, P1, valid, np, m, ks->tables + first * (size_t)np * kKeyPointWords, ks->key_ok + first,
+                          x.s);
+  HIP_TRY(hipGetLastError());
+  // the index, behind the table build (it reads key_ok)
+  launch_append_key_index(P0, P1, ks->key_ok + first, np, first, m, ks->index, ks->slots, ks->slot_mask, x.s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(x.s));
+  return DSV_OK;
+}
+
+// both allocations of a set for ks->capacity keys, never moved afterwards: key_ok zeroed, every slot empty (on s)
+int allocate_keyset(dsv_keyset* ks, hipStream_t s) {
+  const int scheme = ks->scheme;
+  const size_t cap = ks->capacity;
+  ks->bytes = keyset_total_bytes(scheme, cap);
+  if (cap == 0) return DSV_OK;
+  HIP_TRY(hipMalloc(&ks->tables, ks->bytes));
+  ks->key_ok = reinterpret_cast<uint8_t*>(ks->tables) + keyset_table_bytes(scheme, cap);
+  HIP_TRY(hipMalloc(&ks->index, keyset_index_total_bytes(scheme, cap)));
+  ks->slots = reinterpret_cast<uint32_t*>(ks->index + keyset_index_keys_bytes(scheme, cap));
+  ks->slot_mask = keyset_index_cap(cap) - 1;
+  HIP_TRY(hipMemsetAsync(ks->key_ok, 0, ks->bytes - keyset_table_bytes(scheme, cap), s));
+  HIP_TRY(launch_clear_key_index(ks->slots, ks->slot_mask, s));
+  return DSV_OK;
+}
+
+bool registered(const dsv_keyset* ks) {  // (a registry lock held)
+  return std::find(g_keysets.begin(), g_keysets.end(), ks) != g_keysets.end();
+}
+}  // namespace
+
+int create_keyset(int scheme, size_t k, size_t capacity, bool reserved, dsv_keyset** out, const KeysetForm& form) {
+  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null output handle");
+  *out = nullptr;
+  if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
+  if (reserved) {
+    if (capacity < k) return fail(DSV_ERR_INVALID_ARGUMENT, "capacity %zu below the %zu keys given", capacity, k);
+    if (capacity > kMaxKeys - 1)
+      return fail(DSV_ERR_TOO_LARGE, "capacity %zu: indices are 32-bit and DSV_KEY_NONE is taken", capacity);
+  }
+  if (k > kMaxKeys) return fail(DSV_ERR_TOO_LARGE, "%zu keys: indices are 32-bit", k);
+  if (k)
+    if (int r = form.check_pointers()) return r;
+  Context* cp = nullptr;
+  if (int r = current_context(cp)) return r;
+  Context& ctx = *cp;
+  DSV_ON_DEVICE(ctx);
   dsv_keyset* ks = new dsv_keyset();
   ks->scheme = scheme;
-  ks->k = k;
+  ks->capacity = capacity;
   ks->device = ctx.device;
-  ks->bytes = keyset_total_bytes(scheme, k);
-  const int rc = [&]() -> int {
-    if (k == 0) return DSV_OK;
-    HIP_TRY(hipMalloc(&ks->tables, ks->bytes));
-    ks->key_ok = reinterpret_cast<uint8_t*>(ks->tables) + keyset_table_bytes(scheme, k);
-    launch_build_key_tables(P0, P1, valid_in, keyset_points(scheme), k, ks->tables, ks->key_ok, s);
-    HIP_TRY(hipGetLastError());
-    // the index over the keys' bytes, behind the table build (it reads key_ok)
-    HIP_TRY(hipMalloc(&ks->index, keyset_index_total_bytes(scheme, k)));
-    ks->slots = reinterpret_cast<uint32_t*>(ks->index + keyset_index_keys_bytes(scheme, k));
-    ks->slot_mask = keyset_index_cap(k) - 1;
-    HIP_TRY(launch_build_key_index(P0, P1, ks->key_ok, keyset_points(scheme), k, ks->index, ks->slots,
-                                   ks->slot_mask, s));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
+  int rc = [&]() -> int {
+    if (capacity == 0) return DSV_OK;
+    Scratch x;
+    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
+    if (int r = allocate_keyset(ks, x.s)) return r;
+    if (int r = register_keys(ctx, ks, 0, k, form, x)) return r;  // k keys appended to the empty set
+    HIP_TRY(hipStreamSynchronize(x.s));
     return DSV_OK;
   }();
+  ks->k = k;
   std::unique_lock<std::shared_mutex> lk(g_ks_mu);
-  if (rc == DSV_OK && !ctx.ready.load(std::memory_order_acquire)) {
-    free_device_memory(ks);
-    delete ks;
-    return fail(DSV_ERR_NOT_INITIALIZED, "device %d was shut down", ctx.device);
-  }
+  if (rc == DSV_OK && !ctx.ready.load(std::memory_order_acquire))
+    rc = fail(DSV_ERR_NOT_INITIALIZED, "device %d was shut down", ctx.device);
   if (rc != DSV_OK) {
     free_device_memory(ks);
     delete ks;
@@ -84,54 +154,68 @@ int create_from_device(Context& ctx, int scheme, const uint8_t* P0, const uint8_
   return DSV_OK;
 }
 
-// the calling thread's current device, which must be initialised
-int current_context(Context*& out) {
-  if (g_primary.load(std::memory_order_acquire) < 0) return fail(DSV_ERR_NOT_INITIALIZED, "dsv_init() has not been called");
-  int d = -1;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices || !g_ctx[d].ready.load(std::memory_order_acquire))
-    return fail(DSV_ERR_NOT_INITIALIZED, "the current device %d is not initialised", d);
-  out = &g_ctx[d];
+int append_keyset(dsv_keyset* ks, size_t m, uint32_t* first_index,
+                  const std::function<KeysetForm(int scheme)>& form_of) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  std::shared_ptr<std::mutex> mu;
+  {
+    std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+    if (!registered(ks)) return fail(DSV_ERR_INVALID_ARGUMENT, "not a live key set handle");  // (before ks is read)
+    mu = ks->append_mu;
+  }
+  std::lock_guard<std::mutex> one_appender(*mu);
+  size_t first = 0;
+  {
+    // shared, not exclusive: verify calls go on beside the table build; shutdown and destroy wait for it
+    std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+    if (!registered(ks)) return fail(DSV_ERR_INVALID_ARGUMENT, "not a live key set handle");
+    Context* cp = nullptr;
+    if (int r = keyset_context(ks, cp)) return r;
+    first = ks->k;  // (only an appender raises it, and this is the only one)
+    if (m == 0) {
+      if (first_index) *first_index = (uint32_t)first;
+      return DSV_OK;
+    }
+    if (m > ks->capacity - first)
+      return fail(DSV_ERR_TOO_LARGE, "%zu keys appended to %zu of capacity %zu", m, first, ks->capacity);
+    const KeysetForm form = form_of(ks->scheme);
+    if (int r = form.check_pointers()) return r;
+    DSV_ON_DEVICE(*cp);
+    Scratch x;
+    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
+    if (int r = register_keys(*cp, ks, first, m, form, x)) return r;
+  }
+  // the new rows are complete and visible: calls enqueued from here on may use them
+  std::unique_lock<std::shared_mutex> lk(g_ks_mu);
+  if (!registered(ks) || !ks->alive)
+    return fail(DSV_ERR_NOT_INITIALIZED, "the key set's device was shut down during the append");
+  ks->k = first + m;
+  if (first_index) *first_index = (uint32_t)first;
   return DSV_OK;
 }
 
-// device buffers + stream of one create call, released on every path
-struct Scratch {
-  uint8_t* dev = nullptr;
-  hipStream_t s = nullptr;
-  ~Scratch() {
-    if (s) (void)hipStreamSynchronize(s);
-    if (dev) (void)hipFree(dev);
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-}  // namespace
-
-int create_keyset(int scheme, size_t k, dsv_keyset** out, const std::function<int()>& check_pointers,
-                  size_t own_bytes, const KeysetStage& stage) {
-  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null output handle");
-  *out = nullptr;
-  if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
-  if (k > kMaxKeys) return fail(DSV_ERR_TOO_LARGE, "%zu keys: indices are 32-bit", k);
-  if (k)
-    if (int r = check_pointers()) return r;
-  Context* cp = nullptr;
-  if (int r = current_context(cp)) return r;
-  Context& ctx = *cp;
-  DSV_ON_DEVICE(ctx);
-  Scratch x;
-  const uint8_t* P[2] = {nullptr, nullptr};
-  uint8_t* valid = nullptr;
-  if (k) {
-    const int np = keyset_points(scheme);
-    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
-    // device scratch: the affine points (np x k x 64 B), then what the form stages them from
-    const size_t off_own = align_up((size_t)np * k * 64, 256);
-    HIP_TRY(hipMalloc(&x.dev, off_own + own_bytes));
-    for (int p = 0; p < np; p++) P[p] = x.dev + (size_t)p * k * 64;
-    if (int r = stage(ctx, x.dev, x.dev + off_own, x.s, valid)) return r;
-  }
-  return create_from_device(ctx, scheme, P[0], P[1], valid, k, x.s, out);
+KeysetForm keyset_form_affine(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t m) {
+  const bool two = keyset_points(scheme) == 2;
+  return {[=] { return !pk_uv || (two && !pk2_uv) ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; }, 0,
+          [=](Context&, uint8_t* P, uint8_t*, hipStream_t s, uint8_t*&) {
+            HIP_TRY(hipMemcpyAsync(P, pk_uv, m * 64, hipMemcpyHostToDevice, s));
+            if (two) HIP_TRY(hipMemcpyAsync(P + m * 64, pk2_uv, m * 64, hipMemcpyHostToDevice, s));
+            return (int)DSV_OK;
+          }};
+}
+KeysetForm keyset_form_wire(int scheme, const uint8_t* pk_bytes, size_t m) {
+  // behind the points: the records, then the decoder's verdicts
+  const int np = keyset_points(scheme);
+  const size_t rec = 32 * (size_t)np, off_valid = align_up(m * rec, 256);
+  return {[=] { return !pk_bytes ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; },
+          off_valid + align_up(m, 256),
+          [=](Context& ctx, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid) {
+            valid = own + off_valid;
+            HIP_TRY(hipMemcpyAsync(own, pk_bytes, m * rec, hipMemcpyHostToDevice, s));
+            for (int p = 0; p < np; p++)
+              if (int r = decompress_on(ctx, own + 32 * p, rec, m, P + (size_t)p * m * 64, valid, p > 0, s)) return r;
+            return (int)DSV_OK;
+          }};
 }
 
 namespace {
@@ -232,30 +316,28 @@ size_t dsv_keyset_bytes(int scheme, size_t k) { return scheme_ok(scheme) ? keyse
 size_t dsv_keyed_workspace_bytes(size_t n) { return keyed_ws_bytes(n); }
 
 int dsv_keyset_create(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t k, dsv_keyset** out) {
-  const bool two = keyset_points(scheme) == 2;
-  return create_keyset(
-      scheme, k, out,
-      [=] { return !pk_uv || (two && !pk2_uv) ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; }, 0,
-      [=](Context&, uint8_t* P, uint8_t*, hipStream_t s, uint8_t*&) {
-        HIP_TRY(hipMemcpyAsync(P, pk_uv, k * 64, hipMemcpyHostToDevice, s));
-        if (two) HIP_TRY(hipMemcpyAsync(P + k * 64, pk2_uv, k * 64, hipMemcpyHostToDevice, s));
-        return (int)DSV_OK;
-      });
+  return create_keyset(scheme, k, k, false, out, keyset_form_affine(scheme, pk_uv, pk2_uv, k));
 }
 int dsv_keyset_create_wire(int scheme, const uint8_t* pk_bytes, size_t k, dsv_keyset** out) {
-  // behind the points: the records, then the decoder's verdicts
-  const int np = keyset_points(scheme);
-  const size_t rec = 32 * (size_t)np, off_valid = align_up(k * rec, 256);
-  return create_keyset(
-      scheme, k, out, [=] { return !pk_bytes ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; },
-      off_valid + align_up(k, 256),
-      [=](Context& ctx, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid) {
-        valid = own + off_valid;
-        HIP_TRY(hipMemcpyAsync(own, pk_bytes, k * rec, hipMemcpyHostToDevice, s));
-        for (int p = 0; p < np; p++)
-          if (int r = decompress_on(ctx, own + 32 * p, rec, k, P + (size_t)p * k * 64, valid, p > 0, s)) return r;
-        return (int)DSV_OK;
-      });
+  return create_keyset(scheme, k, k, false, out, keyset_form_wire(scheme, pk_bytes, k));
+}
+int dsv_keyset_create_reserved(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t k, size_t capacity,
+                               dsv_keyset** out) {
+  return create_keyset(scheme, k, capacity, true, out, keyset_form_affine(scheme, pk_uv, pk2_uv, k));
+}
+
+int dsv_keyset_append(dsv_keyset* ks, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t m, uint32_t* first_index) {
+  return append_keyset(ks, m, first_index, [=](int scheme) { return keyset_form_affine(scheme, pk_uv, pk2_uv, m); });
+}
+int dsv_keyset_append_wire(dsv_keyset* ks, const uint8_t* pk_bytes, size_t m, uint32_t* first_index) {
+  return append_keyset(ks, m, first_index, [=](int scheme) { return keyset_form_wire(scheme, pk_bytes, m); });
+}
+
+int dsv_keyset_capacity(const dsv_keyset* ks, size_t* capacity) {
+  if (!ks || !capacity) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  *capacity = ks->capacity;
+  return DSV_OK;
 }
 
 int dsv_keyset_destroy(dsv_keyset* ks) {
@@ -285,17 +367,20 @@ int dsv_keyset_info(const dsv_keyset* ks, int* scheme, size_t* k, size_t* bytes,
   return DSV_OK;
 }
 
-int dsv_keyset_key_ok(const dsv_keyset* ks, uint8_t* out) {
+int dsv_keyset_key_ok_n(const dsv_keyset* ks, uint8_t* out, size_t room, size_t* k_out) {
   if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
   std::shared_lock<std::shared_mutex> rl(g_ks_mu);
   Context* cp = nullptr;
   if (int r = keyset_context(ks, cp)) return r;
-  if (ks->k == 0) return DSV_OK;
+  const size_t k = ks->k, n = k < room ? k : room;  // (one read of k: what is copied is what is reported)
+  if (k_out) *k_out = k;
+  if (n == 0) return DSV_OK;
   if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   DSV_ON_DEVICE(*cp);
-  HIP_TRY(hipMemcpy(out, ks->key_ok, ks->k, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, ks->key_ok, n, hipMemcpyDeviceToHost));
   return DSV_OK;
 }
+int dsv_keyset_key_ok(const dsv_keyset* ks, uint8_t* out) { return dsv_keyset_key_ok_n(ks, out, (size_t)-1, nullptr); }
 
 int dsv_verify_single_keyed_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* key_idx,
                                 const void* m, size_t n, void* ok, void* workspace, size_t workspace_bytes,

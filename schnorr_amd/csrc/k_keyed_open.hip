@@ -130,8 +130,7 @@ k_verify_listed(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c, Ch
 }
 
 hipError_t launch_miss_list(const uint32_t* key_idx, size_t n, uint32_t* list, uint32_t* count, hipStream_t s) {
-  const hipError_t e = hipMemsetAsync(count, 0, 4, s);
-  if (e != hipSuccess) return e;
+  launch_store_word(count, 0, s);
   if (n == 0) return hipSuccess;
   const unsigned g = grid_for(n, kMissBlock);
   hipLaunchKernelGGL(k_miss_list, dim3(g < kMaxMissGrid ? g : kMaxMissGrid), dim3(kMissBlock), 0, s, key_idx, n,

@@ -2,11 +2,12 @@
 // dsv_verify_keyed_lookup*, include/dsv.h): what turns the key COLUMNS of a batch — the
 // canonical affine bytes callers hold — into the key_idx column every keyed entry point takes.
 //
-// One device allocation per set, apart from the tables (keyed.h):
+// One device allocation per set, apart from the tables (keyed.h), made for the set's capacity (the plain
+// constructors: k) and never moved:
 //   keys   np * 64 B per key, key-major (PK | PK' for the double scheme, PK | Gen for the var-generator
 //          scheme), the bytes the set was built from; rounded up to 256 B
 //   slots  `cap` uint32, open addressing: a slot holds a key index or kSlotEmpty; cap = the smallest power
-//          of two >= max(64, 2k), so the table is at most half full; rounded up to 256 B
+//          of two >= max(64, 2 * capacity), so the table is at most half full; rounded up to 256 B
 // Only keys with key_ok == 1 are inserted (their bytes are canonical: every coordinate < q), equal keys share
 // one slot that holds the lowest of their indices.  Probing is linear from the key's home slot and wraps.
 // The hash picks the home slot only: a match is always a comparison of all np * 64 bytes.  It is not salted —
@@ -51,18 +52,28 @@ struct KeyHash {
 };
 
 // ---- k_keyed_lookup.hip ------------------------------------------------------------------------
-// The index of k keys from the affine points P0 / P1 (null for one-point keys) the tables were built from
-// and the table build's key_ok (earlier on `s`): copies the key bytes into `keys` and inserts the valid keys
-// into `slots` (mask + 1 of them, a power of two; filled with kSlotEmpty on `s` by this launcher first).  One
-// lane per key.  The first error of the fill, if any, is returned; the launch's own surfaces through
+// *p = v on `s`, by a one-lane kernel: the single words the capturable by-value calls reset per call (misses, the
+// miss list's length).  Not a memset node: in a captured graph, the first replay after a key set was created or
+// appended to in between had its 4-byte memset node write another byte value than the captured 0; a kernel node
+// keeps its arguments.
+void launch_store_word(uint32_t* p, uint32_t v, hipStream_t s);
+// Every slot of an index to kSlotEmpty on `s` (mask + 1 slots, a power of two): once, when the set is created.
+hipError_t launch_clear_key_index(uint32_t* slots, size_t mask, hipStream_t s);
+// m further keys, indices first .. first + m - 1, into the index of a set that holds `first` keys already
+// (a fresh set: first = 0): from the affine points P0 / P1 (null for one-point keys) their tables were built from
+// and the table build's key_ok for them (earlier on `s`; both start at the first NEW key), copies the key bytes
+// into `keys` at row first + j and inserts the valid keys into `slots` (the whole index's, cleared when the set
+// was created).  One lane per new key.  Writes only key-byte rows >= first and slots that were empty or hold an
+// equal key; may run beside lookups enqueued with k <= first.  The launch's error surfaces through
 // hipGetLastError() like every launcher's.
-hipError_t launch_build_key_index(const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints,
-                                  size_t k, uint8_t* keys, uint32_t* slots, size_t mask, hipStream_t s);
+void launch_append_key_index(const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints, size_t first,
+                             size_t m, uint8_t* keys, uint32_t* slots, size_t mask, hipStream_t s);
 // key_idx[i] = the index in the slot of item i's key bytes (key_a[i] | key_b[i], 64 B each, 16-byte aligned;
-// key_b null for one-point keys), else kSlotEmpty; misses (may be null): zeroed on `s`, then the number of
-// items that got kSlotEmpty.  One lane per item, grid-stride.
+// key_b null for one-point keys), else kSlotEmpty; k: the set's key count as the call sees it — an occupant >= k
+// (appended since) is read as an empty slot; misses (may be null): zeroed on `s` (launch_store_word), then the
+// number of items that got kSlotEmpty.  One lane per item, grid-stride.
 hipError_t launch_key_lookup(const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
-                             const uint8_t* keys, const uint32_t* slots, size_t mask, uint32_t* key_idx,
+                             const uint8_t* keys, const uint32_t* slots, size_t mask, size_t k, uint32_t* key_idx,
                              uint32_t* misses, hipStream_t s);
 
 }  // namespace dsv

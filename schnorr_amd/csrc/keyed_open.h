@@ -13,8 +13,8 @@ constexpr unsigned kMaxMissGrid = 2048;
 
 // ---- k_keyed_open.hip --------------------------------------------------------------------------
 // list[0 .. *count) = the positions i < n with key_idx[i] == kSlotEmpty, in no particular order; `count`
-// (one device word) is zeroed on `s` by this launcher first.  `list` holds n words; one atomic per wave.
-// The first error of the fill, if any, is returned; the launch's own surfaces through hipGetLastError().
+// (one device word) is zeroed on `s` by this launcher first (launch_store_word).  `list` holds n words; one
+// atomic per wave.  The launches' errors surface through hipGetLastError().
 hipError_t launch_miss_list(const uint32_t* key_idx, size_t n, uint32_t* list, uint32_t* count, hipStream_t s);
 // launch_verify_half (launch.h) over a list: ok[i] = valid[i] & [every chain's equation holds] for i = list[j],
 // j < min(*count, n), every column read at row i; an entry >= n is skipped and ok[] is left as it is everywhere

@@ -1,6 +1,8 @@
 // keyset_host.h — what the host units know about a registered key set (keyed.h: the tables): the handle,
 // the registry's lock and checks (dsv_keyset.hip), what a keyed call reads of its items.
 #pragma once
+#include <memory>
+#include <mutex>
 #include <shared_mutex>
 
 #include "dsv_host.h"
@@ -8,18 +10,25 @@
 #include "keyed_open.h"
 #include "keyed_wire.h"
 
+// Everything but k is fixed when the set is created: both allocations are sized for `capacity` keys and never
+// move.  k is read under the registry's shared lock and raised by dsv_keyset_append under the exclusive one, so a
+// call that holds the shared lock sees one k from its first check to its last launch.
 struct dsv_keyset {
   int scheme = 0;
-  size_t k = 0;
+  size_t k = 0;         // keys registered
+  size_t capacity = 0;  // keys the allocations hold (the plain constructors: k)
   int device = -1;
-  size_t bytes = 0;
+  size_t bytes = 0;     // of the table allocation: keyset_total_bytes(scheme, capacity)
   uint32_t* tables = nullptr;  // one allocation: the tables, then key_ok
-  uint8_t* key_ok = nullptr;
-  // the index over the set's own keys (keyed_lookup.h), an allocation of its own: the keys' bytes, then the slots
+  uint8_t* key_ok = nullptr;   // behind keyset_table_bytes(scheme, capacity)
+  // the index over the set's own keys (keyed_lookup.h), an allocation of its own: the keys' bytes for `capacity`
+  // keys, then the slots
   uint8_t* index = nullptr;
   uint32_t* slots = nullptr;
-  size_t slot_mask = 0;  // capacity - 1
+  size_t slot_mask = 0;  // keyset_index_cap(capacity) - 1
   bool alive = false;
+  // one appender at a time per set (shared with the appender: it outlives a handle destroyed under a waiting one)
+  std::shared_ptr<std::mutex> append_mu = std::make_shared<std::mutex>();
 };
 
 namespace dsvh {
@@ -85,15 +94,35 @@ int run_keyed_dev(const dsv_keyset* ks, int scheme, Null inputs_null, Bytes cols
                        [](const Context&, hipStream_t, const Workspace&) { return (int)DSV_OK; });
 }
 
-// One constructor call (dsv_keyset.hip), on the calling thread's current device: the checks in this order — null
-// `out`, unknown scheme, k > 2^32 - 1, then for k > 0 the form's own check_pointers() — a stream and a device
-// scratch of its own (the affine points P[p] at p * k * 64, then own_bytes of the form's from the next 256-byte
-// boundary), the form's staging, the table build; blocks, registers the set, *out = its handle.
-// stage(ctx, P, own, s, valid) (k > 0): brings the keys' affine points to P on stream s, working in `own`;
-// valid = the per-key verdicts of its decoding for the table build to AND in (left null: none).
+// One key form (affine host bytes, wire records, typed objects) for m keys, as the constructors and the appends
+// hand it to the one body that registers keys (dsv_keyset.hip):
+//   check_pointers()   the form's own argument checks (m > 0 only),
+//   own_bytes          device scratch of the form's, behind the affine points,
+//   stage(ctx, P, own, s, valid)   brings the m keys' affine points to P (point p of key j at p * m * 64 + j * 64)
+//                      on stream s, working in `own`; valid = the per-key verdicts of its decoding for the table
+//                      build to AND in (left null: none).
+// The form may hold host buffers of its own for the transfer: it lives until the call returns, behind the
+// stream's synchronisation.
 using KeysetStage = std::function<int(Context& ctx, uint8_t* P, uint8_t* own, hipStream_t s, uint8_t*& valid)>;
-int create_keyset(int scheme, size_t k, dsv_keyset** out, const std::function<int()>& check_pointers,
-                  size_t own_bytes, const KeysetStage& stage);
+struct KeysetForm {
+  std::function<int()> check_pointers;
+  size_t own_bytes;
+  KeysetStage stage;
+};
+// One constructor call, on the calling thread's current device: the checks in this order — null `out`, unknown
+// scheme, k > 2^32 - 1 (reserved: capacity < k, capacity > 2^32 - 2), then for k > 0 the form's own
+// check_pointers() — then both allocations for `capacity` keys, and the k keys appended to the empty set by the
+// body dsv_keyset_append runs; blocks, registers the set, *out = its handle.
+// reserved: dsv_keyset_create_reserved (the plain constructors pass capacity = k).
+int create_keyset(int scheme, size_t k, size_t capacity, bool reserved, dsv_keyset** out, const KeysetForm& form);
+// dsv_keyset_append*: m more keys of the form form_of(the set's scheme) into a live set, in place, on a stream of
+// its own; blocks.  *first_index (may be null) = the index of the first of them.
+int append_keyset(dsv_keyset* ks, size_t m, uint32_t* first_index,
+                  const std::function<KeysetForm(int scheme)>& form_of);
+// the three forms over m keys
+KeysetForm keyset_form_affine(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t m);
+KeysetForm keyset_form_wire(int scheme, const uint8_t* pk_bytes, size_t m);
+KeysetForm keyset_form_mont_cols(int scheme, const dsv_column* cols, size_t m);  // dsv_keyed_mont.hip
 
 // ---- decoded or normalised columns of a keyed batch: what a preparation launch leaves for the keyed call -----
 struct KeyedCols {

@@ -1010,16 +1010,24 @@ class KeySet:
         ks.verify_lookup_dev(u, R, PK, m, ok, workspace)      # (u, R, PK, Gen, m)
         ok, misses = ks.verify_open(u, R, PK, m)   # open-set verify (single, double): the unkeyed verdicts, a
         ks.verify_open_dev(u, R, PK, m, ok, workspace)        # registered key only makes them arrive sooner
+        ks = KeySet.reserved("single", 4096, PK)   # room for 4096 keys (PK may be omitted: an empty set)
+        first = ks.append(PK_new)                  # in place: indices first .. first + m - 1; append_wire(records),
+        ks.k, ks.capacity                          # append_mont_cols([pk96]) for the other key forms
     """
 
-    def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None):
+    def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None, capacity=None):
         if scheme not in _SCHEME_CODE:
             raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
         self.scheme = scheme
         self._h = ctypes.c_void_p()
         L = _lib.load()
         code = ctypes.c_int(_SCHEME_CODE[scheme])
-        if _mont_cols is not None:
+        if capacity is not None and (_mont_cols is not None or _wire is not None):
+            raise ValueError("capacity goes with affine keys: reserve, then append_wire / append_mont_cols")
+        if capacity is not None and PK is None and PK2 is None:
+            _lib.check(L.dsv_keyset_create_reserved(code, ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_size_t(0),
+                                                    ctypes.c_size_t(capacity), ctypes.byref(self._h)))
+        elif _mont_cols is not None:
             k, arr, held = _keyed_columns(_mont_cols, [96] * (1 if scheme == "single" else 2), "from_mont_cols")
             _lib.check(L.dsv_keyset_create_mont_cols(code, arr, ctypes.c_size_t(k), ctypes.byref(self._h)))
             del held
@@ -1032,11 +1040,60 @@ class KeySet:
                 raise ValueError("scheme %s takes %s" % (scheme, "PK only" if scheme == "single" else "PK and PK2"))
             arrs = [pk] + ([_arr(PK2, 64)] if PK2 is not None else [])
             _same_n(*arrs)
-            _lib.check(L.dsv_keyset_create(code, _p(pk), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0),
-                                           ctypes.c_size_t(pk.shape[0]), ctypes.byref(self._h)))
-        s, k, b, d = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+            pk2 = _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0)
+            if capacity is None:
+                _lib.check(L.dsv_keyset_create(code, _p(pk), pk2, ctypes.c_size_t(pk.shape[0]), ctypes.byref(self._h)))
+            else:
+                _lib.check(L.dsv_keyset_create_reserved(code, _p(pk), pk2, ctypes.c_size_t(pk.shape[0]),
+                                                        ctypes.c_size_t(capacity), ctypes.byref(self._h)))
+        self._refresh()
+
+    def _refresh(self):
+        """k, capacity, nbytes, device from the library"""
+        L = _lib.load()
+        s, k, b, d, c = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
         _lib.check(L.dsv_keyset_info(self._h, ctypes.byref(s), ctypes.byref(k), ctypes.byref(b), ctypes.byref(d)))
-        self.k, self.nbytes, self.device = k.value, b.value, d.value
+        _lib.check(L.dsv_keyset_capacity(self._h, ctypes.byref(c)))
+        self.k, self.nbytes, self.device, self.capacity = k.value, b.value, d.value, c.value
+
+    @classmethod
+    def reserved(cls, scheme, capacity, PK=None, PK2=None):
+        """dsv_keyset_create_reserved: the affine constructor with room for `capacity` keys; PK (and PK2) may be
+        omitted for a set that starts empty.  append / append_wire / append_mont_cols register keys in place."""
+        return cls(scheme, PK, PK2, capacity=int(capacity))
+
+    def _appended(self, rc, first):
+        _lib.check(rc)
+        self._refresh()
+        return int(first.value)
+
+    def append(self, PK, PK2=None):
+        """dsv_keyset_append: m more keys as affine points (uint8 [m, 64]; PK2 for the two-point schemes) into the
+        live set, in place; blocks.  Returns the index of the first of them (the k before the call); calls enqueued
+        afterwards see the new keys, calls in flight and captured graphs keep the k they were enqueued with."""
+        if (PK2 is None) != (self.scheme == "single"):
+            raise ValueError("scheme %s takes %s" % (self.scheme, "PK only" if self.scheme == "single" else "PK and PK2"))
+        arrs = [_arr(PK, 64)] + ([_arr(PK2, 64)] if PK2 is not None else [])
+        m = _same_n(*arrs)
+        first = ctypes.c_uint32()
+        return self._appended(_lib.load().dsv_keyset_append(
+            self._handle(), _p(arrs[0]), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0), ctypes.c_size_t(m),
+            ctypes.byref(first)), first)
+
+    def append_wire(self, pk_bytes):
+        """dsv_keyset_append_wire: append() for the reference's key records ([m, 32] or [m, 64])"""
+        rec = _arr(pk_bytes, 32 if self.scheme == "single" else 64)
+        first = ctypes.c_uint32()
+        return self._appended(_lib.load().dsv_keyset_append_wire(
+            self._handle(), _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(first)), first)
+
+    def append_mont_cols(self, cols):
+        """dsv_keyset_append_mont_cols: append() for key OBJECTS where they lie (cols as for from_mont_cols)"""
+        m, arr, held = _keyed_columns(list(cols), [96] * (1 if self.scheme == "single" else 2), "append_mont_cols")
+        first = ctypes.c_uint32()
+        rc = _lib.load().dsv_keyset_append_mont_cols(self._handle(), arr, ctypes.c_size_t(m), ctypes.byref(first))
+        del held
+        return self._appended(rc, first)
 
     @classmethod
     def from_wire(cls, scheme, pk_bytes):
@@ -1073,9 +1130,13 @@ class KeySet:
             pass
 
     def key_ok(self):
-        out = np.zeros(self.k, dtype=np.uint8)
-        _lib.check(_lib.load().dsv_keyset_key_ok(self._handle(), _p(out)))
-        return out
+        """one byte per registered key (dsv_keyset_key_ok_n): the buffer is sized by the capacity, which never
+        changes, and cut to the k the library copied for — another thread's append may land at any time"""
+        out = np.zeros(self.capacity, dtype=np.uint8)
+        k = ctypes.c_size_t()
+        _lib.check(_lib.load().dsv_keyset_key_ok_n(self._handle(), _p(out), ctypes.c_size_t(out.shape[0]),
+                                                   ctypes.byref(k)))
+        return out[:min(k.value, out.shape[0])]
 
     def debug_entry(self, key, point, window, digit):
         """affine u || v of digit * 2^(8 * window) * point (0: PK, 1: PK' / Gen) from the key's table"""
