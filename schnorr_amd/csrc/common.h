@@ -253,9 +253,108 @@ DSV_DEV int top_digit4(const u32 (&nz)[8]) {
 // negated, as in the one-base tables); (0, 0) reads the shared identity entry.  Both scalars are
 // non-negative: a term that enters the equation with a minus sign has its point negated instead
 // (load_fq_signed: q - u in the canonical domain, so every bound downstream is unchanged).
-constexpr int kJointSlots = 12;  // slot 0 is never written
-constexpr int kJointLaneWords = kJointSlots * kVarEntryWords;
-static_assert(kJointLaneWords <= 2 * kVarLaneWords, "the joint table lives in the two one-base slots");
+//
+// Storage: an entry is SPLIT by limb so that a lookup touches exactly two 64-byte lines and costs no
+// arithmetic.  Limbs 0..7 of (v+u, v-u, z, 2d*t) are four 32-byte blocks of one 128-byte slot in global
+// memory, slots 128-byte aligned (the table base is rounded up inside the workspace), every load and
+// store an aligned 16-byte one.  The four limb-8 words are one uint4 in LDS, laid out [slot][lane]: a
+// lane's bank is 4 * lane mod 64 whatever slot it picks, so 64 lanes reading 64 different slots do not
+// collide.  The workgroup is ONE wave and the LDS words are lane-private: no barrier.  (The 144-byte
+// entries at a 144-byte stride that this replaces started at 16 * e mod 64 and touched three lines
+// each.)  -entry: the two leading blocks swap by address, the first two LDS words swap in registers.
+constexpr int kJointSlots = 12;      // global slot 0 is never written: digit pair (0, 0) reads kJointIdentity
+constexpr int kJointSlotWords = 32;  // 128 B
+constexpr int kJointLaneWords = kJointSlots * kJointSlotWords;  // 1536 B per lane
+constexpr size_t kJointAlign = 128;
+static_assert((size_t)kVerifyBlock * kJointLaneWords * 4 + kJointAlign <= (size_t)kVerifyBlock * 2 * kVarLaneWords * 4,
+              "the aligned joint tables of a workgroup live in its lanes' two one-base slots");
+constexpr int kJointLdsVectors = kJointSlots * kVerifyBlock;  // uint4 each: 12 KB per one-wave workgroup
+struct JointTable {
+  u32* g;      // the lane's 12 global slots
+  uint4* top;  // the lane's column of the LDS part: slot e at top[e * kVerifyBlock]
+};
+struct alignas(128) JointIdentitySlot {
+  u32 w[kJointSlotWords];
+};
+constexpr JointIdentitySlot joint_identity_slot() {
+  // v+u = 1, v-u = 1, z = 1 (Montgomery form), 2d*t = 0: limbs 0..7
+  const u32 one[NL] = {DSV_ONE_LIST};
+  JointIdentitySlot s = {};
+  for (int i = 0; i < 8; i++) s.w[i] = s.w[8 + i] = s.w[16 + i] = one[i];
+  return s;
+}
+constexpr u32 joint_identity_top() {
+  const u32 one[NL] = {DSV_ONE_LIST};
+  return one[8];
+}
+__device__ const JointIdentitySlot kJointIdentity = joint_identity_slot();
+// the lane's table inside `var_tables` (addressed by workgroup and lane) and `lds` (kJointLdsVectors of the
+// workgroup); writes the identity's LDS part, once per wave
+DSV_DEV JointTable joint_table_of_lane(u32* var_tables, uint4* lds) {
+  // (rounded up by an offset, not through an integer: the pointer stays a global-memory pointer)
+  const size_t pad = (size_t)(0 - reinterpret_cast<uintptr_t>(var_tables)) & (kJointAlign - 1);
+  u32* base = var_tables + pad / 4;
+  JointTable t;
+  t.g = base + ((size_t)blockIdx.x * kVerifyBlock + threadIdx.x) * kJointLaneWords;
+  t.top = lds + threadIdx.x;
+  t.top[0] = make_uint4(joint_identity_top(), joint_identity_top(), joint_identity_top(), 0u);
+  return t;
+}
+DSV_DEV void store_joint_entry(const JointTable& t, int e, const Niels& n) {
+  uint4* p = reinterpret_cast<uint4*>(t.g + e * kJointSlotWords);
+  p[0] = make_uint4(n.vpu.l[0], n.vpu.l[1], n.vpu.l[2], n.vpu.l[3]);
+  p[1] = make_uint4(n.vpu.l[4], n.vpu.l[5], n.vpu.l[6], n.vpu.l[7]);
+  p[2] = make_uint4(n.vmu.l[0], n.vmu.l[1], n.vmu.l[2], n.vmu.l[3]);
+  p[3] = make_uint4(n.vmu.l[4], n.vmu.l[5], n.vmu.l[6], n.vmu.l[7]);
+  p[4] = make_uint4(n.z.l[0], n.z.l[1], n.z.l[2], n.z.l[3]);
+  p[5] = make_uint4(n.z.l[4], n.z.l[5], n.z.l[6], n.z.l[7]);
+  p[6] = make_uint4(n.t2d.l[0], n.t2d.l[1], n.t2d.l[2], n.t2d.l[3]);
+  p[7] = make_uint4(n.t2d.l[4], n.t2d.l[5], n.t2d.l[6], n.t2d.l[7]);
+  t.top[e * kVerifyBlock] = make_uint4(n.vpu.l[8], n.vmu.l[8], n.z.l[8], n.t2d.l[8]);
+}
+// limbs 0..7 from one 32-byte block, limb 8 from the LDS word
+DSV_DEV Fe load_joint_field(const u32* block, u32 top) {
+  const uint4* q = reinterpret_cast<const uint4*>(block);
+  const uint4 lo = q[0], hi = q[1];
+  Fe r;
+  r.l[0] = lo.x; r.l[1] = lo.y; r.l[2] = lo.z; r.l[3] = lo.w;
+  r.l[4] = hi.x; r.l[5] = hi.y; r.l[6] = hi.z; r.l[7] = hi.w;
+  r.l[8] = top;
+  return r;
+}
+// the lookup, software-pipelined like load_var_entry_raw: the loads go out one group operation ahead, the
+// sign fix-up (the LDS swap included) waits in finish_joint_entry until the entry is consumed
+struct RawJoint {
+  Fe a, b, z, t;  // limbs 0..7; a / b already swapped by address for a negative pair
+  uint4 top;      // limb 8 of (v+u, v-u, z, 2d*t) of the +entry
+  bool neg;
+};
+DSV_DEV RawJoint load_joint_entry_raw(const JointTable& tb, int d) {
+  RawJoint r;
+  r.neg = d < 0;
+  const int mag = r.neg ? -d : d;
+  const u32* p = mag == 0 ? kJointIdentity.w : tb.g + mag * kJointSlotWords;
+  r.top = tb.top[mag * kVerifyBlock];
+  r.a = load_joint_field(p + (r.neg ? 8 : 0), 0u);
+  r.b = load_joint_field(p + (r.neg ? 0 : 8), 0u);
+  r.z = load_joint_field(p + 16, 0u);
+  r.t = load_joint_field(p + 24, 0u);
+  return r;
+}
+DSV_DEV Niels finish_joint_entry(const RawJoint& r) {
+  Niels n;
+  n.vpu = r.a;
+  n.vpu.l[8] = r.neg ? r.top.y : r.top.x;
+  n.vmu = r.b;
+  n.vmu.l[8] = r.neg ? r.top.x : r.top.y;
+  n.z = r.z;
+  n.z.l[8] = r.top.z;
+  Fe t = r.t;
+  t.l[8] = r.top.w;
+  n.t2d = fe_select(r.neg, fe_neg2(t), t);
+  return n;
+}
+DSV_DEV Niels load_joint_entry(const JointTable& tb, int d) { return finish_joint_entry(load_joint_entry_raw(tb, d)); }
 // signed slot of the pair (da, db) given as raw digits ra = da + 1, rb = db + 1 (digits in [-1, 2]:
 // with this digit set a scalar of odd bit length never needs a window beyond its own length and
 // one of even length only when its top field is 3 or a carry arrives — 65.7 windows per wave on
@@ -295,14 +394,14 @@ DSV_DEV int top_digit2(const u32 (&nz)[8]) {
 }
 // P = (pu, pv), R = (ru, rv) affine.  Every sum / difference pair is one shared mixed addition onto
 // an extended point whose t1*t2 is at hand (ext_add_sub_aniels_t: 10 M per pair).
-DSV_DEV void build_joint_table(u32* tbl, const Fe& pu, const Fe& pv, const Fe& ru, const Fe& rv) {
+DSV_DEV void build_joint_table(const JointTable& tbl, const Fe& pu, const Fe& pv, const Fe& ru, const Fe& rv) {
   const Ext P = ext_from_affine(pu, pv), R = ext_from_affine(ru, rv);
   const Fe ttP = fe_mul(pu, pv), ttR = fe_mul(ru, rv);
   const Niels nP = ext_to_niels_t(P, ttP), nR = ext_to_niels_t(R, ttR);
-  store_var_entry(tbl, 1, nP);
-  store_var_entry(tbl, 2, nR);
+  store_joint_entry(tbl, 1, nP);
+  store_joint_entry(tbl, 2, nR);
   const ANiels aR = {nR.vpu, nR.vmu, nR.t2d};
-  auto put = [&](int slot, const Ext& x) { store_var_entry(tbl, slot, ext_to_niels(x)); };
+  auto put = [&](int slot, const Ext& x) { store_joint_entry(tbl, slot, ext_to_niels(x)); };
   Ext sum, diff;
   {
     ext_add_sub_aniels_t(sum, diff, P, ttP, aR);  // P + R, P - R
@@ -313,7 +412,7 @@ DSV_DEV void build_joint_table(u32* tbl, const Fe& pu, const Fe& pv, const Fe& r
   {
     const Ext P2 = ext_double_affine(pu, pv);
     const Fe tt = fe_mul(P2.t1, P2.t2);
-    store_var_entry(tbl, 3, ext_to_niels_t(P2, tt));
+    store_joint_entry(tbl, 3, ext_to_niels_t(P2, tt));
     ext_add_sub_aniels_t(sum, diff, P2, tt, aR);  // 2P + R, 2P - R
     put(7, sum);
     put(8, diff);
@@ -321,13 +420,15 @@ DSV_DEV void build_joint_table(u32* tbl, const Fe& pu, const Fe& pv, const Fe& r
   {
     const Ext R2 = ext_double_affine(ru, rv);
     const Fe tt = fe_mul(R2.t1, R2.t2);
-    store_var_entry(tbl, 4, ext_to_niels_t(R2, tt));
+    store_joint_entry(tbl, 4, ext_to_niels_t(R2, tt));
     // P's niels form comes back from its table slot: three fields fewer to keep live — or to spill —
     // across the two blocks above (57 instead of 78 spilled VGPRs in the single-equation kernel:
     // +0.9 %; reloading R's form for the second block as well and reordering the blocks leaves 25
     // but waits on the stores in flight: slower — profiles/r03/ab_joint_windows.txt)
-    const u32* e1 = tbl + 1 * kVarEntryWords;
-    const ANiels aP = {load_fe_words(e1), load_fe_words(e1 + NL), load_fe_words(e1 + 3 * NL)};
+    const u32* e1 = tbl.g + 1 * kJointSlotWords;
+    const uint4 top1 = tbl.top[1 * kVerifyBlock];
+    const ANiels aP = {load_joint_field(e1, top1.x), load_joint_field(e1 + 8, top1.y),
+                       load_joint_field(e1 + 24, top1.w)};
     ext_add_sub_aniels_t(sum, diff, R2, tt, aP);  // 2R + P, 2R - P
     put(9, sum);
     put(10, diff);

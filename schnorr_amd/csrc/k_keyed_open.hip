@@ -30,7 +30,7 @@ k_miss_list(const u32* __restrict__ key_idx, size_t n, u32* __restrict__ list, u
 }
 
 // ------------------------------------------------------------------------------------------
-// The verdict of item i: valid[i] & [every chain's equation holds]; tbl: the lane's window table.  This is the
+// The verdict of item i = list[base + lane]: valid[i] & [every chain's equation holds]; tbl: the lane's window table.  This is the
 // body of k_verify_fixed_half's loop (k_verify.hip, where the method is described), statement for statement, and
 // it is a COPY on purpose: with the body moved into a forced-inline function that both kernels call, the
 // compiled k_verify_fixed_half<1> and <2> came out with another register allocation (same budget, other
@@ -39,7 +39,8 @@ k_miss_list(const u32* __restrict__ key_idx, size_t n, u32* __restrict__ list, u
 // ------------------------------------------------------------------------------------------
 template <int NCHAIN>
 DSV_DEV bool listed_item_ok(const uint8_t* u, const uint8_t* c, const ChainOperands& op0, const ChainOperands& op1,
-                            const uint8_t* valid, size_t i, u32* tbl) {
+                            const uint8_t* valid, size_t i, const JointTable& tbl,
+                            const u32* list, size_t base) {
   bool good = valid[i] != 0;
   u32 ya[8], yb[8], w[8];
   bool b_neg;
@@ -73,22 +74,29 @@ DSV_DEV bool listed_item_ok(const uint8_t* u, const uint8_t* c, const ChainOpera
   for (int h = 0; h < NCHAIN; h++) {
     const ChainOperands op = h ? op1 : op0;
     {
+      // The chain's points are addressed by the row read from the list AGAIN (as for the store of the verdict in
+      // k_verify_listed): the kernel this one mirrors rebuilds its row from the workgroup's base and the lane,
+      // here it would stay in a register — with the addresses made from it — across the first chain's window
+      // loop, and the two-chain kernel spilled more than k_verify_fixed_half<2> (tests/test_keyset_open_abi.py).
+      u32 lane = threadIdx.x;
+      asm volatile("" : "+v"(lane));
+      const size_t r = list[base + lane];
       Fe pku, pkv, ru, rv;
-      good &= load_fq(pku, op.PK_uv, 2 * i);
-      good &= load_fq(pkv, op.PK_uv, 2 * i + 1);
-      good &= load_fq_signed(ru, op.R_uv, 2 * i, !b_neg);  // the chain adds -|b| * R unless b < 0
-      good &= load_fq(rv, op.R_uv, 2 * i + 1);
+      good &= load_fq(pku, op.PK_uv, 2 * r);
+      good &= load_fq(pkv, op.PK_uv, 2 * r + 1);
+      good &= load_fq_signed(ru, op.R_uv, 2 * r, !b_neg);  // the chain adds -|b| * R unless b < 0
+      good &= load_fq(rv, op.R_uv, 2 * r + 1);
       build_joint_table(tbl, pku, pkv, ru, rv);
     }
     // T = a*PK + |b|*(-+R) (+ w*G below): one joint entry per 2-bit window, loaded one window ahead
-    Ext acc = ext_from_niels(load_var_entry(tbl, joint_digit(ya, yb, top)));
+    Ext acc = ext_from_niels(load_joint_entry(tbl, joint_digit(ya, yb, top)));
     {
-      RawNiels e = load_var_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
+      RawJoint e = load_joint_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
 #pragma unroll 1
       for (int k = top - 1; k >= 0; k--) {
         acc = ext_mul4(acc);
-        const Niels cur = finish_var_entry(e);
-        e = load_var_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
+        const Niels cur = finish_joint_entry(e);
+        e = load_joint_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
         acc = ext_add_niels(acc, cur);
       }
     }
@@ -111,14 +119,15 @@ k_verify_listed(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c, Ch
   size_t listed = *count;
   if (listed > n) listed = n;
   if ((size_t)blockIdx.x * kVerifyBlock >= listed) return;
-  u32* tbl = var_tables + ((size_t)blockIdx.x * kVerifyBlock + threadIdx.x) * kJointLaneWords;
+  __shared__ uint4 top_limbs[kJointLdsVectors];  // limb 8 of the lane-private window entries (common.h)
+  const JointTable tbl = joint_table_of_lane(var_tables, top_limbs);
 #pragma unroll 1
   for (size_t base = (size_t)blockIdx.x * kVerifyBlock; base < listed;
        base += (size_t)gridDim.x * kVerifyBlock) {
     const size_t j = base + threadIdx.x;
     const u32 i = j < listed ? list[j] : kSlotEmpty;  // the list is only ever dereferenced where k_miss_list wrote it
     if (i >= n) continue;                             // (n <= DSV_MAX_BATCH = 2^28: kSlotEmpty is no row)
-    const bool good = listed_item_ok<NCHAIN>(u, c, op0, op1, valid, i, tbl);
+    const bool good = listed_item_ok<NCHAIN>(u, c, op0, op1, valid, i, tbl, list, base);
     // The row is read from the list AGAIN for the store, through a lane number the compiler cannot see through,
     // so that it does not stay in a register across the window loop: the kernel this one mirrors rebuilds its
     // row from the workgroup's base and the lane, this one has only the list — and with the row kept live it

@@ -27,7 +27,8 @@ k_verify_fixed_half(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c
                     ChainOperands op1, const uint8_t* __restrict__ valid, bool accumulate, size_t n,
                     uint8_t* __restrict__ ok, u32* __restrict__ var_tables, const u32* __restrict__ gate) {
   if (gate_says_done(gate)) return;  // the batch fast accept decided these items (launch.h)
-  u32* tbl = var_tables + ((size_t)blockIdx.x * kVerifyBlock + threadIdx.x) * kJointLaneWords;
+  __shared__ uint4 top_limbs[kJointLdsVectors];  // limb 8 of the lane-private window entries (common.h)
+  const JointTable tbl = joint_table_of_lane(var_tables, top_limbs);
 #pragma unroll 1
   for (size_t base = (size_t)blockIdx.x * kVerifyBlock; base < n;
        base += (size_t)gridDim.x * kVerifyBlock) {
@@ -74,14 +75,14 @@ k_verify_fixed_half(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c
         build_joint_table(tbl, pku, pkv, ru, rv);
       }
       // T = a*PK + |b|*(-+R) (+ w*G below): one joint entry per 2-bit window, loaded one window ahead
-      Ext acc = ext_from_niels(load_var_entry(tbl, joint_digit(ya, yb, top)));
+      Ext acc = ext_from_niels(load_joint_entry(tbl, joint_digit(ya, yb, top)));
       {
-        RawNiels e = load_var_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
+        RawJoint e = load_joint_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
 #pragma unroll 1
         for (int k = top - 1; k >= 0; k--) {
           acc = ext_mul4(acc);
-          const Niels cur = finish_var_entry(e);
-          e = load_var_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
+          const Niels cur = finish_joint_entry(e);
+          e = load_joint_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
           acc = ext_add_niels(acc, cur);
         }
       }
