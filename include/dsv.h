@@ -771,7 +771,8 @@ int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
  *               a registered key) is decided by the unkeyed equation, in the same call.  Registering a key changes
  *               how fast a verdict arrives and never the verdict.  misses: as for the closed-set call — the number
  *               of items that took the unkeyed path.
- *   Schemes     single and double sets; a var-generator set is DSV_ERR_INVALID_ARGUMENT (nothing launched).
+ *   Schemes     single and double sets through dsv_verify_keyed_open[_dev]; a var-generator set there is
+ *               DSV_ERR_INVALID_ARGUMENT (nothing launched): it has calls of its own, below.
  *   _dev form   checks, error codes and alignment rules of dsv_verify_keyed_lookup_dev.  Enqueue-only on `stream`,
  *               one straight chain, never synchronises, may be captured: the lookup, the challenge hash over all n
  *               (once, for both paths), the keyed kernel over all n (a miss reads no table and gets 0), a one-lane
@@ -793,6 +794,26 @@ int dsv_verify_keyed_open_dev(const dsv_keyset *ks, const void *u, const void *R
 int dsv_verify_keyed_open(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *Rp_uv,
                           const uint8_t *key_a, const uint8_t *key_b, const uint8_t *m, size_t n, uint8_t *ok,
                           size_t *misses);
+/* The var-generator scheme's open-set form: (SignatureVarGen, PublicKeyVarGen, message) triples, the key columns
+ * PK_uv / Gen_uv being what the closed-set call takes as key_a / key_b.
+ *   Verify      ok[i] = what dsv_verify_vargen_dev writes for the same (u, R, PK, Gen, m) columns, for every input.
+ *               An item whose (PK, Gen) bytes are those of a valid registered key is decided by that key's tables;
+ *               every other item — an unregistered pair, a registered PK beside another key's Gen, a registered
+ *               but invalid key, another encoding — by the unkeyed equation u*Gen + c*PK == R, in the same call.
+ *               misses: as for the closed-set call.
+ *   Schemes     var-generator sets only; a single or double set is DSV_ERR_INVALID_ARGUMENT (nothing launched; the
+ *               message names dsv_verify_keyed_open).
+ *   _dev form   checks, error codes, texts and alignment rules of dsv_verify_keyed_open_dev, and its chain of
+ *               launches on `stream` with the three-base one-lane kernel over the miss list at the end;
+ *               enqueue-only, never synchronises, may be captured.  n = 0: DSV_OK, nothing touched.
+ *   Workspace   dsv_keyed_open_workspace_bytes(n), the same layout (its window tables are the three per lane that
+ *               this scheme's unkeyed kernel needs).
+ *   Host form   as dsv_verify_keyed_open: chunks of 2^18 items, *misses summed over the chunks. */
+int dsv_verify_vargen_keyed_open_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *PK_uv,
+                                     const void *Gen_uv, const void *m, size_t n, void *ok, void *workspace,
+                                     size_t workspace_bytes, void *stream, void *misses);
+int dsv_verify_vargen_keyed_open(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *PK_uv,
+                                 const uint8_t *Gen_uv, const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

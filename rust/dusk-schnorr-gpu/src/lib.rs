@@ -92,6 +92,15 @@ extern "C" {
                                      stream: *mut c_void, misses: *mut c_void) -> c_int;
     pub fn dsv_verify_keyed_open(ks: *const c_void, u: *const u8, r_uv: *const u8, rp_uv: *const u8, key_a: *const u8,
                                  key_b: *const u8, m: *const u8, n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    // ... and the var-generator scheme's form (var-generator sets only; key columns PK, Gen): the verdicts of
+    // dsv_verify_vargen_dev for every input.  Same workspace.
+    pub fn dsv_verify_vargen_keyed_open_dev(ks: *const c_void, u: *const c_void, r_uv: *const c_void,
+                                            pk_uv: *const c_void, gen_uv: *const c_void, m: *const c_void, n: usize,
+                                            ok: *mut c_void, workspace: *mut c_void, workspace_bytes: usize,
+                                            stream: *mut c_void, misses: *mut c_void) -> c_int;
+    pub fn dsv_verify_vargen_keyed_open(ks: *const c_void, u: *const u8, r_uv: *const u8, pk_uv: *const u8,
+                                        gen_uv: *const u8, m: *const u8, n: usize, ok: *mut u8,
+                                        misses: *mut usize) -> c_int;
     // key sets that grow (include/dsv.h, "key sets that grow"): a set with reserved capacity (affine host bytes,
     // k may be 0 with null key pointers) and keys appended to a live set in place, in the three key forms;
     // *first_index (may be null) = the index of the first appended key.  Raw exports.

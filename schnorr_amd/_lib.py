@@ -73,6 +73,8 @@ SYMBOLS = [
     "dsv_debug_keyset_index_stats",
     # key sets as a key cache: open-set verify by key value (misses take the unkeyed equation in the same call)
     "dsv_keyed_open_workspace_bytes", "dsv_verify_keyed_open_dev", "dsv_verify_keyed_open",
+    # ... and the var-generator scheme's open-set form (key columns PK, Gen)
+    "dsv_verify_vargen_keyed_open_dev", "dsv_verify_vargen_keyed_open",
     # key sets that grow: reserved capacity, keys appended to a live set
     "dsv_keyset_create_reserved", "dsv_keyset_append", "dsv_keyset_append_wire", "dsv_keyset_append_mont_cols",
     "dsv_keyset_capacity", "dsv_keyset_key_ok_n",
@@ -132,6 +134,10 @@ def load():
     L.dsv_keyset_index_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_debug_keyset_home_slot.restype = ctypes.c_uint64
     L.dsv_debug_keyset_home_slot.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    # (ks, u, R, PK, Gen, m, n, ok, workspace, workspace_bytes, stream, misses) / (ks, u, R, PK, Gen, m, n, ok, misses)
+    L.dsv_verify_vargen_keyed_open_dev.argtypes = [vp] * 6 + [sz, vp, vp, sz, vp, vp]
+    L.dsv_verify_vargen_keyed_open.argtypes = [vp] * 6 + [sz, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("dsv_version", "dsv_last_error", "dsv_debug_keyset_home_slot") + _SIZE_T_FUNCS:

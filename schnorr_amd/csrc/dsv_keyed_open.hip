@@ -1,17 +1,27 @@
-// dsv_keyed_open.hip — registered key sets as a key cache (include/dsv.h: dsv_verify_keyed_open*; keyed_open.h;
-// DESIGN.md §10.5): the open-set form of verify by key value.  The verdicts are those of the unkeyed call on the
-// same columns for every input; an item under a valid registered key is decided by the key's tables, every other
-// item by the unkeyed equation.  Device form, one stream, enqueue-only: lookup, challenge hash and keyed kernel
-// over all n (a miss gets 0 there), the list of the misses, the unkeyed equation over that list.  Host form: the
-// same per chunk through the context's staging.  Single and double signatures.
+// dsv_keyed_open.hip — registered key sets as a key cache (include/dsv.h: dsv_verify_keyed_open*,
+// dsv_verify_vargen_keyed_open*; keyed_open.h): the open-set form of verify by key value.  The
+// verdicts are those of the unkeyed call on the same columns for every input; an item under a valid registered key
+// is decided by the key's tables, every other item by the unkeyed equation.  Device form, one stream,
+// enqueue-only: lookup, challenge hash and keyed kernel over all n (a miss gets 0 there), the list of the misses,
+// the unkeyed equation over that list.  Host form: the same per chunk through the context's staging.  Single and
+// double signatures through the generic call, the var-generator scheme through a call of its own (the generic
+// one refuses its sets); both are one body here.
 #include "keyset_host.h"
 
 namespace dsvh {
 namespace {
 
-int open_scheme_ok(int scheme) {
-  if (scheme == 2)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "the open-set form has no var-generator scheme (key set of scheme 2)");
+// vargen: the call is dsv_verify_vargen_keyed_open*, which takes var-generator sets and no others
+int open_scheme_ok(int scheme, bool vargen) {
+  if (vargen && scheme != 2)
+    return fail(DSV_ERR_INVALID_ARGUMENT,
+                "dsv_verify_vargen_keyed_open takes a var-generator key set (key set of scheme %d: "
+                "dsv_verify_keyed_open)",
+                scheme);
+  if (!vargen && scheme == 2)
+    return fail(DSV_ERR_INVALID_ARGUMENT,
+                "the open-set form has no var-generator scheme (key set of scheme 2); "
+                "dsv_verify_vargen_keyed_open takes such a set");
   return DSV_OK;
 }
 
@@ -28,11 +38,18 @@ MissBranch carve_miss_branch(Stager& x, size_t n) {
   return b;
 }
 // behind the keyed kernel on s: the misses of idx are listed and decided by the unkeyed equation from the c /
-// valid the challenge hash left in w; in: the keyed call's items, key_a / key_b: the items' own key columns
+// valid the challenge hash left in w; in: the keyed call's items, key_a / key_b: the items' own key columns (the
+// var-generator scheme: PK / Gen, one three-base chain)
 int enqueue_miss_branch(const Context& ctx, const Items& in, const void* key_a, const void* key_b,
                         const uint32_t* idx, size_t n, uint8_t* ok, const MissBranch& b, const Workspace& w,
                         hipStream_t s) {
   HIP_TRY(launch_miss_list(idx, n, b.list, b.count, s));
+  if (in.scheme == 2) {
+    launch_verify_var_listed(in.u, w.c, static_cast<const uint8_t*>(key_a), static_cast<const uint8_t*>(key_b), in.R(),
+                             w.valid, n, ok, b.tables, b.list, b.count, s);
+    HIP_TRY(hipGetLastError());
+    return DSV_OK;
+  }
   const ChainOperands op0{static_cast<const uint8_t*>(key_a), in.R(), ctx.table[0]};
   const ChainOperands op1{static_cast<const uint8_t*>(key_b), in.Rp(), ctx.table[1]};
   launch_verify_listed(in.scheme == 1 ? 2 : 1, in.u, w.c, op0, op1, w.valid, n, ok, b.tables, b.list, b.count, s);
@@ -40,26 +57,17 @@ int enqueue_miss_branch(const Context& ctx, const Items& in, const void* key_a, 
   return DSV_OK;
 }
 
-}  // namespace
-}  // namespace dsvh
-
-using namespace dsvh;
-
-extern "C" {
-
-size_t dsv_keyed_open_workspace_bytes(size_t n) {
-  return align_up(4 * n, 256) + keyed_ws_bytes(n) + open_miss_bytes(n);
-}
-
-int dsv_verify_keyed_open_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
-                              const void* key_a, const void* key_b, const void* m, size_t n, void* ok,
-                              void* workspace, size_t workspace_bytes, void* stream, void* misses) {
+// ---- the two forms, for the generic call (vargen = false: single and double sets, key_a / key_b = PK / PK') and
+// for the var-generator one (vargen = true: no second nonce point, key_a / key_b = PK / Gen) -------------------
+int open_dev(bool vargen, const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
+             const void* key_a, const void* key_b, const void* m, size_t n, void* ok, void* workspace,
+             size_t workspace_bytes, void* stream, void* misses) {
   if (int r = library_up(ks)) return r;
   {
     std::shared_lock<std::shared_mutex> rl(keyset_mutex());
     Context* cp = nullptr;
     if (int r = check_set(ks, -1, n, cp)) return r;
-    if (int r = open_scheme_ok(ks->scheme)) return r;
+    if (int r = open_scheme_ok(ks->scheme, vargen)) return r;
   }
   // the workspace in order: idx | list | count | window tables | c | valid; run_keyed_dev checks and hands on the
   // index pointer, which is the workspace itself
@@ -73,7 +81,7 @@ int dsv_verify_keyed_open_dev(const dsv_keyset* ks, const void* u, const void* R
       [=](int) { return align_up(4 * n, 256) + open_miss_bytes(n); }, workspace, n, ok, workspace, workspace_bytes,
       stream,
       [&](const Context& ctx, int scheme, Stager& x, hipStream_t s, Items& in, const uint8_t*&) {
-        if (int r = open_scheme_ok(scheme)) return r;  // (the handle was reused between the two locks)
+        if (int r = open_scheme_ok(scheme, vargen)) return r;  // (the handle was reused between the two locks)
         if (int r = check_key_alignment(scheme, key_a, key_b)) return r;
         if (int r = check_misses(ks, &ctx, misses)) return r;
         uint32_t* idx = reinterpret_cast<uint32_t*>(x.take(4 * n));
@@ -88,25 +96,25 @@ int dsv_verify_keyed_open_dev(const dsv_keyset* ks, const void* u, const void* R
       });
 }
 
-int dsv_verify_keyed_open(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
-                          const uint8_t* key_a, const uint8_t* key_b, const uint8_t* m, size_t n, uint8_t* ok,
-                          size_t* misses) {
+int open_host(bool vargen, const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
+              const uint8_t* key_a, const uint8_t* key_b, const uint8_t* m, size_t n, uint8_t* ok, size_t* misses) {
   if (int r = library_up(ks)) return r;
   std::shared_lock<std::shared_mutex> rl(keyset_mutex());
   Context* cp = nullptr;
   if (int r = check_set(ks, -1, n, cp)) return r;
-  if (int r = open_scheme_ok(ks->scheme)) return r;
+  if (int r = open_scheme_ok(ks->scheme, vargen)) return r;
   if (n == 0) {
     if (misses) *misses = 0;
     return DSV_OK;
   }
-  const int scheme = ks->scheme, np = keyset_points(scheme);  // (as many nonce points as key points here)
-  if (!u || !R_uv || (np == 2 && !Rp_uv) || !m || keys_null(scheme, key_a, key_b) || !ok)
+  // nonce-point and key columns: 1 + 1, 2 + 2, and 1 + 2 for the var-generator scheme
+  const int scheme = ks->scheme, ns = keyed_sig_points(scheme), np = keyset_points(scheme);
+  if (!u || !R_uv || (ns == 2 && !Rp_uv) || !m || keys_null(scheme, key_a, key_b) || !ok)
     return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
   Context& ctx = *cp;
   DSV_HOST_LOCK();
   const size_t chunk = n < kLookupHostChunk ? n : kLookupHostChunk;
-  const size_t per_item = 32 + 32 + 4 + 1 + 64 * (size_t)(2 * np);
+  const size_t per_item = 32 + 32 + 4 + 1 + 64 * (size_t)(ns + np);
   if (int r = ensure_stage(ctx, chunk * per_item + keyed_ws_bytes(chunk) + open_miss_bytes(chunk) + 12 * 256))
     return r;
   size_t total = 0;
@@ -118,7 +126,7 @@ int dsv_verify_keyed_open(const dsv_keyset* ks, const uint8_t* u, const uint8_t*
     uint32_t* di = reinterpret_cast<uint32_t*>(st.take(cnt * 4));
     uint8_t* dok = st.take(cnt);
     uint8_t* dR = st.take(cnt * 64);
-    uint8_t* dRp = np == 2 ? st.take(cnt * 64) : nullptr;
+    uint8_t* dRp = ns == 2 ? st.take(cnt * 64) : nullptr;
     uint8_t* da = st.take(cnt * 64);
     uint8_t* db = np == 2 ? st.take(cnt * 64) : nullptr;
     uint32_t* dmiss = reinterpret_cast<uint32_t*>(st.take(4));
@@ -143,6 +151,38 @@ int dsv_verify_keyed_open(const dsv_keyset* ks, const uint8_t* u, const uint8_t*
   }
   if (misses) *misses = total;
   return DSV_OK;
+}
+
+}  // namespace
+}  // namespace dsvh
+
+using namespace dsvh;
+
+extern "C" {
+
+size_t dsv_keyed_open_workspace_bytes(size_t n) {
+  return align_up(4 * n, 256) + keyed_ws_bytes(n) + open_miss_bytes(n);
+}
+
+int dsv_verify_keyed_open_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
+                              const void* key_a, const void* key_b, const void* m, size_t n, void* ok,
+                              void* workspace, size_t workspace_bytes, void* stream, void* misses) {
+  return open_dev(false, ks, u, R_uv, Rp_uv, key_a, key_b, m, n, ok, workspace, workspace_bytes, stream, misses);
+}
+int dsv_verify_keyed_open(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
+                          const uint8_t* key_a, const uint8_t* key_b, const uint8_t* m, size_t n, uint8_t* ok,
+                          size_t* misses) {
+  return open_host(false, ks, u, R_uv, Rp_uv, key_a, key_b, m, n, ok, misses);
+}
+
+int dsv_verify_vargen_keyed_open_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* PK_uv,
+                                     const void* Gen_uv, const void* m, size_t n, void* ok, void* workspace,
+                                     size_t workspace_bytes, void* stream, void* misses) {
+  return open_dev(true, ks, u, R_uv, nullptr, PK_uv, Gen_uv, m, n, ok, workspace, workspace_bytes, stream, misses);
+}
+int dsv_verify_vargen_keyed_open(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* PK_uv,
+                                 const uint8_t* Gen_uv, const uint8_t* m, size_t n, uint8_t* ok, size_t* misses) {
+  return open_host(true, ks, u, R_uv, nullptr, PK_uv, Gen_uv, m, n, ok, misses);
 }
 
 }  // extern "C"

@@ -23,4 +23,13 @@ void launch_verify_listed(int nchain, const uint8_t* u, const uint8_t* c, ChainO
                           const uint8_t* valid, size_t n, uint8_t* ok, uint32_t* var_tables, const uint32_t* list,
                           const uint32_t* count, hipStream_t s);
 
+// ---- k_keyed_open_var.hip ----------------------------------------------------------------------
+// launch_verify_var's one-lane kernel (launch.h) over a list, the var-generator scheme's miss branch:
+// ok[i] = valid[i] & [u*Gen + c*PK == R] for i = list[j], j < min(*count, n), every column read at row i; an
+// entry >= n is skipped and ok[] is left as it is everywhere else.  verify_grid(n) one-wave workgroups, each
+// reading *count once; var_tables: three window tables per lane, as for launch_verify_var.  No gate.
+void launch_verify_var_listed(const uint8_t* u, const uint8_t* c, const uint8_t* PK_uv, const uint8_t* Gen_uv,
+                              const uint8_t* R_uv, const uint8_t* valid, size_t n, uint8_t* ok,
+                              uint32_t* var_tables, const uint32_t* list, const uint32_t* count, hipStream_t s);
+
 }  // namespace dsv

@@ -1407,3 +1407,36 @@ class KeySet:
             self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
             ctypes.c_size_t(n), okp, wsp,
             ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
+
+    def verify_vargen_open(self, *args):
+        """verify_vargen_open(u, R, PK, Gen, m) -> (verdicts [n], misses): the var-generator scheme's open-set
+        verify by key value (dsv_verify_vargen_keyed_open; var-generator sets — verify_open refuses them), host
+        arrays.  The verdicts are verify_vargen's for every input; an item whose (PK, Gen) bytes are not those of a
+        valid registered key is decided by the unkeyed equation in the same call, and misses counts those."""
+        if len(args) != 5:
+            raise ValueError("verify_vargen_open takes (u, R, PK, Gen, m)")
+        u, R, PK, Gen, m = args
+        u, m = _arr(u, 32), _arr(m, 32)
+        R, PK, Gen = _arr(R, 64), _arr(PK, 64), _arr(Gen, 64)
+        n = _same_n(u, m, R, PK, Gen)
+        ok = np.zeros(n, dtype=np.uint8)
+        misses = ctypes.c_size_t()
+        _lib.check(_lib.load().dsv_verify_vargen_keyed_open(
+            self._handle(), _p(u), _p(R), _p(PK), _p(Gen), _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
+        return ok, misses.value
+
+    def verify_vargen_open_dev(self, *args, misses=None, stream=None):
+        """verify_vargen_open_dev(u, R, PK, Gen, m, ok, workspace, misses=None, stream=None): CUDA tensors;
+        verify_vargen_open's verdicts into ok, enqueued on `stream` (default: torch's current stream of the batch's
+        device) as one chain of launches; does not synchronise and may be captured.  workspace: >=
+        keyed_open_workspace_bytes(n) bytes; misses as for lookup_dev."""
+        if len(args) != 7:
+            raise ValueError("verify_vargen_open_dev takes (u, R, PK, Gen, m), then ok and workspace")
+        u, R, PK, Gen, m, ok, workspace = args
+        n, dev = _rows(*zip([u, R, PK, Gen, m], [32, 64, 64, 64, 32], ["u", "R", "PK", "Gen", "m"]))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_open_workspace_bytes(n), dev, "workspace")
+        _lib.check(_lib.load().dsv_verify_vargen_keyed_open_dev(
+            self._handle(), _tp(u, 32), _tp(R, 64), self._key_ptr(PK, "PK"), self._key_ptr(Gen, "Gen"), _tp(m, 32),
+            ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
+            self._misses_ptr(misses, dev)))

@@ -1,7 +1,7 @@
 """Key sets as a key cache: the open-set verify by key value against the closed-set call and the unkeyed call, by
 the share of items whose key is not registered; device-resident inputs (GPU).
 
-    python tools/keyset_open_bench.py [--out FILE] [--log2-n 20] [--reps 21] [--k 64] [--schemes single,double]
+    python tools/keyset_open_bench.py [--out FILE] [--log2-n 20] [--reps 21] [--k 64] [--schemes single,double,vargen]
                                       [--shares 0,1/64,1/8,1/2,1]
     python tools/keyset_open_bench.py --one SCHEME SHARE [--log2-n 20] [--reps R] [--k K]   # one cell (what the driver runs)
 
@@ -9,11 +9,13 @@ Each cell (scheme, miss share s) is measured in a process of its own under a tim
 items in HBM, round(s * n) of them at random positions signed under valid keys that are NOT registered, the rest
 under the k registered keys.  On identical items, alternating on one stream, each call timed with device events
 after warm-up:
-  T    KeySet.verify_open_dev: lookup, challenge hash, keyed kernel, miss list, unkeyed equation over the list
+  T    KeySet.verify_open_dev (vargen: verify_vargen_open_dev): lookup, challenge hash, keyed kernel, miss list,
+       unkeyed equation over the list
   A    KeySet.verify_lookup_dev on the same items (closed set: the misses get 0)
   U    dsv_verify_<scheme>_dev on all n items
   U_s  dsv_verify_<scheme>_dev on the s * n missed items alone, gathered densely beforehand
-  H_s  dsv_challenge_<scheme>_dev on those same s * n items
+  H_s  dsv_challenge_<scheme>_dev on those same s * n items (vargen: dsv_challenge_single_dev — the scheme's
+       challenge is the one-nonce-point hash of (R, m), and that export is the kernel its verify calls launch)
 T's verdicts must equal U's (all 1), A's must be 1 exactly on the hits, and `misses` must equal round(s * n).
 Reported per cell: medians with min and max, and the conditions
   no_cost_when_nothing_misses (s = 0)   T <= A + (max - min of A)
@@ -51,7 +53,13 @@ def measure(scheme, share, k, log2_n, reps, warmup=3):
     # 2k keys, the first k registered: an item signed under key k + j is a valid signature that misses
     rng = np.random.default_rng(1357 + k)
     sk = _scalars(rng, 2 * k, 0x07)
-    K0, K1 = (E.public_keys(sk), None) if scheme == "single" else (E.public_keys(sk, 0), E.public_keys(sk, 1))
+    if scheme == "single":
+        K0, K1 = E.public_keys(sk), None
+    elif scheme == "double":
+        K0, K1 = E.public_keys(sk, 0), E.public_keys(sk, 1)
+    else:  # a key is the pair (PK, Gen), PK = sk * Gen: the unregistered pairs are valid keys too
+        K1 = E.public_keys(_scalars(rng, 2 * k, 0x07))
+        K0 = E.public_keys(sk, Gen=K1)
     missed = np.zeros(n, bool)
     missed[rng.permutation(n)[:nmiss]] = True
     idx = rng.integers(0, k, size=n) + k * missed
@@ -59,8 +67,10 @@ def measure(scheme, share, k, log2_n, reps, warmup=3):
     Rp = None
     if scheme == "single":
         u, R = E.sign_single(sk[idx], m, r)
-    else:
+    elif scheme == "double":
         u, R, Rp = E.sign_double(sk[idx], m, r)
+    else:
+        u, R = E.sign_vargen(sk[idx], K1[idx], m, r)
     P0, P1 = np.ascontiguousarray(K0[:k]), (np.ascontiguousarray(K1[:k]) if K1 is not None else None)
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     cols = [u, R] + ([Rp] if Rp is not None else []) + [K0[idx]] + ([K1[idx]] if K1 is not None else []) + [m]
@@ -75,7 +85,8 @@ def measure(scheme, share, k, log2_n, reps, warmup=3):
           "A": torch.empty(E.keyed_lookup_workspace_bytes(n), dtype=torch.uint8, device=dev),
           "U": torch.empty(E.workspace_bytes(n), dtype=torch.uint8, device=dev)}
     verify = getattr(E, "verify_%s_dev" % scheme)
-    fns = {"T": lambda: ks.verify_open_dev(*d_all, ok["T"], ws["T"], misses=misses["T"]),
+    verify_open = ks.verify_vargen_open_dev if scheme == "vargen" else ks.verify_open_dev
+    fns = {"T": lambda: verify_open(*d_all, ok["T"], ws["T"], misses=misses["T"]),
            "A": lambda: ks.verify_lookup_dev(*d_all, ok["A"], ws["A"], misses=misses["A"]),
            "U": lambda: verify(*d_all, ok["U"], ws["U"])}
     if nmiss:
@@ -84,7 +95,8 @@ def measure(scheme, share, k, log2_n, reps, warmup=3):
         c_s = torch.empty((nmiss, 32), dtype=torch.uint8, device=dev)
         npts = 2 if scheme == "double" else 1
         fns["U_s"] = lambda: verify(*d_miss, ok_s, ws_s)
-        fns["H_s"] = lambda: getattr(E, "challenge_%s_dev" % scheme)(*d_miss[1:1 + npts], d_miss[-1], c_s)
+        challenge = E.challenge_double_dev if scheme == "double" else E.challenge_single_dev
+        fns["H_s"] = lambda: challenge(*d_miss[1:1 + npts], d_miss[-1], c_s)
 
     def timed(fn):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -135,7 +147,7 @@ def main():
     ap.add_argument("--log2-n", type=int, default=20)
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--k", type=int, default=64)
-    ap.add_argument("--schemes", default="single,double")
+    ap.add_argument("--schemes", default="single,double,vargen")
     ap.add_argument("--shares", default="0,1/64,1/8,1/2,1")
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=300)
