@@ -814,6 +814,72 @@ int dsv_verify_vargen_keyed_open_dev(const dsv_keyset *ks, const void *u, const 
                                      size_t workspace_bytes, void *stream, void *misses);
 int dsv_verify_vargen_keyed_open(const dsv_keyset *ks, const uint8_t *u, const uint8_t *R_uv, const uint8_t *PK_uv,
                                  const uint8_t *Gen_uv, const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
+/* ---- the key cache for serialized records: open-set verify by compressed key ----------
+ * The caller of dsv_verify_keyed_open* usually holds its triples serialized: `Signature*::to_bytes()` records
+ * (sig64 = u || R, sig96 = u || R || R', nonce points compressed) and `PublicKey*::to_bytes()` records (pk32 = pk;
+ * pk64 = pk || pk' for the double scheme, pk || gen for the var-generator scheme; 32 B per point, compressed).
+ * Every key set carries a second index, over the compressed records of its own valid keys, built by every
+ * constructor and every append behind the affine index, in a device allocation of its own, made once for the
+ * set's capacity: dsv_keyset_bytes, dsv_keyset_index_bytes and dsv_keyset_info's `bytes` do not count it,
+ * dsv_keyset_wire_index_bytes(scheme, k) does (no GPU needed; 0 for an unknown scheme or k = 0; a reserved set: of
+ * its capacity) = the records (32 B per point, key-major, rounded up to 256) + as many uint32 slots as the affine
+ * index has (rounded up to 256), probed the same way from a home slot of its own
+ * (dsv_debug_keyset_wire_home_slot).  The record of a valid key is v with bit 255 set to the lowest bit of u — a
+ * pure function of its affine bytes — so a registered key is found by byte comparison and never decompressed;
+ * only the keys of the items that miss pay for a square root.
+ *   Lookup      key_idx_out[i] = the LOWEST index of a VALID registered key (dsv_keyset_key_ok: 1) whose canonical
+ *               compressed record equals item i's key record byte for byte, else DSV_KEY_NONE: what
+ *               dsv_keyset_lookup writes for the decompressed keys whenever the record is the canonical one.  Every
+ *               other record is a miss, not an error: another encoding of a registered point (u = 0 with the sign
+ *               bit set), v >= q, a non-square, a registered key's pk beside another key's gen, the record of a key
+ *               that was registered but is invalid.  misses as for dsv_keyset_lookup[_dev].
+ *   Verify      ok[i] = what dsv_verify_*_wire_dev writes for the same records, for every input: 1 iff every
+ *               `from_bytes` would succeed and `verify()` would return true.  Registering a key changes how fast the
+ *               verdict arrives and never the verdict.  misses: the number of items that took the unkeyed path.
+ *   _dev forms  checks and error codes of the keyed _dev calls in their order (a dead set DSV_ERR_NOT_INITIALIZED;
+ *               a set of another scheme DSV_ERR_INVALID_ARGUMENT; n = 0 DSV_OK with nothing enqueued; a NULL
+ *               pointer with n > 0, a short workspace, outputs that are not on the set's device:
+ *               DSV_ERR_INVALID_ARGUMENT), then alignment: `sig` and `pk` 16-byte aligned, key_idx_out and misses
+ *               4-byte aligned (DSV_ERR_INVALID_ARGUMENT).  On any error nothing is launched and nothing written.
+ *               Enqueue-only on `stream`, one straight chain, never synchronise, may be captured: the decode of the
+ *               signatures (dsv_verify_*_keyed_wire_dev's), the lookup of the key records, the challenge hash and
+ *               the keyed kernel over all n (a miss gets 0 there), the miss list, the decompression of the listed
+ *               items' key records (dsv_decompress_points_dev's arithmetic and bytes; its flag is AND-ed into the
+ *               item's validity), and the unkeyed equation over the list.  The last two launches are sized for n
+ *               items and read the list's length on the device.  A call carries the k it was enqueued with (the
+ *               stale-k rule of "key sets that grow"); an empty set (k = 0): every item takes the unkeyed path.
+ *   Workspace   dsv_keyed_open_wire_workspace_bytes(scheme, n) = (dsv_keyed_wire_workspace_bytes(scheme, n) -
+ *               dsv_keyed_workspace_bytes(n)) [the decoded signature columns] + the key columns of the misses (64 B
+ *               per item and key point, each column rounded up to 256) + dsv_keyed_open_workspace_bytes(n); device,
+ *               256-byte aligned; no GPU needed; 0 for an unknown scheme.
+ *   Host forms  host arrays, staged in chunks of 2^18 items on the key set's device (any alignment); block;
+ *               *misses is the sum over the chunks.
+ *   Before dsv_init a call of this group with a NULL handle returns DSV_ERR_NOT_INITIALIZED. */
+size_t dsv_keyset_wire_index_bytes(int scheme, size_t k);
+int dsv_keyset_lookup_wire_dev(const dsv_keyset *ks, const void *pk_records, size_t n, void *key_idx_out,
+                               void *misses, void *stream);
+int dsv_keyset_lookup_wire(const dsv_keyset *ks, const uint8_t *pk_records, size_t n, uint32_t *key_idx_out,
+                           size_t *misses);
+/* introspection: *slot = the home slot of a key record (32 B per key point) in the wire index of a set of
+ * `capacity` keys (no GPU needed): dsv_debug_keyset_home_slot's hash over the record's 8 (16) little-endian 32-bit
+ * words, & (cap - 1).  Unknown scheme, capacity = 0 or a NULL pointer: DSV_ERR_INVALID_ARGUMENT. */
+int dsv_debug_keyset_wire_home_slot(int scheme, size_t capacity, const uint8_t *record, uint64_t *slot);
+size_t dsv_keyed_open_wire_workspace_bytes(int scheme, size_t n);
+int dsv_verify_single_keyed_open_wire_dev(const dsv_keyset *ks, const void *sig64, const void *pk32, const void *m,
+                                          size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream,
+                                          void *misses);
+int dsv_verify_double_keyed_open_wire_dev(const dsv_keyset *ks, const void *sig96, const void *pk64, const void *m,
+                                          size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream,
+                                          void *misses);
+int dsv_verify_vargen_keyed_open_wire_dev(const dsv_keyset *ks, const void *sig64, const void *pk64, const void *m,
+                                          size_t n, void *ok, void *workspace, size_t workspace_bytes, void *stream,
+                                          void *misses);
+int dsv_verify_single_keyed_open_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint8_t *pk32,
+                                      const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
+int dsv_verify_double_keyed_open_wire(const dsv_keyset *ks, const uint8_t *sig96, const uint8_t *pk64,
+                                      const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
+int dsv_verify_vargen_keyed_open_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint8_t *pk64,
+                                      const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

@@ -114,6 +114,35 @@ extern "C" {
     pub fn dsv_keyset_capacity(ks: *const c_void, capacity: *mut usize) -> c_int;
     // key_ok of a set that may grow meanwhile: at most `room` bytes, *k_out = the k they belong to
     pub fn dsv_keyset_key_ok_n(ks: *const c_void, out: *mut u8, room: usize, k_out: *mut usize) -> c_int;
+    // the key cache for serialized records (include/dsv.h, "open-set verify by compressed key"): `to_bytes()`
+    // records of signatures (64 / 96 B) and keys (32 / 64 B), every scheme.  The verdicts of dsv_verify_*_wire_dev
+    // for every input; a key record that is the canonical record of a valid registered key is found in the set's
+    // wire index and never decompressed.  Raw exports.
+    pub fn dsv_keyset_wire_index_bytes(scheme: c_int, k: usize) -> usize;
+    pub fn dsv_keyset_lookup_wire_dev(ks: *const c_void, pk_records: *const c_void, n: usize,
+                                      key_idx_out: *mut c_void, misses: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn dsv_keyset_lookup_wire(ks: *const c_void, pk_records: *const u8, n: usize, key_idx_out: *mut u32,
+                                  misses: *mut usize) -> c_int;
+    pub fn dsv_debug_keyset_wire_home_slot(scheme: c_int, capacity: usize, record: *const u8, slot: *mut u64) -> c_int;
+    pub fn dsv_keyed_open_wire_workspace_bytes(scheme: c_int, n: usize) -> usize;
+    pub fn dsv_verify_single_keyed_open_wire_dev(ks: *const c_void, sig64: *const c_void, pk32: *const c_void,
+                                                 m: *const c_void, n: usize, ok: *mut c_void,
+                                                 workspace: *mut c_void, workspace_bytes: usize,
+                                                 stream: *mut c_void, misses: *mut c_void) -> c_int;
+    pub fn dsv_verify_double_keyed_open_wire_dev(ks: *const c_void, sig96: *const c_void, pk64: *const c_void,
+                                                 m: *const c_void, n: usize, ok: *mut c_void,
+                                                 workspace: *mut c_void, workspace_bytes: usize,
+                                                 stream: *mut c_void, misses: *mut c_void) -> c_int;
+    pub fn dsv_verify_vargen_keyed_open_wire_dev(ks: *const c_void, sig64: *const c_void, pk64: *const c_void,
+                                                 m: *const c_void, n: usize, ok: *mut c_void,
+                                                 workspace: *mut c_void, workspace_bytes: usize,
+                                                 stream: *mut c_void, misses: *mut c_void) -> c_int;
+    pub fn dsv_verify_single_keyed_open_wire(ks: *const c_void, sig64: *const u8, pk32: *const u8, m: *const u8,
+                                             n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    pub fn dsv_verify_double_keyed_open_wire(ks: *const c_void, sig96: *const u8, pk64: *const u8, m: *const u8,
+                                             n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    pub fn dsv_verify_vargen_keyed_open_wire(ks: *const c_void, sig64: *const u8, pk64: *const u8, m: *const u8,
+                                             n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.

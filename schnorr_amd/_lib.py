@@ -78,13 +78,20 @@ SYMBOLS = [
     # key sets that grow: reserved capacity, keys appended to a live set
     "dsv_keyset_create_reserved", "dsv_keyset_append", "dsv_keyset_append_wire", "dsv_keyset_append_mont_cols",
     "dsv_keyset_capacity", "dsv_keyset_key_ok_n",
+    # the key cache for serialized records: the wire index, open-set verify by compressed key
+    "dsv_keyset_wire_index_bytes", "dsv_keyset_lookup_wire_dev", "dsv_keyset_lookup_wire",
+    "dsv_debug_keyset_wire_home_slot", "dsv_keyed_open_wire_workspace_bytes",
+    "dsv_verify_single_keyed_open_wire_dev", "dsv_verify_double_keyed_open_wire_dev",
+    "dsv_verify_vargen_keyed_open_wire_dev", "dsv_verify_single_keyed_open_wire",
+    "dsv_verify_double_keyed_open_wire", "dsv_verify_vargen_keyed_open_wire",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
                  "dsv_rlc_workspace_bytes", "dsv_wire_rlc_workspace_bytes", "dsv_mixed_rlc_workspace_bytes",
                  "dsv_keyset_bytes", "dsv_keyed_workspace_bytes", "dsv_keyed_rlc_workspace_bytes",
                  "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes",
-                 "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes", "dsv_keyed_open_workspace_bytes")
+                 "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes", "dsv_keyed_open_workspace_bytes",
+                 "dsv_keyset_wire_index_bytes", "dsv_keyed_open_wire_workspace_bytes")
 
 
 class Column(ctypes.Structure):
@@ -132,12 +139,21 @@ def load():
     L.dsv_keyed_mont_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
     L.dsv_keyed_rlc_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
     L.dsv_keyset_index_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.dsv_keyset_wire_index_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.dsv_keyed_open_wire_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.dsv_debug_keyset_wire_home_slot.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.dsv_debug_keyset_home_slot.restype = ctypes.c_uint64
     L.dsv_debug_keyset_home_slot.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     vp, sz = ctypes.c_void_p, ctypes.c_size_t
     # (ks, u, R, PK, Gen, m, n, ok, workspace, workspace_bytes, stream, misses) / (ks, u, R, PK, Gen, m, n, ok, misses)
     L.dsv_verify_vargen_keyed_open_dev.argtypes = [vp] * 6 + [sz, vp, vp, sz, vp, vp]
     L.dsv_verify_vargen_keyed_open.argtypes = [vp] * 6 + [sz, vp, vp]
+    for scheme in ("single", "double", "vargen"):
+        # (ks, sig, pk, m, n, ok, workspace, workspace_bytes, stream, misses) / (ks, sig, pk, m, n, ok, misses)
+        getattr(L, "dsv_verify_%s_keyed_open_wire_dev" % scheme).argtypes = [vp] * 4 + [sz, vp, vp, sz, vp, vp]
+        getattr(L, "dsv_verify_%s_keyed_open_wire" % scheme).argtypes = [vp] * 4 + [sz, vp, vp]
+    L.dsv_keyset_lookup_wire_dev.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.dsv_keyset_lookup_wire.argtypes = [vp, vp, sz, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("dsv_version", "dsv_last_error", "dsv_debug_keyset_home_slot") + _SIZE_T_FUNCS:

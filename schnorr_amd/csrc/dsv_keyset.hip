@@ -17,10 +17,13 @@ std::vector<dsv_keyset*> g_keysets;
 constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
 constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
 
-// the tables and the index of a set (its device selected)
+// the tables and the two indices of a set (its device selected)
 void free_device_memory(dsv_keyset* ks) {
   if (ks->tables) (void)hipFree(ks->tables);
   if (ks->index) (void)hipFree(ks->index);
+  if (ks->wire_index) (void)hipFree(ks->wire_index);
+  ks->wire_index = nullptr;
+  ks->wire_slots = nullptr;
   ks->tables = nullptr;
   ks->key_ok = nullptr;
   ks->index = nullptr;
@@ -85,11 +88,15 @@ int register_keys(Context& ctx, dsv_keyset* ks, size_t first, size_t m, const Ke
   // the index, behind the table build (it reads key_ok)
   launch_append_key_index(P0, P1, ks->key_ok + first, np, first, m, ks->index, ks->slots, ks->slot_mask, x.s);
   HIP_TRY(hipGetLastError());
+  // the wire index: the same keys by their compressed records (keyed_open_wire.h)
+  launch_append_wire_index(P0, P1, ks->key_ok + first, np, first, m, ks->wire_index, ks->wire_slots, ks->slot_mask,
+                           x.s);
+  HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(x.s));
   return DSV_OK;
 }
 
-// both allocations of a set for ks->capacity keys, never moved afterwards: key_ok zeroed, every slot empty (on s)
+// the allocations of a set for ks->capacity keys, never moved afterwards: key_ok zeroed, every slot empty (on s)
 int allocate_keyset(dsv_keyset* ks, hipStream_t s) {
   const int scheme = ks->scheme;
   const size_t cap = ks->capacity;
@@ -102,6 +109,9 @@ int allocate_keyset(dsv_keyset* ks, hipStream_t s) {
   ks->slot_mask = keyset_index_cap(cap) - 1;
   HIP_TRY(hipMemsetAsync(ks->key_ok, 0, ks->bytes - keyset_table_bytes(scheme, cap), s));
   HIP_TRY(launch_clear_key_index(ks->slots, ks->slot_mask, s));
+  HIP_TRY(hipMalloc(&ks->wire_index, keyset_wire_index_total_bytes(scheme, cap)));
+  ks->wire_slots = reinterpret_cast<uint32_t*>(ks->wire_index + keyset_wire_records_bytes(scheme, cap));
+  HIP_TRY(launch_clear_key_index(ks->wire_slots, ks->slot_mask, s));
   return DSV_OK;
 }
 

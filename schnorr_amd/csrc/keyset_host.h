@@ -8,9 +8,10 @@
 #include "dsv_host.h"
 #include "keyed_lookup.h"
 #include "keyed_open.h"
+#include "keyed_open_wire.h"
 #include "keyed_wire.h"
 
-// Everything but k is fixed when the set is created: both allocations are sized for `capacity` keys and never
+// Everything but k is fixed when the set is created: the allocations are sized for `capacity` keys and never
 // move.  k is read under the registry's shared lock and raised by dsv_keyset_append under the exclusive one, so a
 // call that holds the shared lock sees one k from its first check to its last launch.
 struct dsv_keyset {
@@ -26,6 +27,10 @@ struct dsv_keyset {
   uint8_t* index = nullptr;
   uint32_t* slots = nullptr;
   size_t slot_mask = 0;  // keyset_index_cap(capacity) - 1
+  // the index over the compressed records of the set's own keys (keyed_open_wire.h), a third allocation: the
+  // records for `capacity` keys, then as many slots as the affine index has (slot_mask)
+  uint8_t* wire_index = nullptr;
+  uint32_t* wire_slots = nullptr;
   bool alive = false;
   // one appender at a time per set (shared with the appender: it outlives a handle destroyed under a waiting one)
   std::shared_ptr<std::mutex> append_mu = std::make_shared<std::mutex>();
@@ -159,5 +164,10 @@ int check_misses(const dsv_keyset* ks, const Context* ctx, const void* misses);
 // the lookup of n items on s; every pointer device memory of the set's device.  An empty set: everything misses.
 int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
                    uint32_t* misses, hipStream_t s);
+
+// ---- the key cache for serialized records (dsv_keyed_open_wire.hip, keyed_open_wire.h) ---------------------
+// enqueue_lookup for key records (32 B per key point, 16-byte aligned) through the set's wire index
+int enqueue_lookup_wire(const dsv_keyset* ks, const void* pk, size_t n, uint32_t* idx, uint32_t* misses,
+                        hipStream_t s);
 
 }  // namespace dsvh

@@ -912,6 +912,35 @@ def keyed_open_workspace_bytes(n):
     return int(_lib.load().dsv_keyed_open_workspace_bytes(ctypes.c_size_t(n)))
 
 
+def keyset_wire_index_bytes(scheme, k):
+    """dsv_keyset_wire_index_bytes: device bytes of the index over the compressed records of a key set's own keys
+    (KeySet.lookup_wire; no GPU needed); not part of keyset_bytes or keyset_index_bytes"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyset_wire_index_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
+
+
+def keyed_open_wire_workspace_bytes(scheme, n):
+    """dsv_keyed_open_wire_workspace_bytes: device bytes of KeySet.verify_open_wire_dev's workspace (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyed_open_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+
+
+def keyset_wire_home_slot(scheme, capacity, record):
+    """dsv_debug_keyset_wire_home_slot: where the probe for a key record (32 bytes per key point) starts in the
+    wire index of a set of `capacity` keys (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    rec = _arr(record, _SCHEMES[scheme][1][1])
+    if rec.shape[0] != 1:
+        raise ValueError("one key record at a time")
+    slot = ctypes.c_uint64()
+    _lib.check(_lib.load().dsv_debug_keyset_wire_home_slot(
+        ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(capacity), _p(rec), ctypes.byref(slot)))
+    return int(slot.value)
+
+
 KEY_NONE = 0xFFFFFFFF  # DSV_KEY_NONE: the index of a key that is not in the set
 
 
@@ -1010,6 +1039,9 @@ class KeySet:
         ks.verify_lookup_dev(u, R, PK, m, ok, workspace)      # (u, R, PK, Gen, m)
         ok, misses = ks.verify_open(u, R, PK, m)   # open-set verify (single, double): the unkeyed verdicts, a
         ks.verify_open_dev(u, R, PK, m, ok, workspace)        # registered key only makes them arrive sooner
+        idx, misses = ks.lookup_wire(pk)           # by key RECORD ([n, 32] or [n, 64], as from_wire takes them)
+        ok, misses = ks.verify_open_wire(sig, pk, m)          # open-set verify of serialized triples, every scheme:
+        ks.verify_open_wire_dev(sig, pk, m, ok, workspace)    # the unkeyed wire verdicts; a hit needs no square root
         ks = KeySet.reserved("single", 4096, PK)   # room for 4096 keys (PK may be omitted: an empty set)
         first = ks.append(PK_new)                  # in place: indices first .. first + m - 1; append_wire(records),
         ks.k, ks.capacity                          # append_mont_cols([pk96]) for the other key forms
@@ -1438,5 +1470,65 @@ class KeySet:
         wsp = _bytes_out(workspace, keyed_open_workspace_bytes(n), dev, "workspace")
         _lib.check(_lib.load().dsv_verify_vargen_keyed_open_dev(
             self._handle(), _tp(u, 32), _tp(R, 64), self._key_ptr(PK, "PK"), self._key_ptr(Gen, "Gen"), _tp(m, 32),
+            ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
+            self._misses_ptr(misses, dev)))
+
+    # ---- by key record: the index over the compressed records of the set's own keys ----------------------------
+    def _rec_bytes(self):
+        return _SCHEMES[self.scheme][1][1]
+
+    def _rec_ptr(self, t, width, name):
+        """a record column of the _dev forms: uint8 [n, width], 16-byte aligned (read in 16-byte loads)"""
+        if _t(t, width, name).data_ptr() % 16:
+            raise ValueError("%s: records must be 16-byte aligned" % name)
+        return ctypes.c_void_p(t.data_ptr())
+
+    def lookup_wire(self, pk):
+        """host array pk [n, 32] (two-point sets: [n, 64]) of key records -> (idx uint32 [n], misses): the lowest
+        index of a valid registered key whose canonical record these bytes are, KEY_NONE where there is none"""
+        rec = _arr(pk, self._rec_bytes())
+        n = rec.shape[0]
+        idx = np.zeros(n, dtype=np.uint32)
+        misses = ctypes.c_size_t()
+        _lib.check(_lib.load().dsv_keyset_lookup_wire(self._handle(), _p(rec), ctypes.c_size_t(n), _p(idx),
+                                                      ctypes.byref(misses)))
+        return idx, misses.value
+
+    def lookup_wire_dev(self, pk, idx_out, misses=None, stream=None):
+        """CUDA tensors pk [n, 32 | 64], idx_out int32 [n] (written as uint32, KEY_NONE = -1); misses as for
+        lookup_dev.  Enqueued on `stream` (default: torch's current stream of the batch's device); does not
+        synchronise."""
+        n, dev = _rows((pk, self._rec_bytes(), "pk"))
+        op = _idx(idx_out, n, dev, "idx_out")
+        if idx_out.dim() != 1 or idx_out.shape[0] != n:
+            raise ValueError("idx_out: expected [n] = [%d], got %r" % (n, tuple(idx_out.shape)))
+        _lib.check(_lib.load().dsv_keyset_lookup_wire_dev(
+            self._handle(), self._rec_ptr(pk, self._rec_bytes(), "pk"), ctypes.c_size_t(n), op,
+            self._misses_ptr(misses, dev), _stream_ptr(stream, dev)))
+
+    def verify_open_wire(self, sig, pk, m):
+        """Open-set verify of serialized triples (dsv_verify_*_keyed_open_wire; every scheme): host arrays sig
+        [n, 64] (double: [n, 96]), pk [n, 32] (two-point sets: [n, 64]), m [n, 32] -> (verdicts [n], misses).  The
+        verdicts are verify_*_wire's for every input; an item whose key record is not the canonical record of a
+        valid registered key is decided by the unkeyed equation in the same call, and misses counts those."""
+        sig, rec, m = _arr(sig, _SCHEMES[self.scheme][1][0]), _arr(pk, self._rec_bytes()), _arr(m, 32)
+        n = _same_n(sig, rec, m)
+        ok = np.zeros(n, dtype=np.uint8)
+        misses = ctypes.c_size_t()
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_open_wire" % self.scheme)(
+            self._handle(), _p(sig), _p(rec), _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
+        return ok, misses.value
+
+    def verify_open_wire_dev(self, sig, pk, m, ok, workspace, misses=None, stream=None):
+        """CUDA tensors sig [n, 64 | 96], pk [n, 32 | 64], m [n, 32]: verify_open_wire's verdicts into ok, enqueued
+        on `stream` (default: torch's current stream of the batch's device) as one chain of launches; does not
+        synchronise and may be captured.  workspace: >= keyed_open_wire_workspace_bytes(scheme, n) bytes; misses
+        as for lookup_dev."""
+        sb = _SCHEMES[self.scheme][1][0]
+        n, dev = _rows((sig, sb, "sig"), (pk, self._rec_bytes(), "pk"), (m, 32, "m"))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_open_wire_workspace_bytes(self.scheme, n), dev, "workspace")
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_open_wire_dev" % self.scheme)(
+            self._handle(), self._rec_ptr(sig, sb, "sig"), self._rec_ptr(pk, self._rec_bytes(), "pk"), _tp(m, 32),
             ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
             self._misses_ptr(misses, dev)))
