@@ -12,7 +12,7 @@
 //   dsv_keyset.hip    registered key sets: per-key tables, verify by key index (keyed.h)
 //   dsv_keyed_lookup.hip  key sets by key value: the index over a set's keys, lookup, closed-set verify (keyed_lookup.h)
 //   dsv_keyed_open.hip    key sets as a key cache: open-set verify, the misses take the unkeyed equation (keyed_open.h)
-//   dsv_keyed_open_wire.hip  the key cache for serialized records: the index over key records, open-set verify by
+//   dsv_keyed_open_wire.hip  the key cache for serialized records: open-set verify by
 //                         compressed key (keyed_open_wire.h)
 // The host pipeline itself (run_pipelined, run_multi) is a template: dsv_pipeline.h.
 // Nothing here is part of the C ABI (include/dsv.h); everything lives in namespace dsvh.

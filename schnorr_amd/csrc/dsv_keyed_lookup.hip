@@ -1,8 +1,9 @@
 // dsv_keyed_lookup.hip — registered key sets by key VALUE (include/dsv.h: dsv_keyset_lookup*,
-// dsv_verify_keyed_lookup*; keyed_lookup.h): the key columns of a batch, canonical affine bytes, are looked up
-// in the set's index and the batch is verified by the indices found — the closed-set form of verify: a key
-// that is not in the set is a rejection.  Device form: lookup (k_key_lookup), challenge hash, keyed kernel —
-// three launches on the caller's stream.  Host forms: the same per chunk through the context's staging.
+// dsv_keyset_lookup_wire*, dsv_verify_keyed_lookup*; keyed_lookup.h): the keys of a batch — canonical affine
+// bytes in columns, or compressed records — are looked up in the set's index of that form, and the batch is
+// verified by the indices found — the closed-set form of verify: a key that is not in the set is a rejection.
+// Device form: lookup (k_index_lookup), challenge hash, keyed kernel — three launches on the caller's stream.
+// Host forms: the same per chunk through the context's staging (run_by_value_host).
 #include "keyset_host.h"
 
 namespace dsvh {
@@ -15,13 +16,16 @@ int library_up(const dsv_keyset* ks) {
   return DSV_OK;
 }
 
-bool keys_null(int scheme, const void* key_a, const void* key_b) {
-  return !key_a || (keyset_points(scheme) == 2 && !key_b);
+// columns a batch's keys come in: one per key point (affine), or one of whole records
+static int key_columns(KeyForm form, int scheme) { return form == kKeyAffine ? keyset_points(scheme) : 1; }
+
+bool keys_null(KeyForm form, int scheme, const void* key_a, const void* key_b) {
+  return !key_a || (key_columns(form, scheme) == 2 && !key_b);
 }
-// the lookup kernel reads a key in 16-byte loads
-int check_key_alignment(int scheme, const void* key_a, const void* key_b) {
-  if (((uintptr_t)key_a & 15) || (keyset_points(scheme) == 2 && ((uintptr_t)key_b & 15)))
-    return fail(DSV_ERR_INVALID_ARGUMENT, "key columns must be 16-byte aligned");
+int check_key_alignment(KeyForm form, int scheme, const void* key_a, const void* key_b) {
+  if (((uintptr_t)key_a & 15) || (key_columns(form, scheme) == 2 && ((uintptr_t)key_b & 15)))
+    return fail(DSV_ERR_INVALID_ARGUMENT, "%s must be 16-byte aligned",
+                form == kKeyAffine ? "key columns" : "key records");
   return DSV_OK;
 }
 // a 4-byte-aligned word on the set's device (ctx: the set's context)
@@ -35,9 +39,7 @@ int check_misses(const dsv_keyset* ks, const Context* ctx, const void* misses) {
   return DSV_OK;
 }
 
-// the lookup of n items on s; every pointer device memory of the set's device.  An empty set has no index:
-// everything misses.
-int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
+int enqueue_lookup(const dsv_keyset* ks, KeyForm form, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
                    uint32_t* misses, hipStream_t s) {
   if (ks->k == 0) {
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx), (int)kSlotEmpty, n, s));
@@ -45,24 +47,86 @@ int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, s
     HIP_TRY(hipGetLastError());
     return DSV_OK;
   }
-  HIP_TRY(launch_key_lookup(static_cast<const uint8_t*>(key_a), static_cast<const uint8_t*>(key_b),
-                            keyset_points(ks->scheme), n, ks->index, ks->slots, ks->slot_mask, ks->k, idx, misses,
-                            s));
+  HIP_TRY(launch_index_lookup(form, static_cast<const uint8_t*>(key_a), static_cast<const uint8_t*>(key_b),
+                              keyset_points(ks->scheme), n, ks->index[form].rows, ks->index[form].slots,
+                              ks->slot_mask, ks->k, idx, misses, s));
   HIP_TRY(hipGetLastError());
   return DSV_OK;
 }
 
+int stage_keys(KeyForm form, int scheme, Stager& st, const uint8_t* key_a, const uint8_t* key_b, size_t off,
+               size_t cnt, uint8_t*& da, uint8_t*& db) {
+  const size_t item = keys_item_bytes(form, scheme) / (size_t)key_columns(form, scheme);
+  da = st.take(cnt * item);
+  db = key_columns(form, scheme) == 2 ? st.take(cnt * item) : nullptr;
+  H2D(da, key_a + off * item, cnt * item);
+  if (db) H2D(db, key_b + off * item, cnt * item);
+  return DSV_OK;
+}
+
+int stage_affine_chunk(int scheme, Stager& st, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
+                       const uint8_t* m, const uint8_t* key_a, const uint8_t* key_b, size_t off, size_t cnt,
+                       AffineChunk& c) {
+  const int ns = keyed_sig_points(scheme);
+  uint8_t* du = st.take(cnt * 32);
+  uint8_t* dm = st.take(cnt * 32);
+  c.idx = reinterpret_cast<uint32_t*>(st.take(cnt * 4));
+  c.ok = st.take(cnt);
+  uint8_t* dR = st.take(cnt * 64);
+  uint8_t* dRp = ns == 2 ? st.take(cnt * 64) : nullptr;
+  H2D(du, u + off * 32, cnt * 32);
+  H2D(dm, m + off * 32, cnt * 32);
+  H2D(dR, R_uv + off * 64, cnt * 64);
+  if (dRp) H2D(dRp, Rp_uv + off * 64, cnt * 64);
+  c.in = make_items(scheme, du, {dR, dRp}, dm);
+  return stage_keys(kKeyAffine, scheme, st, key_a, key_b, off, cnt, c.key_a, c.key_b);
+}
+
 namespace {
 
-uint32_t home_hash_host(int np, const uint8_t* key_a, const uint8_t* key_b) {
+// the hash of a key's little-endian words: `words` at a, then as many at b (null: none)
+uint32_t key_hash_host(const uint8_t* a, const uint8_t* b, int words) {
   KeyHash h;
-  for (int p = 0; p < np; p++) {
-    const uint8_t* b = p ? key_b : key_a;
-    for (int i = 0; i < 16; i++)
-      h.word((uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 |
-             (uint32_t)b[4 * i + 3] << 24);
-  }
+  for (const uint8_t* p : {a, b})
+    for (int i = 0; p && i < words; i++)
+      h.word((uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 |
+             (uint32_t)p[4 * i + 3] << 24);
   return h.finish();
+}
+
+int lookup_dev(KeyForm form, const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, void* key_idx_out,
+               void* misses, void* stream) {
+  if (int r = library_up(ks)) return r;
+  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
+  Context* cp = nullptr;
+  if (int r = check_set(ks, -1, n, cp)) return r;
+  if (n == 0) return DSV_OK;
+  if (keys_null(form, ks->scheme, key_a, key_b) || !key_idx_out)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int r = check_key_alignment(form, ks->scheme, key_a, key_b)) return r;
+  if ((uintptr_t)key_idx_out & 3) return fail(DSV_ERR_INVALID_ARGUMENT, "key_idx_out must be 4-byte aligned");
+  Context* octx = nullptr;
+  if (int r = device_context(key_idx_out, octx)) return r;
+  if (octx != cp)
+    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
+  if (int r = check_misses(ks, cp, misses)) return r;
+  DSV_ON_DEVICE(*cp);
+  return enqueue_lookup(ks, form, key_a, key_b, n, static_cast<uint32_t*>(key_idx_out),
+                        static_cast<uint32_t*>(misses), (hipStream_t)stream);
+}
+
+int lookup_host(KeyForm form, const dsv_keyset* ks, const uint8_t* key_a, const uint8_t* key_b, size_t n,
+                uint32_t* key_idx_out, size_t* misses) {
+  return run_by_value_host(
+      ks, -1, any_scheme, [=](int scheme) { return keys_null(form, scheme, key_a, key_b); },
+      [=](int scheme, size_t cnt) { return cnt * (keys_item_bytes(form, scheme) + 4) + 5 * 256; }, n, key_idx_out, 4,
+      misses, [=](Context&, int scheme, Stager& st, size_t off, size_t cnt, uint32_t* dmiss, const void*& dout) {
+        uint8_t *da, *db;
+        if (int r = stage_keys(form, scheme, st, key_a, key_b, off, cnt, da, db)) return r;
+        uint32_t* di = reinterpret_cast<uint32_t*>(st.take(cnt * 4));
+        dout = di;
+        return enqueue_lookup(ks, form, da, db, cnt, di, dmiss, 0);
+      });
 }
 
 }  // namespace
@@ -73,70 +137,42 @@ using namespace dsvh;
 extern "C" {
 
 size_t dsv_keyset_index_bytes(int scheme, size_t k) {
-  return scheme_ok(scheme) ? keyset_index_total_bytes(scheme, k) : 0;
+  return scheme_ok(scheme) ? keyset_index_total_bytes(kKeyAffine, scheme, k) : 0;
+}
+size_t dsv_keyset_wire_index_bytes(int scheme, size_t k) {
+  return scheme_ok(scheme) ? keyset_index_total_bytes(kKeyRecord, scheme, k) : 0;
 }
 size_t dsv_keyed_lookup_workspace_bytes(size_t n) { return align_up(4 * n, 256) + keyed_ws_bytes(n); }
 
 uint64_t dsv_debug_keyset_home_slot(int scheme, size_t k, const uint8_t* key_a, const uint8_t* key_b) {
-  if (!scheme_ok(scheme) || k == 0 || keys_null(scheme, key_a, key_b)) return ~(uint64_t)0;
-  return (uint64_t)home_hash_host(keyset_points(scheme), key_a, key_b) & ((uint64_t)keyset_index_cap(k) - 1);
+  if (!scheme_ok(scheme) || k == 0 || keys_null(kKeyAffine, scheme, key_a, key_b)) return ~(uint64_t)0;
+  return (uint64_t)key_hash_host(key_a, keyset_points(scheme) == 2 ? key_b : nullptr, 16) &
+         ((uint64_t)keyset_index_cap(k) - 1);
+}
+int dsv_debug_keyset_wire_home_slot(int scheme, size_t capacity, const uint8_t* record, uint64_t* slot) {
+  if (!scheme_ok(scheme)) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown scheme %d", scheme);
+  if (capacity == 0) return fail(DSV_ERR_INVALID_ARGUMENT, "a set of no capacity has no index");
+  if (!record || !slot) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  *slot = (uint64_t)key_hash_host(record, nullptr, 8 * keyset_points(scheme)) &
+          ((uint64_t)keyset_index_cap(capacity) - 1);
+  return DSV_OK;
 }
 
 int dsv_keyset_lookup_dev(const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, void* key_idx_out,
                           void* misses, void* stream) {
-  if (int r = library_up(ks)) return r;
-  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  Context* cp = nullptr;
-  if (int r = check_set(ks, -1, n, cp)) return r;
-  if (n == 0) return DSV_OK;
-  if (keys_null(ks->scheme, key_a, key_b) || !key_idx_out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int r = check_key_alignment(ks->scheme, key_a, key_b)) return r;
-  if ((uintptr_t)key_idx_out & 3) return fail(DSV_ERR_INVALID_ARGUMENT, "key_idx_out must be 4-byte aligned");
-  Context* octx = nullptr;
-  if (int r = device_context(key_idx_out, octx)) return r;
-  if (octx != cp)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "key set of device %d used on device %d", ks->device, octx->device);
-  if (int r = check_misses(ks, cp, misses)) return r;
-  DSV_ON_DEVICE(*cp);
-  return enqueue_lookup(ks, key_a, key_b, n, static_cast<uint32_t*>(key_idx_out), static_cast<uint32_t*>(misses),
-                        (hipStream_t)stream);
+  return lookup_dev(kKeyAffine, ks, key_a, key_b, n, key_idx_out, misses, stream);
 }
-
+int dsv_keyset_lookup_wire_dev(const dsv_keyset* ks, const void* pk_records, size_t n, void* key_idx_out,
+                               void* misses, void* stream) {
+  return lookup_dev(kKeyRecord, ks, pk_records, nullptr, n, key_idx_out, misses, stream);
+}
 int dsv_keyset_lookup(const dsv_keyset* ks, const uint8_t* key_a, const uint8_t* key_b, size_t n,
                       uint32_t* key_idx_out, size_t* misses) {
-  if (int r = library_up(ks)) return r;
-  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  Context* cp = nullptr;
-  if (int r = check_set(ks, -1, n, cp)) return r;
-  if (n == 0) {
-    if (misses) *misses = 0;
-    return DSV_OK;
-  }
-  if (keys_null(ks->scheme, key_a, key_b) || !key_idx_out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  Context& ctx = *cp;
-  DSV_HOST_LOCK();
-  const int np = keyset_points(ks->scheme);
-  const size_t chunk = n < kLookupHostChunk ? n : kLookupHostChunk;
-  if (int r = ensure_stage(ctx, chunk * (64 * (size_t)np + 4) + 5 * 256)) return r;
-  size_t total = 0;
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t cnt = n - off < chunk ? n - off : chunk;
-    Stager st(ctx.stage);
-    uint8_t* da = st.take(cnt * 64);
-    uint8_t* db = np == 2 ? st.take(cnt * 64) : nullptr;
-    uint32_t* di = reinterpret_cast<uint32_t*>(st.take(cnt * 4));
-    uint32_t* dmiss = reinterpret_cast<uint32_t*>(st.take(4));
-    H2D(da, key_a + off * 64, cnt * 64);
-    if (db) H2D(db, key_b + off * 64, cnt * 64);
-    if (int r = enqueue_lookup(ks, da, db, cnt, di, dmiss, 0)) return r;
-    uint32_t missed = 0;
-    D2H(key_idx_out + off, di, cnt * 4);
-    D2H(&missed, dmiss, 4);
-    HIP_TRY(hipStreamSynchronize(0));
-    total += missed;
-  }
-  if (misses) *misses = total;
-  return DSV_OK;
+  return lookup_host(kKeyAffine, ks, key_a, key_b, n, key_idx_out, misses);
+}
+int dsv_keyset_lookup_wire(const dsv_keyset* ks, const uint8_t* pk_records, size_t n, uint32_t* key_idx_out,
+                           size_t* misses) {
+  return lookup_host(kKeyRecord, ks, pk_records, nullptr, n, key_idx_out, misses);
 }
 
 int dsv_verify_keyed_lookup_dev(const dsv_keyset* ks, const void* u, const void* R_uv, const void* Rp_uv,
@@ -148,14 +184,15 @@ int dsv_verify_keyed_lookup_dev(const dsv_keyset* ks, const void* u, const void*
   return run_keyed_dev(
       ks, -1,
       [=](int scheme) {
-        return !u || !R_uv || (keyed_sig_points(scheme) == 2 && !Rp_uv) || !m || keys_null(scheme, key_a, key_b);
+        return !u || !R_uv || (keyed_sig_points(scheme) == 2 && !Rp_uv) || !m ||
+               keys_null(kKeyAffine, scheme, key_a, key_b);
       },
       [=](int) { return align_up(4 * n, 256); }, workspace, n, ok, workspace, workspace_bytes, stream,
       [=](const Context& ctx, int scheme, Stager& x, hipStream_t s, Items& in, const uint8_t*&) {
-        if (int r = check_key_alignment(scheme, key_a, key_b)) return r;
+        if (int r = check_key_alignment(kKeyAffine, scheme, key_a, key_b)) return r;
         if (int r = check_misses(ks, &ctx, misses)) return r;
         uint32_t* idx = reinterpret_cast<uint32_t*>(x.take(4 * n));
-        if (int r = enqueue_lookup(ks, key_a, key_b, n, idx, static_cast<uint32_t*>(misses), s)) return r;
+        if (int r = enqueue_lookup(ks, kKeyAffine, key_a, key_b, n, idx, static_cast<uint32_t*>(misses), s)) return r;
         in = make_items(scheme, u, {R_uv, keyed_sig_points(scheme) == 2 ? Rp_uv : nullptr}, m);
         return (int)DSV_OK;
       });
@@ -164,53 +201,20 @@ int dsv_verify_keyed_lookup_dev(const dsv_keyset* ks, const void* u, const void*
 int dsv_verify_keyed_lookup(const dsv_keyset* ks, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
                             const uint8_t* key_a, const uint8_t* key_b, const uint8_t* m, size_t n, uint8_t* ok,
                             size_t* misses) {
-  if (int r = library_up(ks)) return r;
-  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
-  Context* cp = nullptr;
-  if (int r = check_set(ks, -1, n, cp)) return r;
-  if (n == 0) {
-    if (misses) *misses = 0;
-    return DSV_OK;
-  }
-  const int scheme = ks->scheme, ns = keyed_sig_points(scheme), np = keyset_points(scheme);
-  if (!u || !R_uv || (ns == 2 && !Rp_uv) || !m || keys_null(scheme, key_a, key_b) || !ok)
-    return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
-  Context& ctx = *cp;
-  DSV_HOST_LOCK();
-  const size_t chunk = n < kLookupHostChunk ? n : kLookupHostChunk;
-  const size_t per_item = 32 + 32 + 4 + 1 + 64 * (size_t)(ns + np);
-  if (int r = ensure_stage(ctx, chunk * per_item + keyed_ws_bytes(chunk) + 12 * 256)) return r;
-  size_t total = 0;
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t cnt = n - off < chunk ? n - off : chunk;
-    Stager st(ctx.stage);
-    uint8_t* du = st.take(cnt * 32);
-    uint8_t* dm = st.take(cnt * 32);
-    uint32_t* di = reinterpret_cast<uint32_t*>(st.take(cnt * 4));
-    uint8_t* dok = st.take(cnt);
-    uint8_t* dR = st.take(cnt * 64);
-    uint8_t* dRp = ns == 2 ? st.take(cnt * 64) : nullptr;
-    uint8_t* da = st.take(cnt * 64);
-    uint8_t* db = np == 2 ? st.take(cnt * 64) : nullptr;
-    uint32_t* dmiss = reinterpret_cast<uint32_t*>(st.take(4));
-    void* ws = st.take(keyed_ws_bytes(cnt));
-    H2D(du, u + off * 32, cnt * 32);
-    H2D(dm, m + off * 32, cnt * 32);
-    H2D(dR, R_uv + off * 64, cnt * 64);
-    if (dRp) H2D(dRp, Rp_uv + off * 64, cnt * 64);
-    H2D(da, key_a + off * 64, cnt * 64);
-    if (db) H2D(db, key_b + off * 64, cnt * 64);
-    if (int r = enqueue_lookup(ks, da, db, cnt, di, dmiss, 0)) return r;
-    enqueue_keyed(ctx, ks, make_items(scheme, du, {dR, dRp}, dm), di, cnt, dok, ws, 0);
-    HIP_TRY(hipGetLastError());
-    uint32_t missed = 0;
-    D2H(ok + off, dok, cnt);
-    D2H(&missed, dmiss, 4);
-    HIP_TRY(hipStreamSynchronize(0));
-    total += missed;
-  }
-  if (misses) *misses = total;
-  return DSV_OK;
+  return run_by_value_host(
+      ks, -1, any_scheme,
+      [=](int scheme) { return affine_inputs_null(scheme, u, R_uv, Rp_uv, m, key_a, key_b); },
+      [=](int scheme, size_t cnt) { return affine_chunk_bytes(scheme, cnt) + keyed_ws_bytes(cnt); }, n, ok, 1, misses,
+      [=](Context& ctx, int scheme, Stager& st, size_t off, size_t cnt, uint32_t* dmiss, const void*& dout) {
+        AffineChunk c;
+        if (int r = stage_affine_chunk(scheme, st, u, R_uv, Rp_uv, m, key_a, key_b, off, cnt, c)) return r;
+        void* ws = st.take(keyed_ws_bytes(cnt));
+        dout = c.ok;
+        if (int r = enqueue_lookup(ks, kKeyAffine, c.key_a, c.key_b, cnt, c.idx, dmiss, 0)) return r;
+        enqueue_keyed(ctx, ks, c.in, c.idx, cnt, c.ok, ws, 0);
+        HIP_TRY(hipGetLastError());
+        return (int)DSV_OK;
+      });
 }
 
 int dsv_debug_keyset_index_stats(const dsv_keyset* ks, uint64_t out[4]) {
@@ -227,8 +231,8 @@ int dsv_debug_keyset_index_stats(const dsv_keyset* ks, uint64_t out[4]) {
   const size_t cap = ks->slot_mask + 1, key_bytes = 64 * (size_t)np;
   std::vector<uint8_t> keys(k * key_bytes);
   std::vector<uint32_t> slots(cap);
-  HIP_TRY(hipMemcpy(keys.data(), ks->index, keys.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(slots.data(), ks->slots, cap * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(keys.data(), ks->index[kKeyAffine].rows, keys.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slots.data(), ks->index[kKeyAffine].slots, cap * 4, hipMemcpyDeviceToHost));
   out[0] = cap;
   for (size_t slot = 0; slot < cap; slot++) {
     const uint32_t occ = slots[slot];
@@ -237,7 +241,7 @@ int dsv_debug_keyset_index_stats(const dsv_keyset* ks, uint64_t out[4]) {
     if (occ >= k) continue;  // a key newer than this call: an empty slot, as the lookup reads it
     out[1]++;
     const uint8_t* kb = keys.data() + occ * key_bytes;
-    const size_t home = home_hash_host(np, kb, kb + 64) & ks->slot_mask;
+    const size_t home = key_hash_host(kb, np == 2 ? kb + 64 : nullptr, 16) & ks->slot_mask;
     const uint64_t probes = ((slot - home) & ks->slot_mask) + 1;  // slots read to find it
     if (slot != home) out[2]++;
     if (probes > out[3]) out[3] = probes;

@@ -17,17 +17,15 @@ std::vector<dsv_keyset*> g_keysets;
 constexpr size_t kKeyedHostChunk = (size_t)1 << 18;
 constexpr size_t kMaxKeys = 0xffffffffu;  // indices are uint32
 
-// the tables and the two indices of a set (its device selected)
+// the tables and the indices of a set (its device selected)
 void free_device_memory(dsv_keyset* ks) {
   if (ks->tables) (void)hipFree(ks->tables);
-  if (ks->index) (void)hipFree(ks->index);
-  if (ks->wire_index) (void)hipFree(ks->wire_index);
-  ks->wire_index = nullptr;
-  ks->wire_slots = nullptr;
   ks->tables = nullptr;
   ks->key_ok = nullptr;
-  ks->index = nullptr;
-  ks->slots = nullptr;
+  for (dsv_keyset::KeyIndex& ix : ks->index) {
+    if (ix.rows) (void)hipFree(ix.rows);
+    ix = {};
+  }
 }
 
 void free_sets_of(int device) {  // (exclusive lock held)
@@ -70,7 +68,7 @@ struct Scratch {
 
 // The one body that registers keys: the m keys of `form` become rows first .. first + m - 1 of ks — their affine
 // points staged into a scratch of this call's (np x m x 64 B, then the form's own bytes from the next 256-byte
-// boundary), their tables and key_ok bytes built, their bytes and slots added to the index — on a stream of the
+// boundary), their tables and key_ok bytes built, their rows and slots added to both indices — on a stream of the
 // call's own (x.s; x.dev: the scratch), synchronised before it returns.  Writes only rows >= first and slots that
 // are empty.  ks->k is the caller's to raise.  (ks's device memory held: a new set, or the registry's shared lock.)
 int register_keys(Context& ctx, dsv_keyset* ks, size_t first, size_t m, const KeysetForm& form, Scratch& x) {
@@ -85,14 +83,21 @@ int register_keys(Context& ctx, dsv_keyset* ks, size_t first, size_t m, const Ke
   launch_build_key_tables(P0, P1, valid, np, m, ks->tables + first * (size_t)np * kKeyPointWords, ks->key_ok + first,
                           x.s);
   HIP_TRY(hipGetLastError());
-  // the index, behind the table build (it reads key_ok)
-  launch_append_key_index(P0, P1, ks->key_ok + first, np, first, m, ks->index, ks->slots, ks->slot_mask, x.s);
-  HIP_TRY(hipGetLastError());
-  // the wire index: the same keys by their compressed records (keyed_open_wire.h)
-  launch_append_wire_index(P0, P1, ks->key_ok + first, np, first, m, ks->wire_index, ks->wire_slots, ks->slot_mask,
-                           x.s);
-  HIP_TRY(hipGetLastError());
+  // the indices, behind the table build (they read key_ok): the affine one, then the same keys by their records
+  for (KeyForm f : {kKeyAffine, kKeyRecord}) {
+    launch_index_append(f, P0, P1, ks->key_ok + first, np, first, m, ks->index[f].rows, ks->index[f].slots,
+                        ks->slot_mask, x.s);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(x.s));
+  return DSV_OK;
+}
+
+// the `f` index of a set for ks->capacity keys: the rows, then the slots
+int allocate_index(dsv_keyset* ks, KeyForm f) {
+  dsv_keyset::KeyIndex& ix = ks->index[f];
+  HIP_TRY(hipMalloc(&ix.rows, keyset_index_total_bytes(f, ks->scheme, ks->capacity)));
+  ix.slots = reinterpret_cast<uint32_t*>(ix.rows + keyset_index_rows_bytes(f, ks->scheme, ks->capacity));
   return DSV_OK;
 }
 
@@ -104,14 +109,12 @@ int allocate_keyset(dsv_keyset* ks, hipStream_t s) {
   if (cap == 0) return DSV_OK;
   HIP_TRY(hipMalloc(&ks->tables, ks->bytes));
   ks->key_ok = reinterpret_cast<uint8_t*>(ks->tables) + keyset_table_bytes(scheme, cap);
-  HIP_TRY(hipMalloc(&ks->index, keyset_index_total_bytes(scheme, cap)));
-  ks->slots = reinterpret_cast<uint32_t*>(ks->index + keyset_index_keys_bytes(scheme, cap));
   ks->slot_mask = keyset_index_cap(cap) - 1;
+  if (int r = allocate_index(ks, kKeyAffine)) return r;
   HIP_TRY(hipMemsetAsync(ks->key_ok, 0, ks->bytes - keyset_table_bytes(scheme, cap), s));
-  HIP_TRY(launch_clear_key_index(ks->slots, ks->slot_mask, s));
-  HIP_TRY(hipMalloc(&ks->wire_index, keyset_wire_index_total_bytes(scheme, cap)));
-  ks->wire_slots = reinterpret_cast<uint32_t*>(ks->wire_index + keyset_wire_records_bytes(scheme, cap));
-  HIP_TRY(launch_clear_key_index(ks->wire_slots, ks->slot_mask, s));
+  HIP_TRY(launch_clear_key_index(ks->index[kKeyAffine].slots, ks->slot_mask, s));
+  if (int r = allocate_index(ks, kKeyRecord)) return r;
+  HIP_TRY(launch_clear_key_index(ks->index[kKeyRecord].slots, ks->slot_mask, s));
   return DSV_OK;
 }
 

@@ -1,54 +1,41 @@
-// k_keyed_lookup.hip — the index of a registered key set over its own keys (keyed_lookup.h): its build, one
-// lane per key behind the table build, the insertion of further keys into a live index (dsv_keyset_append),
-// and the lookup that turns a batch's key columns into the key_idx column of the keyed kernels, one lane per
-// item.  Bytes in, indices out: no field arithmetic, no table of keyed.h is read.
+// k_keyed_lookup.hip — the indices of a registered key set over its own keys (keyed_lookup.h): the insertion of
+// keys into an index, fresh or live (every constructor and dsv_keyset_append), one lane per key behind the table
+// build, and the lookup that turns a batch's keys into the key_idx column of the keyed kernels, one lane per
+// item.  Both are one kernel each over a key form — the affine bytes or the compressed records of the same keys.
+// Bytes in, indices out: no field arithmetic, no table of keyed.h is read, a hit costs no square root.
 #include "keyed_lookup.h"
 
 namespace dsv {
 namespace {
 
-// a key's bytes in registers: 4 x 16 B per point
-template <int NP>
-struct KeyWords {
-  uint4 q[4 * NP];
+// a row in registers: W x 16 B
+template <int W>
+struct Words {
+  uint4 q[W];
 };
-template <int NP>
-__device__ __forceinline__ KeyWords<NP> load_key(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                  size_t i) {
-  KeyWords<NP> w;
-  const uint4* pa = reinterpret_cast<const uint4*>(a + i * 64);
+template <int W>
+__device__ __forceinline__ Words<W> load_row(const uint8_t* __restrict__ rows, size_t i) {
+  Words<W> w;
+  const uint4* p = reinterpret_cast<const uint4*>(rows + i * (size_t)(16 * W));
 #pragma unroll
-  for (int j = 0; j < 4; j++) w.q[j] = pa[j];
-  if (NP == 2) {
-    const uint4* pb = reinterpret_cast<const uint4*>(b + i * 64);
-#pragma unroll
-    for (int j = 0; j < 4; j++) w.q[4 * (NP - 1) + j] = pb[j];
-  }
+  for (int j = 0; j < W; j++) w.q[j] = p[j];
   return w;
 }
 __device__ __forceinline__ bool same16(const uint4& x, const uint4& y) {
   return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) == 0u;
 }
-// w against 4 * NP consecutive 16-byte words at p
-template <int NP>
-__device__ __forceinline__ bool same_key(const KeyWords<NP>& w, const uint4* __restrict__ p) {
+template <int W>
+__device__ __forceinline__ bool same_words(const Words<W>& a, const Words<W>& b) {
   bool eq = true;
 #pragma unroll
-  for (int j = 0; j < 4 * NP; j++) eq &= same16(w.q[j], p[j]);
+  for (int j = 0; j < W; j++) eq &= same16(a.q[j], b.q[j]);
   return eq;
 }
-template <int NP>
-__device__ __forceinline__ bool same_words(const KeyWords<NP>& a, const KeyWords<NP>& b) {
-  bool eq = true;
-#pragma unroll
-  for (int j = 0; j < 4 * NP; j++) eq &= same16(a.q[j], b.q[j]);
-  return eq;
-}
-template <int NP>
-__device__ __forceinline__ uint32_t home_hash(const KeyWords<NP>& w) {
+template <int W>
+__device__ __forceinline__ uint32_t home_hash(const Words<W>& w) {
   KeyHash h;
 #pragma unroll
-  for (int j = 0; j < 4 * NP; j++) {
+  for (int j = 0; j < W; j++) {
     h.word(w.q[j].x);
     h.word(w.q[j].y);
     h.word(w.q[j].z);
@@ -57,81 +44,125 @@ __device__ __forceinline__ uint32_t home_hash(const KeyWords<NP>& w) {
   return h.finish();
 }
 
+// ---- the key forms: W = 16-byte words per row; source(P0, P1, j) = the row of the affine source key j (u || v,
+// 64 B per point), item(key_a, key_b, i) = the row of a batch's item i, occupant(...) = the row of the occupant
+// `old` of a slot as the append kernel compares it: a key of an earlier call (old < first) from the index's own
+// rows, a lane of this launch from the source points ----------------------------------------------------------
+
+// kKeyAffine: 64 B per point, the source key's bytes as they are; an item's columns are read the same way
+template <int NP>
+struct AffineKey {
+  static constexpr int W = 4 * NP;
+  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                    size_t i) {
+    Words<W> w;
+    const uint4* pa = reinterpret_cast<const uint4*>(a + i * 64);
+#pragma unroll
+    for (int j = 0; j < 4; j++) w.q[j] = pa[j];
+    if (NP == 2) {
+      const uint4* pb = reinterpret_cast<const uint4*>(b + i * 64);
+#pragma unroll
+      for (int j = 0; j < 4; j++) w.q[4 * (NP - 1) + j] = pb[j];
+    }
+    return w;
+  }
+  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                  size_t i) {
+    return source(a, b, i);
+  }
+  // one pointer select, one load (a pair of loads under `old < first` costs NP = 2 nine VGPRs and a wave of
+  // occupancy)
+  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
+                                                      const uint8_t* rows, uint32_t old, size_t first) {
+    const bool older = old < first;
+    const uint8_t* pa = older ? rows + (size_t)old * (size_t)(64 * NP) : P0 + (size_t)(old - first) * 64;
+    const uint8_t* pb = older ? pa + 64 : P1 + (size_t)(old - first) * 64;
+    return source(pa, pb, 0);
+  }
+};
+
+// kKeyRecord: 32 B per point, the compressed record of the source point — v, bit 255 = the lowest bit of u —
+// formed by byte operations; an item's record is one row at key_a (key_b unused)
+template <int NP>
+struct RecordKey {
+  static constexpr int W = 2 * NP;
+  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                    size_t i) {
+    Words<W> w;
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+      const uint4* pt = reinterpret_cast<const uint4*>((p ? b : a) + i * 64);
+      const uint32_t sign = pt[0].x << 31;
+      w.q[2 * p] = pt[2];
+      w.q[2 * p + 1] = pt[3];
+      w.q[2 * p + 1].w = (w.q[2 * p + 1].w & 0x7fffffffu) | sign;
+    }
+    return w;
+  }
+  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__,
+                                                  size_t i) {
+    return load_row<W>(a, i);
+  }
+  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
+                                                      const uint8_t* rows, uint32_t old, size_t first) {
+    return old < first ? load_row<W>(rows, old) : source(P0, P1, old - first);
+  }
+};
+
+// the lookup's tail, per block: the waves' sums meet in LDS, one atomic per block that missed at all
+__device__ __forceinline__ void add_block_misses(uint32_t missed, uint32_t& block_misses,
+                                                 uint32_t* __restrict__ misses) {
+#pragma unroll
+  for (int off = warpSize / 2; off > 0; off >>= 1) missed += __shfl_down(missed, off);
+  if ((threadIdx.x & (warpSize - 1)) == 0 && missed) atomicAdd(&block_misses, missed);
+  __syncthreads();
+  if (threadIdx.x == 0 && block_misses) atomicAdd(misses, block_misses);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
-// One lane per key: its bytes go into the index's own copy; a valid key then claims the first empty slot from
-// its home slot on.  An occupied slot holds a key that differs (go on) or an equal one registered twice: the
-// slot then keeps the lower index.  A slot never returns to empty and its occupant only ever changes to an
-// equal key, so every lane of equal keys walks the same slots and stops at the same one.  Occupants are
-// compared by the source points, which no lane writes.  The table is at most half full: the walk ends.
+// m keys, indices first .. first + m - 1, into an index that already holds the keys below `first` (a fresh set:
+// first = 0) and that lookups enqueued earlier may be walking.  One lane per new key (P0 / P1, key_ok: the m new
+// keys' source points and verdicts; rows / slots: the whole index): its row goes into the index's own copy at
+// first + j, fenced; a valid key then claims the first empty slot from its home slot on.  An occupied slot holds a
+// key that differs (go on) or an equal one registered twice: the slot then keeps the lower index (atomicMin), so a
+// key appended twice, or one already registered, keeps its first index.  An occupant below `first` was registered
+// by an earlier call: it is compared by the index's own copy, which no lane of this launch writes (rows < first);
+// an occupant from `first` on is a lane of this launch and is compared by the source points, which nobody writes
+// (Form::occupant).  Why the walk is right:
+//   - a slot never returns to empty, and its occupant only ever changes to an equal key with a lower index, so
+//     every lane of equal keys walks the same slots and stops at the same one;
+//   - the table is at most half full (cap >= 2 * capacity), so the walk ends at an empty slot;
+//   - a lookup that runs beside this launch carries the k of its own call (< first + 1) and reads every occupant
+//     >= k as an empty slot: it never follows an index into a row this launch is still writing.
+// Two valid keys have equal records iff they have equal affine bytes, so both forms' indices
+// hold the same keys at the same lowest indices.
 // ------------------------------------------------------------------------------------------
-template <int NP>
+template <class Form>
 __global__ void __launch_bounds__(kLookupBlock)
-k_build_key_index(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
-                  const uint8_t* __restrict__ key_ok, size_t k, uint8_t* __restrict__ keys,
-                  uint32_t* __restrict__ slots, size_t mask) {
-  const size_t key = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (key >= k) return;
-  const KeyWords<NP> w = load_key<NP>(P0, P1, key);
-  uint4* own = reinterpret_cast<uint4*>(keys + key * (size_t)(64 * NP));
-#pragma unroll
-  for (int j = 0; j < 4 * NP; j++) own[j] = w.q[j];
-  if (key_ok[key] == 0) return;
-  const uint32_t me = (uint32_t)key;
-  size_t slot = home_hash<NP>(w) & mask;
-#pragma unroll 1
-  for (size_t probe = 0;; probe++) {
-    const uint32_t old = atomicCAS(&slots[slot], kSlotEmpty, me);
-    if (old == kSlotEmpty) return;
-    if (old < k && same_words<NP>(w, load_key<NP>(P0, P1, old))) {
-      atomicMin(&slots[slot], me);
-      return;
-    }
-    if (probe == mask) return;  // unreachable: the table is at most half full, so an empty slot comes first
-    slot = (slot + 1) & mask;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// dsv_keyset_append: m further keys, indices first .. first + m - 1, into an index that already holds the keys
-// below `first` and that lookups enqueued earlier may be walking.  One lane per new key (P0 / P1, key_ok: the m
-// new keys' rows; keys / slots: the whole index): its bytes go into the index's own copy at row first + j,
-// fenced; a valid key then claims the first empty slot from its home slot on, exactly as in the build.  An
-// occupant below `first` was registered by an earlier call: it is compared by the index's own copy, which no
-// lane of this launch writes (rows < first); an occupant from `first` on is a lane of this launch and is
-// compared by the source points, which nobody writes.  An equal occupant keeps the lower index (atomicMin), so
-// a key appended twice, or one already registered, keeps its first index.  As in the build:
-// a slot never returns to empty, an occupant only ever changes to an equal key with a lower index, and the
-// table is at most half full (cap >= 2 * capacity), so the walk ends.  A lookup that runs beside this launch
-// carries the k of its own call (< first + 1) and reads every occupant >= k as an empty slot: it never follows
-// an index into a row this launch is still writing.
-// ------------------------------------------------------------------------------------------
-template <int NP>
-__global__ void __launch_bounds__(kLookupBlock)
-k_append_key_index(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
-                   const uint8_t* __restrict__ key_ok, size_t first, size_t m, uint8_t* keys,
-                   uint32_t* __restrict__ slots, size_t mask) {
+k_index_append(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1, const uint8_t* __restrict__ key_ok,
+               size_t first, size_t m, uint8_t* rows, uint32_t* __restrict__ slots, size_t mask) {
+  constexpr int W = Form::W;
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
-  const KeyWords<NP> w = load_key<NP>(P0, P1, j);
-  uint4* own = reinterpret_cast<uint4*>(keys + (first + j) * (size_t)(64 * NP));
+  const Words<W> w = Form::source(P0, P1, j);
+  uint4* own = reinterpret_cast<uint4*>(rows + (first + j) * (size_t)(16 * W));
 #pragma unroll
-  for (int q = 0; q < 4 * NP; q++) own[q] = w.q[q];
+  for (int q = 0; q < W; q++) own[q] = w.q[q];
   __threadfence();
   if (key_ok[j] == 0) return;
   const uint32_t me = (uint32_t)(first + j);
-  size_t slot = home_hash<NP>(w) & mask;
+  size_t slot = home_hash<W>(w) & mask;
 #pragma unroll 1
   for (size_t probe = 0;; probe++) {
     const uint32_t old = atomicCAS(&slots[slot], kSlotEmpty, me);
     if (old == kSlotEmpty) return;
-    // the occupant's bytes: an earlier call's key from the index's copy, a lane of this launch from the source
-    const bool older = old < first;
-    const uint8_t* pa = older ? keys + (size_t)old * (size_t)(64 * NP) : P0 + (size_t)(old - first) * 64;
-    const uint8_t* pb = older ? pa + 64 : P1 + (size_t)(old - first) * 64;
-    const bool equal = old < first + m && same_words<NP>(w, load_key<NP>(pa, pb, 0));
-    if (equal) {
+    // (no slot holds an index >= first + m; were there one, the lane reads its own row instead, in bounds, and
+    // goes on — the load stands in front of the test: behind it, AffineKey<2> takes 72 VGPRs instead of 66)
+    const bool known = old < first + m;
+    const Words<W> occ = Form::occupant(P0, P1, rows, known ? old : me, first);
+    if (known && same_words<W>(w, occ)) {
       atomicMin(&slots[slot], me);
       return;
     }
@@ -141,31 +172,32 @@ k_append_key_index(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P
 }
 
 // ------------------------------------------------------------------------------------------
-// One lane per item, grid-stride: the item's key bytes in registers, a walk from the home slot that compares
-// against the index's copy of each occupant's bytes and ends at the first empty slot.  k: the set's key count
-// when the call was enqueued.  An occupant >= k was appended since: it is read as an empty slot and ends the
-// walk.  That is exact: every key below k whose walk passes this slot was placed while the slot was still
-// empty, so it sits in front of it.
+// One lane per item, grid-stride: the item's row in registers, a walk from the home slot that compares against
+// the index's copy of each occupant's row and ends at the first empty slot.  k: the set's key count when the call
+// was enqueued.  An occupant >= k was appended since: it is read as an empty slot and ends the walk.  That is
+// exact: every key below k whose walk passes this slot was placed while the slot was still empty, so it sits in
+// front of it.
 // ------------------------------------------------------------------------------------------
-template <int NP>
+template <class Form>
 __global__ void __launch_bounds__(kLookupBlock)
-k_key_lookup(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ key_b, size_t n,
-             const uint8_t* __restrict__ keys, const uint32_t* __restrict__ slots, size_t mask, size_t k,
-             uint32_t* __restrict__ key_idx, uint32_t* __restrict__ misses) {
+k_index_lookup(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ key_b, size_t n,
+               const uint8_t* __restrict__ rows, const uint32_t* __restrict__ slots, size_t mask, size_t k,
+               uint32_t* __restrict__ key_idx, uint32_t* __restrict__ misses) {
+  constexpr int W = Form::W;
   __shared__ uint32_t block_misses;
   if (threadIdx.x == 0) block_misses = 0;
   __syncthreads();
   uint32_t missed = 0;
 #pragma unroll 1
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const KeyWords<NP> w = load_key<NP>(key_a, key_b, i);
-    size_t slot = home_hash<NP>(w) & mask;
+    const Words<W> w = Form::item(key_a, key_b, i);
+    size_t slot = home_hash<W>(w) & mask;
     uint32_t found = kSlotEmpty;
 #pragma unroll 1
     for (size_t probe = 0;; probe++) {
       const uint32_t occ = slots[slot];
       if (occ >= k) break;  // empty (kSlotEmpty >= k), or a key newer than this call
-      if (same_key<NP>(w, reinterpret_cast<const uint4*>(keys + (size_t)occ * (size_t)(64 * NP)))) {
+      if (same_words<W>(w, load_row<W>(rows, occ))) {
         found = occ;
         break;
       }
@@ -176,13 +208,20 @@ k_key_lookup(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ key_
     missed += found == kSlotEmpty ? 1u : 0u;
   }
   if (!misses) return;  // (uniform: every lane of the grid takes the same side)
-  // per block: the waves' sums meet in LDS, one atomic per block that missed at all
-#pragma unroll
-  for (int off = warpSize / 2; off > 0; off >>= 1) missed += __shfl_down(missed, off);
-  if ((threadIdx.x & (warpSize - 1)) == 0 && missed) atomicAdd(&block_misses, missed);
-  __syncthreads();
-  if (threadIdx.x == 0 && block_misses) atomicAdd(misses, block_misses);
+  add_block_misses(missed, block_misses, misses);
 }
+
+namespace {
+// go(Form{}) for the form of `npoints`-point keys
+template <class Go>
+void with_key_form(KeyForm form, int npoints, Go go) {
+  if (form == kKeyAffine) {
+    if (npoints == 1) go(AffineKey<1>{}); else go(AffineKey<2>{});
+  } else {
+    if (npoints == 1) go(RecordKey<1>{}); else go(RecordKey<2>{});
+  }
+}
+}  // namespace
 
 // one word, written by a kernel of its own (launch_store_word)
 __global__ void k_store_word(uint32_t* __restrict__ p, uint32_t v) {
@@ -196,35 +235,26 @@ hipError_t launch_clear_key_index(uint32_t* slots, size_t mask, hipStream_t s) {
   return hipMemsetAsync(slots, 0xff, (mask + 1) * 4, s);
 }
 
-void launch_append_key_index(const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints, size_t first,
-                             size_t m, uint8_t* keys, uint32_t* slots, size_t mask, hipStream_t s) {
+void launch_index_append(KeyForm form, const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints,
+                         size_t first, size_t m, uint8_t* rows, uint32_t* slots, size_t mask, hipStream_t s) {
   if (m == 0) return;
   const dim3 grid(grid_for(m, kLookupBlock)), block(kLookupBlock);
-  if (first == 0) {  // nothing registered yet: the build, which compares by the source points alone
-    if (npoints == 1)
-      hipLaunchKernelGGL(k_build_key_index<1>, grid, block, 0, s, P0, P1, key_ok, m, keys, slots, mask);
-    else
-      hipLaunchKernelGGL(k_build_key_index<2>, grid, block, 0, s, P0, P1, key_ok, m, keys, slots, mask);
-  } else if (npoints == 1) {
-    hipLaunchKernelGGL(k_append_key_index<1>, grid, block, 0, s, P0, P1, key_ok, first, m, keys, slots, mask);
-  } else {
-    hipLaunchKernelGGL(k_append_key_index<2>, grid, block, 0, s, P0, P1, key_ok, first, m, keys, slots, mask);
-  }
+  with_key_form(form, npoints, [&](auto f) {
+    hipLaunchKernelGGL(k_index_append<decltype(f)>, grid, block, 0, s, P0, P1, key_ok, first, m, rows, slots, mask);
+  });
 }
 
-hipError_t launch_key_lookup(const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
-                             const uint8_t* keys, const uint32_t* slots, size_t mask, size_t k,
-                             uint32_t* key_idx, uint32_t* misses, hipStream_t s) {
+hipError_t launch_index_lookup(KeyForm form, const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
+                               const uint8_t* rows, const uint32_t* slots, size_t mask, size_t k, uint32_t* key_idx,
+                               uint32_t* misses, hipStream_t s) {
   if (misses) launch_store_word(misses, 0, s);
   if (n == 0) return hipSuccess;
   const unsigned g = grid_for(n, kLookupBlock);
   const dim3 grid(g < kMaxLookupGrid ? g : kMaxLookupGrid), block(kLookupBlock);
-  if (npoints == 1)
-    hipLaunchKernelGGL(k_key_lookup<1>, grid, block, 0, s, key_a, key_b, n, keys, slots, mask, k, key_idx,
+  with_key_form(form, npoints, [&](auto f) {
+    hipLaunchKernelGGL(k_index_lookup<decltype(f)>, grid, block, 0, s, key_a, key_b, n, rows, slots, mask, k, key_idx,
                        misses);
-  else
-    hipLaunchKernelGGL(k_key_lookup<2>, grid, block, 0, s, key_a, key_b, n, keys, slots, mask, k, key_idx,
-                       misses);
+  });
   return hipSuccess;
 }
 

@@ -1,18 +1,22 @@
-// keyed_lookup.h — the index of a registered key set over its own keys (dsv_keyset_lookup*,
-// dsv_verify_keyed_lookup*, include/dsv.h): what turns the key COLUMNS of a batch — the
-// canonical affine bytes callers hold — into the key_idx column every keyed entry point takes.
+// keyed_lookup.h — the indices of a registered key set over its own keys (dsv_keyset_lookup*,
+// dsv_verify_keyed_lookup*, dsv_verify_*_keyed_open*, include/dsv.h): what turns the keys
+// of a batch, given by VALUE, into the key_idx column every keyed entry point takes.  A set has one index per key
+// form (KeyForm): over the canonical affine bytes callers hold in columns, and over the compressed records
+// (`PublicKey*::to_bytes()`) of the same keys.  The record of a valid key is a pure function of its affine bytes
+// (v, with bit 255 set to the lowest bit of u), so both are filled from the affine points by byte operations.
 //
-// One device allocation per set, apart from the tables (keyed.h), made for the set's capacity (the plain
+// One device allocation per index, apart from the tables (keyed.h), made for the set's capacity (the plain
 // constructors: k) and never moved:
-//   keys   np * 64 B per key, key-major (PK | PK' for the double scheme, PK | Gen for the var-generator
-//          scheme), the bytes the set was built from; rounded up to 256 B
+//   rows   np * 64 B (affine) or np * 32 B (records) per key, key-major (PK | PK' for the double scheme, PK | Gen
+//          for the var-generator scheme); rounded up to 256 B
 //   slots  `cap` uint32, open addressing: a slot holds a key index or kSlotEmpty; cap = the smallest power
 //          of two >= max(64, 2 * capacity), so the table is at most half full; rounded up to 256 B
 // Only keys with key_ok == 1 are inserted (their bytes are canonical: every coordinate < q), equal keys share
 // one slot that holds the lowest of their indices.  Probing is linear from the key's home slot and wraps.
-// The hash picks the home slot only: a match is always a comparison of all np * 64 bytes.  It is not salted —
-// whoever registers the keys chooses the clusters — and no probe sequence is longer than the number of
-// distinct valid keys plus one (the table is never full, and a probe stops at the first empty slot).
+// The hash (KeyHash over the row's little-endian words) picks the home slot only: a match is always a comparison
+// of the whole row.  It is not salted — whoever registers the keys chooses the clusters — and no probe sequence is
+// longer than the number of distinct valid keys plus one (the table is never full, and a probe stops at the first
+// empty slot).
 #pragma once
 #include "keyed.h"
 
@@ -29,14 +33,18 @@ inline size_t keyset_index_cap(size_t k) {
   while (cap < 2 * k) cap <<= 1;
   return cap;
 }
-inline size_t keyset_index_keys_bytes(int scheme, size_t k) {
-  return lookup_round256((size_t)keyset_points(scheme) * 64 * k);
+// the forms a key takes in an index, and the bytes of one key point in each
+enum KeyForm { kKeyAffine = 0, kKeyRecord = 1 };
+constexpr int kKeyForms = 2;
+inline size_t key_point_bytes(KeyForm form) { return form == kKeyAffine ? 64 : 32; }
+inline size_t keyset_index_rows_bytes(KeyForm form, int scheme, size_t k) {
+  return lookup_round256((size_t)keyset_points(scheme) * key_point_bytes(form) * k);
 }
-inline size_t keyset_index_total_bytes(int scheme, size_t k) {
-  return k ? keyset_index_keys_bytes(scheme, k) + lookup_round256(4 * keyset_index_cap(k)) : 0;
+inline size_t keyset_index_total_bytes(KeyForm form, int scheme, size_t k) {
+  return k ? keyset_index_rows_bytes(form, scheme, k) + lookup_round256(4 * keyset_index_cap(k)) : 0;
 }
 
-// the hash of a key's 16 * np little-endian words; home slot = hash & (cap - 1)
+// the hash of a row's little-endian words (16 * np affine, 8 * np record); home slot = hash & (cap - 1)
 struct KeyHash {
   uint32_t h = 0;
   __host__ __device__ void word(uint32_t w) { h = (h ^ w) * 0x9E3779B1u; }
@@ -59,21 +67,22 @@ struct KeyHash {
 void launch_store_word(uint32_t* p, uint32_t v, hipStream_t s);
 // Every slot of an index to kSlotEmpty on `s` (mask + 1 slots, a power of two): once, when the set is created.
 hipError_t launch_clear_key_index(uint32_t* slots, size_t mask, hipStream_t s);
-// m further keys, indices first .. first + m - 1, into the index of a set that holds `first` keys already
+// m further keys, indices first .. first + m - 1, into the `form` index of a set that holds `first` keys already
 // (a fresh set: first = 0): from the affine points P0 / P1 (null for one-point keys) their tables were built from
-// and the table build's key_ok for them (earlier on `s`; both start at the first NEW key), copies the key bytes
-// into `keys` at row first + j and inserts the valid keys into `slots` (the whole index's, cleared when the set
-// was created).  One lane per new key.  Writes only key-byte rows >= first and slots that were empty or hold an
-// equal key; may run beside lookups enqueued with k <= first.  The launch's error surfaces through
-// hipGetLastError() like every launcher's.
-void launch_append_key_index(const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints, size_t first,
-                             size_t m, uint8_t* keys, uint32_t* slots, size_t mask, hipStream_t s);
-// key_idx[i] = the index in the slot of item i's key bytes (key_a[i] | key_b[i], 64 B each, 16-byte aligned;
-// key_b null for one-point keys), else kSlotEmpty; k: the set's key count as the call sees it — an occupant >= k
-// (appended since) is read as an empty slot; misses (may be null): zeroed on `s` (launch_store_word), then the
-// number of items that got kSlotEmpty.  One lane per item, grid-stride.
-hipError_t launch_key_lookup(const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
-                             const uint8_t* keys, const uint32_t* slots, size_t mask, size_t k, uint32_t* key_idx,
-                             uint32_t* misses, hipStream_t s);
+// and the table build's key_ok for them (earlier on `s`; both start at the first NEW key), writes the keys' rows
+// (the affine bytes, or the records formed from them) into `rows` at first + j and inserts the valid keys into
+// `slots` (the whole index's, cleared when the set was created).  One lane per new key.  Writes only rows >= first
+// and slots that were empty or hold an equal key; may run beside lookups enqueued with k <= first.  The launch's
+// error surfaces through hipGetLastError() like every launcher's.
+void launch_index_append(KeyForm form, const uint8_t* P0, const uint8_t* P1, const uint8_t* key_ok, int npoints,
+                         size_t first, size_t m, uint8_t* rows, uint32_t* slots, size_t mask, hipStream_t s);
+// key_idx[i] = the index in the slot of item i's key, else kSlotEmpty.  kKeyAffine: the key's bytes are
+// key_a[i] | key_b[i], 64 B each (key_b null for one-point keys); kKeyRecord: its record, 32 * npoints bytes at
+// key_a + i * 32 * npoints (key_b null); 16-byte aligned either way.  k: the set's key count as the call sees it —
+// an occupant >= k (appended since) is read as an empty slot; misses (may be null): zeroed on `s`
+// (launch_store_word), then the number of items that got kSlotEmpty.  One lane per item, grid-stride.
+hipError_t launch_index_lookup(KeyForm form, const uint8_t* key_a, const uint8_t* key_b, int npoints, size_t n,
+                               const uint8_t* rows, const uint32_t* slots, size_t mask, size_t k, uint32_t* key_idx,
+                               uint32_t* misses, hipStream_t s);
 
 }  // namespace dsv

@@ -22,15 +22,14 @@ struct dsv_keyset {
   size_t bytes = 0;     // of the table allocation: keyset_total_bytes(scheme, capacity)
   uint32_t* tables = nullptr;  // one allocation: the tables, then key_ok
   uint8_t* key_ok = nullptr;   // behind keyset_table_bytes(scheme, capacity)
-  // the index over the set's own keys (keyed_lookup.h), an allocation of its own: the keys' bytes for `capacity`
-  // keys, then the slots
-  uint8_t* index = nullptr;
-  uint32_t* slots = nullptr;
+  // the indices over the set's own keys (keyed_lookup.h), by KeyForm — affine bytes, compressed records — an
+  // allocation each: the rows for `capacity` keys, then the slots; both have keyset_index_cap(capacity) slots
+  struct KeyIndex {
+    uint8_t* rows = nullptr;
+    uint32_t* slots = nullptr;
+  };
+  KeyIndex index[dsv::kKeyForms];
   size_t slot_mask = 0;  // keyset_index_cap(capacity) - 1
-  // the index over the compressed records of the set's own keys (keyed_open_wire.h), a third allocation: the
-  // records for `capacity` keys, then as many slots as the affine index has (slot_mask)
-  uint8_t* wire_index = nullptr;
-  uint32_t* wire_slots = nullptr;
   bool alive = false;
   // one appender at a time per set (shared with the appender: it outlives a handle destroyed under a waiting one)
   std::shared_ptr<std::mutex> append_mu = std::make_shared<std::mutex>();
@@ -156,18 +155,108 @@ constexpr size_t kLookupHostChunk = (size_t)1 << 18;  // items per chunk of the 
 // a call without a handle before dsv_init is told that nothing is up (a handle, live or dead, goes through
 // check_set like every keyed call)
 int library_up(const dsv_keyset* ks);
-bool keys_null(int scheme, const void* key_a, const void* key_b);
+// the keys of a batch in `form`: kKeyAffine — columns key_a [, key_b], 64 B per item each; kKeyRecord — records at
+// key_a, 32 B per key point, key_b unused
+bool keys_null(KeyForm form, int scheme, const void* key_a, const void* key_b);
 // the lookup kernel reads a key in 16-byte loads
-int check_key_alignment(int scheme, const void* key_a, const void* key_b);
+int check_key_alignment(KeyForm form, int scheme, const void* key_a, const void* key_b);
 // misses (may be null): a 4-byte-aligned word on the set's device (ctx: the set's context)
 int check_misses(const dsv_keyset* ks, const Context* ctx, const void* misses);
-// the lookup of n items on s; every pointer device memory of the set's device.  An empty set: everything misses.
-int enqueue_lookup(const dsv_keyset* ks, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
+// the lookup of n items on s through the set's `form` index; every pointer device memory of the set's device.  An
+// empty set has no index: everything misses.
+int enqueue_lookup(const dsv_keyset* ks, KeyForm form, const void* key_a, const void* key_b, size_t n, uint32_t* idx,
                    uint32_t* misses, hipStream_t s);
 
-// ---- the key cache for serialized records (dsv_keyed_open_wire.hip, keyed_open_wire.h) ---------------------
-// enqueue_lookup for key records (32 B per key point, 16-byte aligned) through the set's wire index
-int enqueue_lookup_wire(const dsv_keyset* ks, const void* pk, size_t n, uint32_t* idx, uint32_t* misses,
-                        hipStream_t s);
+// a batch's key bytes per item in `form`
+inline size_t keys_item_bytes(KeyForm form, int scheme) {
+  return (size_t)keyset_points(scheme) * key_point_bytes(form);
+}
+// host forms: the keys of items off .. off + cnt - 1 carved from st and copied up on the null stream (db null:
+// one column)
+int stage_keys(KeyForm form, int scheme, Stager& st, const uint8_t* key_a, const uint8_t* key_b, size_t off,
+               size_t cnt, uint8_t*& da, uint8_t*& db);
+// host forms of verify by affine key value: a chunk's columns carved from st and copied up — u, m, the nonce
+// points, the key columns — with room for the index and verdict columns; nonce-point and key columns: 1 + 1,
+// 2 + 2, and 1 + 2 for the var-generator scheme
+struct AffineChunk {
+  Items in;
+  uint8_t *key_a, *key_b, *ok;
+  uint32_t* idx;
+};
+int stage_affine_chunk(int scheme, Stager& st, const uint8_t* u, const uint8_t* R_uv, const uint8_t* Rp_uv,
+                       const uint8_t* m, const uint8_t* key_a, const uint8_t* key_b, size_t off, size_t cnt,
+                       AffineChunk& c);
+inline size_t affine_chunk_bytes(int scheme, size_t cnt) {
+  return cnt * (32 + 32 + 4 + 1 + 64 * (size_t)(keyed_sig_points(scheme) + keyset_points(scheme))) + 12 * 256;
+}
+inline bool affine_inputs_null(int scheme, const void* u, const void* R_uv, const void* Rp_uv, const void* m,
+                               const void* key_a, const void* key_b) {
+  return !u || !R_uv || (keyed_sig_points(scheme) == 2 && !Rp_uv) || !m || keys_null(kKeyAffine, scheme, key_a, key_b);
+}
+
+// The body of the by-value host forms (lookup and verify, closed and open set, affine keys and records), under the
+// registry's shared lock: library_up, check_set (scheme: the entry point's, or negative for the set's own), the
+// form's scheme check, n == 0 (*misses = 0), null pointers, the context's lock and staging, then chunks of
+// kLookupHostChunk items on the null stream, each synchronised once after its output column and its miss word
+// were copied back; *misses (may be null) = the sum over the chunks.  A form supplies
+//   scheme_check(scheme)       its own check of the set's scheme (DSV_OK: none),
+//   inputs_null(scheme)        one of its input pointers is null,
+//   stage_bytes(scheme, cnt)   the staging a chunk of cnt items needs, the miss word included,
+//   chunk(ctx, scheme, st, off, cnt, dmiss, dout)   carves from st, copies items off .. off + cnt - 1 up, enqueues
+//                              with dmiss as the lookup's miss word, and names the output column's device copy.
+// out: the caller's output column, out_item bytes per item.
+template <class Check, class Null, class Bytes, class Chunk>
+int run_by_value_host(const dsv_keyset* ks, int scheme, Check scheme_check, Null inputs_null, Bytes stage_bytes,
+                      size_t n, void* out, size_t out_item, size_t* misses, Chunk chunk) {
+  if (int r = library_up(ks)) return r;
+  std::shared_lock<std::shared_mutex> rl(keyset_mutex());
+  Context* cp = nullptr;
+  if (int r = check_set(ks, scheme, n, cp)) return r;
+  scheme = ks->scheme;
+  if (int r = scheme_check(scheme)) return r;
+  if (n == 0) {
+    if (misses) *misses = 0;
+    return DSV_OK;
+  }
+  if (inputs_null(scheme) || !out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  Context& ctx = *cp;
+  DSV_HOST_LOCK();
+  const size_t per = n < kLookupHostChunk ? n : kLookupHostChunk;
+  if (int r = ensure_stage(ctx, stage_bytes(scheme, per))) return r;
+  size_t total = 0;
+  for (size_t off = 0; off < n; off += per) {
+    const size_t cnt = n - off < per ? n - off : per;
+    Stager st(ctx.stage);
+    uint32_t* dmiss = reinterpret_cast<uint32_t*>(st.take(4));
+    const void* dout = nullptr;
+    if (int r = chunk(ctx, scheme, st, off, cnt, dmiss, dout)) return r;
+    uint32_t missed = 0;
+    D2H(static_cast<uint8_t*>(out) + off * out_item, dout, cnt * out_item);
+    D2H(&missed, dmiss, 4);
+    HIP_TRY(hipStreamSynchronize(0));
+    total += missed;
+  }
+  if (misses) *misses = total;
+  return DSV_OK;
+}
+inline int any_scheme(int) { return DSV_OK; }
+
+// ---- the open-set forms' miss branch (dsv_keyed_open.hip) ---------------------------------------------------
+// its part of a workspace: list | count | per-lane window tables, and for kKeyRecord behind them the key columns
+// P0 [| P1] it decompresses into, of which only the listed rows are ever written
+size_t open_miss_bytes(KeyForm form, int scheme, size_t n);
+struct MissBranch {
+  uint32_t *list, *count, *tables;
+  const uint8_t *key_a, *key_b;  // the items' affine key columns: the caller's, or own_a / own_b
+  const uint8_t* records;        // not null: the items' key records, decompressed for the listed items into
+  uint8_t *own_a, *own_b;        //   columns of the branch's own
+};
+// kKeyAffine: key_a / key_b are the caller's columns; kKeyRecord: key_a the records, key_b unused
+MissBranch carve_miss_branch(Stager& x, KeyForm form, int scheme, size_t n, const void* key_a, const void* key_b);
+// behind the keyed kernel on s: the misses of idx are listed, their keys decompressed if the branch holds records
+// (the decode flags AND-ed into w.valid), and decided by the unkeyed equation from the c / valid the challenge hash
+// left in w; in: the keyed call's items (the var-generator scheme: key_a / key_b = PK / Gen, one three-base chain)
+int enqueue_miss_branch(const Context& ctx, const Items& in, const uint32_t* idx, size_t n, uint8_t* ok,
+                        const MissBranch& b, const Workspace& w, hipStream_t s);
 
 }  // namespace dsvh

@@ -327,6 +327,69 @@ def test_verify_by_value_rejects_a_valid_signature_under_an_unregistered_key(eng
     assert (ok == (idx < 4)).all() and misses == int((idx == 4).sum()) > 0
 
 
+# ---- 5b. the host forms across a chunk boundary ------------------------------------------------------------
+HOST_CHUNK = 1 << 18  # items per chunk of the by-value host forms
+
+
+def _tiled(a, n):
+    return np.ascontiguousarray(np.concatenate([a] * -(-n // len(a)))[:n])
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_host_lookups_across_a_chunk_boundary(engine, scheme):
+    """dsv_keyset_lookup and dsv_keyset_lookup_wire on 2^18 + 5 host items tiled from 4099: the second chunk
+    holds five items; the indices are the dict model's and `misses` is the sum over both chunks"""
+    from test_gpu_keyset_open_wire import _expect_rec, _key_records, _where_rec
+
+    k, extra, base, n = 33, 8, 4099, HOST_CHUNK + 5
+    _, _, K0, K1 = _keys(engine, scheme, k + extra, 4711)
+    P0, X0 = np.ascontiguousarray(K0[:k]), K0[k:]
+    P1, X1 = (np.ascontiguousarray(K1[:k]), K1[k:]) if K1 is not None else (None, None)
+    rng = np.random.default_rng(len(scheme))
+    A, B = _lookup_items(rng, P0, P1, X0, X1, base)
+    # records: registered and unregistered keys at random, every 16th with a flipped byte
+    pk = _key_records(K0, K1)[rng.integers(0, k + extra, size=base)].copy()
+    pk[::16, 5] ^= 1
+    kok = np.ones(k, np.uint8)
+    cases = (("affine", _expect(_where(P0, P1, kok), A, B),
+              lambda ks: ks.lookup(*[_tiled(c, n) for c in ([A] + ([B] if B is not None else []))])),
+             ("wire", _expect_rec(_where_rec(P0, P1, kok), pk), lambda ks: ks.lookup_wire(_tiled(pk, n))))
+    with engine.KeySet(scheme, P0, P1) as ks:
+        assert (ks.key_ok() == 1).all()
+        for form, want, call in cases:
+            want = _tiled(want, n)
+            nmiss = int((want == NONE).sum())
+            assert 0 < nmiss < n, (form, nmiss)
+            got, misses = call(ks)
+            assert got.shape == (n,) and (got == want).all(), (scheme, form, _diff(got, want))
+            assert misses == nmiss, (scheme, form, misses, nmiss)
+
+
+@pytest.mark.parametrize("scheme", ("single", "double"))
+def test_verify_by_value_host_across_a_chunk_boundary(engine, scheme):
+    """dsv_verify_keyed_lookup on 2^18 + 5 host items tiled from the parity batch: the second chunk holds five
+    items; verdicts and `misses` equal the _dev form's and the tiled expectation"""
+    b = _value_batch(engine, scheme)
+    base, n = len(b["m"]), HOST_CHUNK + 5
+    with engine.KeySet(scheme, b["P0"], b["P1"]) as ks:
+        found = _expect(_where(b["P0"], b["P1"], ks.key_ok()), b["A"], b["B"]) != NONE
+        want = _tiled(b["oracle"].astype(np.uint8) & found.astype(np.uint8), n)
+        nmiss = int((~_tiled(found, n)).sum())
+        assert 0 < nmiss < n and 0 < want.sum() < n
+        args = [_tiled(c, n) for c in _value_args(b, base)]
+        ok = _poison(n)
+        ws = torch.empty(engine.keyed_lookup_workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        misses = torch.full((1,), 999, dtype=torch.int32, device=DEV)
+        ks.verify_lookup_dev(*_dev(args), ok, ws, misses=misses)
+        torch.cuda.synchronize()
+        dev = ok.cpu().numpy()
+        assert (dev == want).all(), (scheme, "dev", _diff(dev, want))
+        assert int(misses.item()) == nmiss
+        got, hm = ks.verify_lookup(*args)
+        assert (got == dev).all(), (scheme, "host", _diff(got, dev))
+        assert hm == nmiss
+
+
 # ---- 6. the _dev contract ----------------------------------------------------------------------------------
 def test_dev_contract(engine):
     from schnorr_amd import _lib

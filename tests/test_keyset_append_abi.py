@@ -1,6 +1,6 @@
 """Key sets that grow, CPU side (no GPU): the new exports and their signatures in include/dsv.h, the size formulas
 a reserved set is allocated by, the argument checks of dsv_keyset_create_reserved / dsv_keyset_append* that need no
-device, the calls before dsv_init, and the register budget of k_append_key_index and the guarded k_key_lookup."""
+device, the calls before dsv_init, and the register budget of the affine k_index_append and the guarded k_index_lookup."""
 import ctypes
 import os
 import re
@@ -110,25 +110,23 @@ print("ok")
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_append_and_lookup_kernels_stay_in_registers():
-    """k_append_key_index<NP>: no scratch, no spilled VGPRs, no AGPRs, and no more VGPRs than k_build_key_index<NP>
-    of the same unit — an append lane holds what a build lane holds (its own key's words and an occupant's) and
-    two more scalars — nor more than 44 (NP = 1) / 70 (NP = 2), what k_build_key_index<NP> took at the commit
-    before the append kernel existed: a fixed ceiling, so that both kernels growing together
-    does not pass.  k_key_lookup<NP> with the k guard: within the 42 - 68 VGPRs DESIGN.md §10.4 records for
+    """k_index_append<AffineKey<NP>>: no scratch, no spilled VGPRs, no AGPRs, and no more than 44 (NP = 1) / 70
+    (NP = 2) VGPRs, what the build kernel of a fresh set took at the commit before the append kernel existed
+     and the append kernel, which now serves fresh sets too (first = 0), has kept to since: a fixed
+    ceiling.  k_index_lookup<AffineKey<NP>> with the k guard: within the 42 - 68 VGPRs DESIGN.md §10.4 records for
     the kernel without it (one more scalar argument, one compare per slot)."""
     from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_lookup.hip"), _stamp()))
 
-    def one(needle):
-        hits = [k for k in info if needle in k]
-        assert len(hits) == 1, (needle, sorted(info))
+    def one(kernel, needle):
+        hits = [k for k in info if kernel in k and needle in k]
+        assert len(hits) == 1, (kernel, needle, sorted(info))
         return info[hits[0]]
 
     for np_ in (1, 2):
-        build, append, lookup = (one("%sILi%dE" % (name, np_))
-                                 for name in ("k_build_key_index", "k_append_key_index", "k_key_lookup"))
+        append, lookup = (one(name, "AffineKeyILi%dE" % np_) for name in ("k_index_append", "k_index_lookup"))
         for k in (append, lookup):
             assert k["scratch"] == 0 and k["vgpr_spill_count"] == 0 and k["agprs"] == 0, (np_, k)
-        assert 42 <= append["vgprs"] <= min(build["vgprs"], {1: 44, 2: 70}[np_]), (np_, append, build)
+        assert 42 <= append["vgprs"] <= {1: 44, 2: 70}[np_], (np_, append)
         assert 42 <= lookup["vgprs"] <= 68, (np_, lookup)

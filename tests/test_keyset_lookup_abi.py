@@ -152,8 +152,11 @@ def test_lookup_kernels_stay_in_registers():
     from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_lookup.hip"), _stamp()))
-    for needle in ("k_build_key_indexILi1E", "k_build_key_indexILi2E", "k_key_lookupILi1E", "k_key_lookupILi2E"):
-        hits = [k for k in info if needle in k]
-        assert len(hits) == 1, (needle, sorted(info))
-        k = info[hits[0]]
-        assert k["scratch"] == 0 and k["vgpr_spill_count"] == 0, (needle, k)
+    # the affine instantiations of the two index kernels (the fresh set's build is the append kernel at first = 0)
+    for kernel in ("k_index_append", "k_index_lookup"):
+        for np_ in (1, 2):
+            needle = "AffineKeyILi%dE" % np_
+            hits = [k for k in info if kernel in k and needle in k]
+            assert len(hits) == 1, (kernel, needle, sorted(info))
+            k = info[hits[0]]
+            assert k["scratch"] == 0 and k["vgpr_spill_count"] == 0, (kernel, needle, k)

@@ -1,7 +1,7 @@
 """The key cache for serialized records, CPU side (no GPU): the exports of the wire index and of the open-set verify
 by compressed key (dsv_keyset_lookup_wire*, dsv_verify_*_keyed_open_wire*, include/dsv.h), the size formulas, the
 calls before dsv_init, the home slot of a record against a Python KeyHash, and the register budget of
-k_keyed_open_wire.hip's kernels against the kernels they mirror."""
+the record kernels against the kernels they mirror."""
 import ctypes
 import os
 import re
@@ -168,10 +168,11 @@ def test_wire_home_slot_is_keyhash_of_the_record_words():
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_wire_kernels_register_budget():
-    """VGPRs, scratch and occupancy only.  The wire index kernel and the wire lookup move half the bytes of the
-    kernels they mirror: no scratch, no AGPRs, and no more VGPRs than k_append_key_index / k_key_lookup of the same
-    key-point count, compiled by this run.  k_decompress_listed is k_keyed_wire_decode's arithmetic behind one
-    more indirection: no more VGPRs and no more scratch than the decode kernel with as many points per item."""
+    """VGPRs, scratch and occupancy only.  The record instantiations of the index kernels move half the bytes of
+    the affine ones: no scratch, no AGPRs, no more VGPRs and no less occupancy than the affine instantiation of the
+    same key-point count, compiled by this run from the same unit.  k_decompress_listed is k_keyed_wire_decode's
+    arithmetic behind one more indirection: no more VGPRs and no more scratch than the decode kernel with as many
+    points per item."""
     from concurrent.futures import ThreadPoolExecutor
 
     from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
@@ -181,19 +182,18 @@ def test_wire_kernels_register_budget():
     with ThreadPoolExecutor(3) as ex:
         wire, lookup, decode = [_kernel_info(s) for s in ex.map(lambda u: _asm(os.path.join(CSRC, u), stamp), units)]
 
-    def one(info, needle):
-        hits = [k for k in info if needle in k]
-        assert len(hits) == 1, (needle, sorted(info))
+    def one(info, *needles):
+        hits = [k for k in info if all(n in k for n in needles)]
+        assert len(hits) == 1, (needles, sorted(info))
         return info[hits[0]]
 
     for np_ in (1, 2):
-        for mine, ref in (("k_append_wire_indexILi%dE", "k_append_key_indexILi%dE"),
-                          ("k_key_lookup_wireILi%dE", "k_key_lookupILi%dE")):
-            k, r = one(wire, mine % np_), one(lookup, ref % np_)
-            print(mine % np_, k, "against", ref % np_, r)
-            assert k["scratch"] == 0 and k["agprs"] == 0, (mine, np_, k)
-            assert k["vgprs"] <= r["vgprs"], (mine, np_, k, r)
-            assert k["occupancy"] >= r["occupancy"], (mine, np_, k, r)
+        for kernel in ("k_index_append", "k_index_lookup"):
+            k, r = one(lookup, kernel, "RecordKeyILi%dE" % np_), one(lookup, kernel, "AffineKeyILi%dE" % np_)
+            print(kernel, "records", np_, k, "against affine", r)
+            assert k["scratch"] == 0 and k["agprs"] == 0, (kernel, np_, k)
+            assert k["vgprs"] <= r["vgprs"], (kernel, np_, k, r)
+            assert k["occupancy"] >= r["occupancy"], (kernel, np_, k, r)
         # points per item: k_keyed_wire_decode<0> (single) decodes one, <1> (double) two in adjacent lanes
         k, r = one(wire, "k_decompress_listedILi%dE" % np_), one(decode, "k_keyed_wire_decodeILi%dE" % (np_ - 1))
         print("k_decompress_listed<%d>" % np_, k, "against k_keyed_wire_decode<%d>" % (np_ - 1), r)
