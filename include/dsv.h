@@ -530,9 +530,10 @@ int dsv_stdrng_vargen_inputs_dev(uint64_t seed, size_t first_item, size_t n, voi
  * Contract:
  *   Ownership   a key set belongs to the device that was current when it was created (it must be
  *               initialised).  Its device memory is allocated once and never moves; any number of concurrent
- *               calls may read it.  It changes in one way only: dsv_keyset_append registers further keys behind
- *               the ones it holds ("key sets that grow", below).  A call sees the set as it was when the call was
- *               enqueued (or captured).
+ *               calls may read it.  It changes in two ways only: dsv_keyset_append registers further keys behind
+ *               the ones it holds ("key sets that grow", below), and dsv_keyset_replace puts new keys in the places
+ *               of registered ones while nothing reads the set ("keys replaced in place", below).  A call sees the
+ *               set as it was when the call was enqueued; a captured graph keeps the k of its capture.
  *   Verdicts    ok[i] equals the unkeyed entry point's verdict on (u, R, PK[key_idx[i]], m) for every input
  *               the reference's types can hold.
  *   Key indices key_idx is uint32 per item; an index >= k gives ok = 0 and never a fault.
@@ -594,12 +595,52 @@ int dsv_keyset_key_ok_n(const dsv_keyset *ks, uint8_t *out /* room bytes */, siz
  *               same verdict.  To use the new keys from a graph, capture it again.
  *   Sizes       workspaces that depend on k (dsv_keyed_rlc_workspace_bytes) are checked against the k the call
  *               sees: size them for `capacity`.
- * Not here: eviction and replacement of keys. */
+ * Eviction is replacement: "keys replaced in place", next.  Not here: retiring a key without a successor, growing
+ * past the capacity. */
 int dsv_keyset_create_reserved(int scheme, const uint8_t *pk_uv, const uint8_t *pk2_uv, size_t k, size_t capacity,
                                dsv_keyset **out);
 int dsv_keyset_append(dsv_keyset *ks, const uint8_t *pk_uv, const uint8_t *pk2_uv, size_t m, uint32_t *first_index);
 int dsv_keyset_append_wire(dsv_keyset *ks, const uint8_t *pk_bytes, size_t m, uint32_t *first_index);
 int dsv_keyset_capacity(const dsv_keyset *ks, size_t *capacity);
+/* ---- keys replaced in place: the key cache's eviction ----------------------------------
+ * A full set (k == capacity) takes a new busy key in the place of an idle one, at the cost of the new key's own
+ * table, instead of a second set over all keys: no allocation moves; k, the capacity and every other key's index,
+ * table and verdict stay as they are; captured graphs stay valid.
+ *   replace     `indices`: a host array of m pairwise distinct indices, each < k; key j of the call takes the place
+ *               of key indices[j].  The keys come in the constructor's form (replace: affine host bytes;
+ *               replace_wire: key records, decoded by the device decoder exactly as dsv_keyset_append_wire does)
+ *               and are validated and recorded as at creation: an invalid or undecodable key gets key_ok = 0, keeps
+ *               the index and is in neither index over the keys' values.
+ *   Checks      in this order, all before anything is launched or written: NULL handle, a handle that is not
+ *               live (DSV_ERR_INVALID_ARGUMENT; the former also before dsv_init), a dead set
+ *               (DSV_ERR_NOT_INITIALIZED), m == 0 (DSV_OK), NULL `indices` or keys, an index >= k or an index
+ *               given twice (DSV_ERR_INVALID_ARGUMENT).  On each of them the set is unchanged.
+ *   Contract    The call blocks.  When it has returned, every keyed call enqueued afterwards, on any stream of the
+ *               set's device, sees the new keys at those indices: by index, ok[i] is the unkeyed verdict under the
+ *               new key; by value, the old key is a miss unless an equal key is registered at another index, and the
+ *               new key looks up to the lowest index of an equal valid key.  The open-set forms keep returning the
+ *               unkeyed call's verdict for every input, before and after.  Replaces and appends to one set are
+ *               serialised.
+ *   Calls in flight   The call quiesces.  It first builds the new keys' tables in a scratch of its own, on a stream
+ *               of its own, while verify calls go on.  Then it takes the library's key-set lock exclusively, so no
+ *               library call is enqueueing on any key set, and waits for the set's device (hipDeviceSynchronize)
+ *               before the first byte of the set changes; the lock is released when the set is complete again.  A
+ *               call enqueued before the replace decides on the old set and a call enqueued after it on the new; no
+ *               call sees a mixture.  Two duties are the caller's: no graph that holds the set may be replayed
+ *               while the replace runs (graph launches do not pass through the library's lock), and no stream of
+ *               the device may be capturing then (a device-wide wait is illegal during a capture).
+ *   Captured graphs   A graph captured earlier stays valid afterwards.  It keeps its k: at a replaced index below
+ *               that k it sees the new key, by index and by value; keys at indices >= its k stay misses.  Both
+ *               indices over the keys' values are rebuilt in the layout that inserting key 0, then 1, and so on
+ *               gives, so the stale-k rule above holds for every k, not only for the k of an append.
+ *   Failures    A HIP failure before the set is written leaves it unchanged.  A HIP failure while it is written
+ *               leaves the set dead — its device memory freed, every later call on it DSV_ERR_NOT_INITIALIZED,
+ *               dsv_keyset_destroy releases the handle — and returns the error.
+ *   Sizes       no device allocation changes: dsv_keyset_bytes, dsv_keyset_index_bytes and
+ *               dsv_keyset_wire_index_bytes are what they were. */
+int dsv_keyset_replace(dsv_keyset *ks, const uint32_t *indices, const uint8_t *pk_uv,
+                       const uint8_t *pk2_uv, size_t m);
+int dsv_keyset_replace_wire(dsv_keyset *ks, const uint32_t *indices, const uint8_t *pk_bytes, size_t m);
 size_t dsv_keyed_workspace_bytes(size_t n);
 int dsv_verify_single_keyed_dev(const dsv_keyset *ks, const void *u, const void *R_uv, const void *key_idx,
                                 const void *m, size_t n, void *ok, void *workspace, size_t workspace_bytes,
@@ -761,6 +802,14 @@ uint64_t dsv_debug_keyset_home_slot(int scheme, size_t k, const uint8_t *key_a, 
  * is not in its home slot, [3] = the longest probe of a registered key (slots read to find it; 1 = at home);
  * all 0 for an empty set */
 int dsv_debug_keyset_index_stats(const dsv_keyset *ks, uint64_t out[4]);
+/* introspection: copies the slot array of one index (form 0 = affine, 1 = record) to the host:
+ * writes min(slots, room) uint32 and reports the slot count in *slots_out (may be NULL); a slot holds a key index
+ * or DSV_KEY_NONE.  Blocks; a NULL handle is DSV_ERR_NOT_INITIALIZED before dsv_init and
+ * DSV_ERR_INVALID_ARGUMENT after it, as is an unknown form. */
+int dsv_debug_keyset_slots(const dsv_keyset *ks, int form, uint32_t *out, size_t room, size_t *slots_out);
+/* introspection: host nanoseconds the latest dsv_keyset_replace* of this process held the key-set lock exclusively
+ * (the device-wide wait, the commit, the index rebuild); 0 before the first */
+uint64_t dsv_debug_keyset_replace_exclusive_ns(void);
 /* ---- key sets as a key cache: open-set verify by key value -----------------------------
  * The caller that verifies (signature, public key, message) triples as they arrive, most under a few busy keys
  * and some under keys it has never seen.  Same arguments as dsv_verify_keyed_lookup[_dev]; what differs is what a

@@ -143,6 +143,16 @@ extern "C" {
                                              n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
     pub fn dsv_verify_vargen_keyed_open_wire(ks: *const c_void, sig64: *const u8, pk64: *const u8, m: *const u8,
                                              n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    // keys replaced in place (include/dsv.h, "keys replaced in place"): key j of the call takes the place of key
+    // indices[j] (m pairwise distinct indices below k) of a live set; blocks, quiesces the set's device.  No graph
+    // that holds the set may be replayed, and no stream of the device may be capturing, meanwhile.  Raw exports.
+    pub fn dsv_keyset_replace(ks: *mut c_void, indices: *const u32, pk_uv: *const u8, pk2_uv: *const u8,
+                              m: usize) -> c_int;
+    pub fn dsv_keyset_replace_wire(ks: *mut c_void, indices: *const u32, pk_bytes: *const u8, m: usize) -> c_int;
+    // the slot array of one index (form 0 = affine, 1 = record): at most `room` words, *slots_out = the slot count
+    pub fn dsv_debug_keyset_slots(ks: *const c_void, form: c_int, out: *mut u32, room: usize,
+                                  slots_out: *mut usize) -> c_int;
+    pub fn dsv_debug_keyset_replace_exclusive_ns() -> u64;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.

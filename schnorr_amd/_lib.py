@@ -84,6 +84,8 @@ SYMBOLS = [
     "dsv_verify_single_keyed_open_wire_dev", "dsv_verify_double_keyed_open_wire_dev",
     "dsv_verify_vargen_keyed_open_wire_dev", "dsv_verify_single_keyed_open_wire",
     "dsv_verify_double_keyed_open_wire", "dsv_verify_vargen_keyed_open_wire",
+    # keys replaced in place: the key cache's eviction
+    "dsv_keyset_replace", "dsv_keyset_replace_wire", "dsv_debug_keyset_slots", "dsv_debug_keyset_replace_exclusive_ns",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
@@ -145,6 +147,10 @@ def load():
     L.dsv_debug_keyset_home_slot.restype = ctypes.c_uint64
     L.dsv_debug_keyset_home_slot.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    L.dsv_keyset_replace.argtypes = [vp, vp, vp, vp, sz]
+    L.dsv_keyset_replace_wire.argtypes = [vp, vp, vp, sz]
+    L.dsv_debug_keyset_slots.argtypes = [vp, ctypes.c_int, vp, sz, vp]
+    L.dsv_debug_keyset_replace_exclusive_ns.restype = ctypes.c_uint64
     # (ks, u, R, PK, Gen, m, n, ok, workspace, workspace_bytes, stream, misses) / (ks, u, R, PK, Gen, m, n, ok, misses)
     L.dsv_verify_vargen_keyed_open_dev.argtypes = [vp] * 6 + [sz, vp, vp, sz, vp, vp]
     L.dsv_verify_vargen_keyed_open.argtypes = [vp] * 6 + [sz, vp, vp]
@@ -156,7 +162,8 @@ def load():
     L.dsv_keyset_lookup_wire.argtypes = [vp, vp, sz, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
-        if name not in ("dsv_version", "dsv_last_error", "dsv_debug_keyset_home_slot") + _SIZE_T_FUNCS:
+        if name not in ("dsv_version", "dsv_last_error", "dsv_debug_keyset_home_slot",
+                        "dsv_debug_keyset_replace_exclusive_ns") + _SIZE_T_FUNCS:
             fn.restype = ctypes.c_int
     _lib = L
     return L

@@ -1,7 +1,8 @@
 // dsv_keyset.hip — registered key sets (include/dsv.h: dsv_keyset_*, dsv_verify_*_keyed*): creation from
-// affine points or wire records, with or without reserved capacity, appending keys to a live set, the registry
-// that dsv_shutdown_device empties, and the keyed verify entry points (k_challenge unchanged, then
-// k_verify_keyed; keyed.h).
+// affine points or wire records, with or without reserved capacity, appending keys to a live set, replacing keys of
+// a live set in place (the quiesce, the commit and the index rebuild of k_keyed_replace.hip), the registry that
+// dsv_shutdown_device empties, and the keyed verify entry points (k_challenge unchanged, then k_verify_keyed;
+// keyed.h).
 #include <algorithm>
 #include <shared_mutex>
 
@@ -10,7 +11,8 @@
 namespace dsvh {
 namespace {
 // live key sets; verify calls read under the shared lock, create / destroy / shutdown write under the
-// exclusive one; an append builds its rows under the shared lock and raises k under the exclusive one
+// exclusive one; an append builds its rows under the shared lock and raises k under the exclusive one; a replace
+// builds its tables under the shared lock and writes the set under the exclusive one, on a device that has run dry
 std::shared_mutex g_ks_mu;
 std::vector<dsv_keyset*> g_keysets;
 
@@ -207,6 +209,120 @@ int append_keyset(dsv_keyset* ks, size_t m, uint32_t* first_index,
   return DSV_OK;
 }
 
+// the rebuild of both indices from the set's own rows, on s: the affine rows of the k keys as
+// planar columns, one entry per distinct valid key at its lowest index by the append kernel at first = 0 into a
+// scratch index (ws: k * np * 64 B of columns, as many of rows, the slots; carved as rebuild_bytes counts them),
+// then both live slot arrays cleared and those representatives inserted in order
+static size_t rebuild_bytes(const dsv_keyset* ks) {
+  const size_t cols = align_up(ks->k * (size_t)keyset_points(ks->scheme) * 64, 256);
+  return 2 * cols + align_up(4 * (ks->slot_mask + 1), 256);
+}
+static int rebuild_indices(dsv_keyset* ks, uint8_t* ws, hipStream_t s) {
+  const int np = keyset_points(ks->scheme);
+  const size_t k = ks->k;
+  Stager x(ws);
+  uint8_t* P0 = x.take(k * (size_t)np * 64);
+  uint8_t* P1 = np == 2 ? P0 + k * 64 : nullptr;
+  uint8_t* rows = x.take(k * (size_t)np * 64);
+  uint32_t* reps = reinterpret_cast<uint32_t*>(x.take(4 * (ks->slot_mask + 1)));
+  const uint8_t* own = ks->index[kKeyAffine].rows;
+  launch_rows_to_planar(np, own, k, P0, P1, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_clear_key_index(reps, ks->slot_mask, s));
+  launch_index_append(kKeyAffine, P0, P1, ks->key_ok, np, 0, k, rows, reps, ks->slot_mask, s);
+  HIP_TRY(hipGetLastError());
+  for (KeyForm f : {kKeyAffine, kKeyRecord}) {
+    HIP_TRY(launch_clear_key_index(ks->index[f].slots, ks->slot_mask, s));
+    launch_index_reinsert(f, np, own, reps, ks->index[f].slots, ks->slot_mask, s);
+    HIP_TRY(hipGetLastError());
+  }
+  return DSV_OK;
+}
+
+// host nanoseconds the latest replace held the registry's exclusive lock (dsv_debug_keyset_replace_exclusive_ns)
+static std::atomic<uint64_t> g_replace_exclusive_ns{0};
+
+int replace_keyset(dsv_keyset* ks, const uint32_t* indices, size_t m,
+                   const std::function<KeysetForm(int scheme)>& form_of) {
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  std::shared_ptr<std::mutex> mu;
+  {
+    std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+    if (!registered(ks)) return fail(DSV_ERR_INVALID_ARGUMENT, "not a live key set handle");  // (before ks is read)
+    mu = ks->append_mu;
+  }
+  std::lock_guard<std::mutex> one_writer(*mu);  // replaces and appends to one set take turns
+  // the call's scratch, alive through both phases: the staged points and the form's own bytes, the m keys' tables
+  // and key_ok, their indices, and what the rebuild works in
+  Scratch x;
+  uint8_t *P0 = nullptr, *P1 = nullptr, *new_ok = nullptr, *rebuild = nullptr;
+  uint32_t *new_tables = nullptr, *dev_indices = nullptr;
+  int np = 0;
+  {
+    // phase 1, shared: the new keys' tables are built beside the verify calls, as an append builds its own
+    std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+    if (!registered(ks)) return fail(DSV_ERR_INVALID_ARGUMENT, "not a live key set handle");
+    Context* cp = nullptr;
+    if (int r = keyset_context(ks, cp)) return r;
+    if (m == 0) return DSV_OK;
+    const KeysetForm form = form_of(ks->scheme);
+    if (!indices) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int r = form.check_pointers()) return r;
+    const size_t k = ks->k;  // (only an appender raises it, and append_mu is held)
+    if (m > k) return fail(DSV_ERR_INVALID_ARGUMENT, "%zu distinct indices cannot all lie below k = %zu", m, k);
+    std::vector<uint32_t> sorted(indices, indices + m);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.back() >= k) return fail(DSV_ERR_INVALID_ARGUMENT, "index %u of %zu keys", sorted.back(), k);
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      return fail(DSV_ERR_INVALID_ARGUMENT, "an index is given twice");
+    np = keyset_points(ks->scheme);
+    DSV_ON_DEVICE(*cp);
+    HIP_TRY(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
+    const size_t own_bytes = align_up((size_t)np * m * 64, 256) + align_up(form.own_bytes, 256) +
+                             align_up(m * (size_t)np * kKeyPointBytes, 256) + align_up(m, 256) + align_up(4 * m, 256);
+    HIP_TRY(hipMalloc(&x.dev, own_bytes + rebuild_bytes(ks)));
+    Stager st(x.dev);
+    P0 = st.take((size_t)np * m * 64);
+    P1 = np == 2 ? P0 + m * 64 : nullptr;
+    uint8_t* own = st.take(form.own_bytes);
+    new_tables = reinterpret_cast<uint32_t*>(st.take(m * (size_t)np * kKeyPointBytes));
+    new_ok = st.take(m);
+    dev_indices = reinterpret_cast<uint32_t*>(st.take(4 * m));
+    rebuild = x.dev + st.off;
+    HIP_TRY(hipMemcpyAsync(dev_indices, indices, 4 * m, hipMemcpyHostToDevice, x.s));
+    uint8_t* valid = nullptr;
+    if (int r = form.stage(*cp, P0, own, x.s, valid)) return r;
+    launch_build_key_tables(P0, P1, valid, np, m, new_tables, new_ok, x.s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(x.s));
+  }
+  // phase 2, exclusive: no library call is enqueueing on any key set; the device runs dry before the first byte of
+  // the set changes, so a call enqueued earlier decides on the old set and a later one on the new
+  std::unique_lock<std::shared_mutex> lk(g_ks_mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!registered(ks) || !ks->alive)
+    return fail(DSV_ERR_NOT_INITIALIZED, "the key set's device was shut down during the replace");
+  DeviceGuard guard(ks->device);
+  if (guard.err != hipSuccess) return fail(DSV_ERR_HIP, "cannot select device %d", ks->device);
+  HIP_TRY(hipDeviceSynchronize());
+  const int rc = [&]() -> int {
+    launch_replace_commit(np, dev_indices, m, new_tables, new_ok, P0, P1, ks->tables, ks->key_ok,
+                          ks->index[kKeyAffine].rows, ks->index[kKeyRecord].rows, x.s);
+    HIP_TRY(hipGetLastError());
+    if (int r = rebuild_indices(ks, rebuild, x.s)) return r;
+    HIP_TRY(hipStreamSynchronize(x.s));
+    return DSV_OK;
+  }();
+  if (rc != DSV_OK) {  // the set may hold a mixture: it is dead from here on
+    free_device_memory(ks);
+    ks->alive = false;
+  }
+  g_replace_exclusive_ns.store(
+      (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(),
+      std::memory_order_relaxed);
+  return rc;
+}
+
 KeysetForm keyset_form_affine(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t m) {
   const bool two = keyset_points(scheme) == 2;
   return {[=] { return !pk_uv || (two && !pk2_uv) ? fail(DSV_ERR_INVALID_ARGUMENT, "null pointer") : DSV_OK; }, 0,
@@ -344,6 +460,32 @@ int dsv_keyset_append(dsv_keyset* ks, const uint8_t* pk_uv, const uint8_t* pk2_u
 }
 int dsv_keyset_append_wire(dsv_keyset* ks, const uint8_t* pk_bytes, size_t m, uint32_t* first_index) {
   return append_keyset(ks, m, first_index, [=](int scheme) { return keyset_form_wire(scheme, pk_bytes, m); });
+}
+
+int dsv_keyset_replace(dsv_keyset* ks, const uint32_t* indices, const uint8_t* pk_uv, const uint8_t* pk2_uv,
+                       size_t m) {
+  return replace_keyset(ks, indices, m, [=](int scheme) { return keyset_form_affine(scheme, pk_uv, pk2_uv, m); });
+}
+int dsv_keyset_replace_wire(dsv_keyset* ks, const uint32_t* indices, const uint8_t* pk_bytes, size_t m) {
+  return replace_keyset(ks, indices, m, [=](int scheme) { return keyset_form_wire(scheme, pk_bytes, m); });
+}
+uint64_t dsv_debug_keyset_replace_exclusive_ns(void) {
+  return g_replace_exclusive_ns.load(std::memory_order_relaxed);
+}
+int dsv_debug_keyset_slots(const dsv_keyset* ks, int form, uint32_t* out, size_t room, size_t* slots_out) {
+  if (int r = library_up(ks)) return r;
+  if (!ks) return fail(DSV_ERR_INVALID_ARGUMENT, "null key set");
+  if (form != kKeyAffine && form != kKeyRecord) return fail(DSV_ERR_INVALID_ARGUMENT, "unknown key form %d", form);
+  std::shared_lock<std::shared_mutex> rl(g_ks_mu);
+  Context* cp = nullptr;
+  if (int r = keyset_context(ks, cp)) return r;
+  const size_t slots = ks->capacity ? ks->slot_mask + 1 : 0, n = slots < room ? slots : room;
+  if (slots_out) *slots_out = slots;
+  if (n == 0) return DSV_OK;
+  if (!out) return fail(DSV_ERR_INVALID_ARGUMENT, "null pointer");
+  DSV_ON_DEVICE(*cp);
+  HIP_TRY(hipMemcpy(out, ks->index[form].slots, 4 * n, hipMemcpyDeviceToHost));
+  return DSV_OK;
 }
 
 int dsv_keyset_capacity(const dsv_keyset* ks, size_t* capacity) {

@@ -3,111 +3,11 @@
 // build, and the lookup that turns a batch's keys into the key_idx column of the keyed kernels, one lane per
 // item.  Both are one kernel each over a key form — the affine bytes or the compressed records of the same keys.
 // Bytes in, indices out: no field arithmetic, no table of keyed.h is read, a hit costs no square root.
+#define DSV_INDEX_KERNELS
 #include "keyed_lookup.h"
 
 namespace dsv {
 namespace {
-
-// a row in registers: W x 16 B
-template <int W>
-struct Words {
-  uint4 q[W];
-};
-template <int W>
-__device__ __forceinline__ Words<W> load_row(const uint8_t* __restrict__ rows, size_t i) {
-  Words<W> w;
-  const uint4* p = reinterpret_cast<const uint4*>(rows + i * (size_t)(16 * W));
-#pragma unroll
-  for (int j = 0; j < W; j++) w.q[j] = p[j];
-  return w;
-}
-__device__ __forceinline__ bool same16(const uint4& x, const uint4& y) {
-  return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) == 0u;
-}
-template <int W>
-__device__ __forceinline__ bool same_words(const Words<W>& a, const Words<W>& b) {
-  bool eq = true;
-#pragma unroll
-  for (int j = 0; j < W; j++) eq &= same16(a.q[j], b.q[j]);
-  return eq;
-}
-template <int W>
-__device__ __forceinline__ uint32_t home_hash(const Words<W>& w) {
-  KeyHash h;
-#pragma unroll
-  for (int j = 0; j < W; j++) {
-    h.word(w.q[j].x);
-    h.word(w.q[j].y);
-    h.word(w.q[j].z);
-    h.word(w.q[j].w);
-  }
-  return h.finish();
-}
-
-// ---- the key forms: W = 16-byte words per row; source(P0, P1, j) = the row of the affine source key j (u || v,
-// 64 B per point), item(key_a, key_b, i) = the row of a batch's item i, occupant(...) = the row of the occupant
-// `old` of a slot as the append kernel compares it: a key of an earlier call (old < first) from the index's own
-// rows, a lane of this launch from the source points ----------------------------------------------------------
-
-// kKeyAffine: 64 B per point, the source key's bytes as they are; an item's columns are read the same way
-template <int NP>
-struct AffineKey {
-  static constexpr int W = 4 * NP;
-  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                    size_t i) {
-    Words<W> w;
-    const uint4* pa = reinterpret_cast<const uint4*>(a + i * 64);
-#pragma unroll
-    for (int j = 0; j < 4; j++) w.q[j] = pa[j];
-    if (NP == 2) {
-      const uint4* pb = reinterpret_cast<const uint4*>(b + i * 64);
-#pragma unroll
-      for (int j = 0; j < 4; j++) w.q[4 * (NP - 1) + j] = pb[j];
-    }
-    return w;
-  }
-  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                  size_t i) {
-    return source(a, b, i);
-  }
-  // one pointer select, one load (a pair of loads under `old < first` costs NP = 2 nine VGPRs and a wave of
-  // occupancy)
-  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
-                                                      const uint8_t* rows, uint32_t old, size_t first) {
-    const bool older = old < first;
-    const uint8_t* pa = older ? rows + (size_t)old * (size_t)(64 * NP) : P0 + (size_t)(old - first) * 64;
-    const uint8_t* pb = older ? pa + 64 : P1 + (size_t)(old - first) * 64;
-    return source(pa, pb, 0);
-  }
-};
-
-// kKeyRecord: 32 B per point, the compressed record of the source point — v, bit 255 = the lowest bit of u —
-// formed by byte operations; an item's record is one row at key_a (key_b unused)
-template <int NP>
-struct RecordKey {
-  static constexpr int W = 2 * NP;
-  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                    size_t i) {
-    Words<W> w;
-#pragma unroll
-    for (int p = 0; p < NP; p++) {
-      const uint4* pt = reinterpret_cast<const uint4*>((p ? b : a) + i * 64);
-      const uint32_t sign = pt[0].x << 31;
-      w.q[2 * p] = pt[2];
-      w.q[2 * p + 1] = pt[3];
-      w.q[2 * p + 1].w = (w.q[2 * p + 1].w & 0x7fffffffu) | sign;
-    }
-    return w;
-  }
-  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__,
-                                                  size_t i) {
-    return load_row<W>(a, i);
-  }
-  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
-                                                      const uint8_t* rows, uint32_t old, size_t first) {
-    return old < first ? load_row<W>(rows, old) : source(P0, P1, old - first);
-  }
-};
 
 // the lookup's tail, per block: the waves' sums meet in LDS, one atomic per block that missed at all
 __device__ __forceinline__ void add_block_misses(uint32_t missed, uint32_t& block_misses,

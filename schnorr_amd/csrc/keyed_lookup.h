@@ -85,4 +85,134 @@ hipError_t launch_index_lookup(KeyForm form, const uint8_t* key_a, const uint8_t
                                const uint8_t* rows, const uint32_t* slots, size_t mask, size_t k, uint32_t* key_idx,
                                uint32_t* misses, hipStream_t s);
 
+// ---- k_keyed_replace.hip: keys replaced in place (dsv_keyset_replace*) -----------------------
+// m keys built in a scratch of the call's own — tables (m * npoints tables, key-major), key_ok (m bytes), and the
+// affine points they were built from (P0 / P1 as for launch_index_append) — scattered into the set: key j's tables,
+// key_ok byte, affine index row and record index row (formed from the point as the append forms it) go to index
+// indices[j] (device memory, m pairwise distinct indices below the set's k).  16-byte loads and stores, grid-stride.
+void launch_replace_commit(int npoints, const uint32_t* indices, size_t m, const uint32_t* src_tables,
+                           const uint8_t* src_key_ok, const uint8_t* P0, const uint8_t* P1, uint32_t* tables,
+                           uint8_t* key_ok, uint8_t* affine_rows, uint8_t* record_rows, hipStream_t s);
+// the affine index rows of k keys (key-major) as the planar columns P0 [, P1] launch_index_append reads
+void launch_rows_to_planar(int npoints, const uint8_t* affine_rows, size_t k, uint8_t* P0, uint8_t* P1,
+                           hipStream_t s);
+// The canonical layout of the `form` index over keys 0 .. k - 1 — what inserting them one after the other in index
+// order gives: each valid key that equals no valid key of lower index in the first empty slot from its home slot
+// on.  reps: a slot array of the same size that holds exactly those keys' indices, in any layout (what
+// launch_index_append at first = 0 leaves in a cleared array); slots: the index's own, cleared earlier on `s`.  One
+// lane per slot of reps; the keys' bytes come from the affine rows (the record form: its rows' bytes formed from
+// them).
+void launch_index_reinsert(KeyForm form, int npoints, const uint8_t* affine_rows, const uint32_t* reps,
+                           uint32_t* slots, size_t mask, hipStream_t s);
+
 }  // namespace dsv
+
+#ifdef DSV_INDEX_KERNELS
+// what the kernel units of the indices share (k_keyed_lookup.hip, k_keyed_replace.hip)
+namespace dsv {
+namespace {
+
+// a row in registers: W x 16 B
+template <int W>
+struct Words {
+  uint4 q[W];
+};
+template <int W>
+__device__ __forceinline__ Words<W> load_row(const uint8_t* __restrict__ rows, size_t i) {
+  Words<W> w;
+  const uint4* p = reinterpret_cast<const uint4*>(rows + i * (size_t)(16 * W));
+#pragma unroll
+  for (int j = 0; j < W; j++) w.q[j] = p[j];
+  return w;
+}
+__device__ __forceinline__ bool same16(const uint4& x, const uint4& y) {
+  return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) == 0u;
+}
+template <int W>
+__device__ __forceinline__ bool same_words(const Words<W>& a, const Words<W>& b) {
+  bool eq = true;
+#pragma unroll
+  for (int j = 0; j < W; j++) eq &= same16(a.q[j], b.q[j]);
+  return eq;
+}
+template <int W>
+__device__ __forceinline__ uint32_t home_hash(const Words<W>& w) {
+  KeyHash h;
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    h.word(w.q[j].x);
+    h.word(w.q[j].y);
+    h.word(w.q[j].z);
+    h.word(w.q[j].w);
+  }
+  return h.finish();
+}
+
+// ---- the key forms: W = 16-byte words per row; source(P0, P1, j) = the row of the affine source key j (u || v,
+// 64 B per point), item(key_a, key_b, i) = the row of a batch's item i, occupant(...) = the row of the occupant
+// `old` of a slot as the append kernel compares it: a key of an earlier call (old < first) from the index's own
+// rows, a lane of this launch from the source points ----------------------------------------------------------
+
+// kKeyAffine: 64 B per point, the source key's bytes as they are; an item's columns are read the same way
+template <int NP>
+struct AffineKey {
+  static constexpr int W = 4 * NP;
+  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                    size_t i) {
+    Words<W> w;
+    const uint4* pa = reinterpret_cast<const uint4*>(a + i * 64);
+#pragma unroll
+    for (int j = 0; j < 4; j++) w.q[j] = pa[j];
+    if (NP == 2) {
+      const uint4* pb = reinterpret_cast<const uint4*>(b + i * 64);
+#pragma unroll
+      for (int j = 0; j < 4; j++) w.q[4 * (NP - 1) + j] = pb[j];
+    }
+    return w;
+  }
+  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                  size_t i) {
+    return source(a, b, i);
+  }
+  // one pointer select, one load (a pair of loads under `old < first` costs NP = 2 nine VGPRs and a wave of
+  // occupancy)
+  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
+                                                      const uint8_t* rows, uint32_t old, size_t first) {
+    const bool older = old < first;
+    const uint8_t* pa = older ? rows + (size_t)old * (size_t)(64 * NP) : P0 + (size_t)(old - first) * 64;
+    const uint8_t* pb = older ? pa + 64 : P1 + (size_t)(old - first) * 64;
+    return source(pa, pb, 0);
+  }
+};
+
+// kKeyRecord: 32 B per point, the compressed record of the source point — v, bit 255 = the lowest bit of u —
+// formed by byte operations; an item's record is one row at key_a (key_b unused)
+template <int NP>
+struct RecordKey {
+  static constexpr int W = 2 * NP;
+  static __device__ __forceinline__ Words<W> source(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                    size_t i) {
+    Words<W> w;
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+      const uint4* pt = reinterpret_cast<const uint4*>((p ? b : a) + i * 64);
+      const uint32_t sign = pt[0].x << 31;
+      w.q[2 * p] = pt[2];
+      w.q[2 * p + 1] = pt[3];
+      w.q[2 * p + 1].w = (w.q[2 * p + 1].w & 0x7fffffffu) | sign;
+    }
+    return w;
+  }
+  static __device__ __forceinline__ Words<W> item(const uint8_t* __restrict__ a, const uint8_t* __restrict__,
+                                                  size_t i) {
+    return load_row<W>(a, i);
+  }
+  static __device__ __forceinline__ Words<W> occupant(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1,
+                                                      const uint8_t* rows, uint32_t old, size_t first) {
+    return old < first ? load_row<W>(rows, old) : source(P0, P1, old - first);
+  }
+};
+
+}  // namespace
+}  // namespace dsv
+#endif

@@ -13,7 +13,8 @@
 
 // Everything but k is fixed when the set is created: the allocations are sized for `capacity` keys and never
 // move.  k is read under the registry's shared lock and raised by dsv_keyset_append under the exclusive one, so a
-// call that holds the shared lock sees one k from its first check to its last launch.
+// call that holds the shared lock sees one k from its first check to its last launch.  The bytes of registered keys
+// change only under the exclusive lock, on a device that has run dry (dsv_keyset_replace).
 struct dsv_keyset {
   int scheme = 0;
   size_t k = 0;         // keys registered
@@ -123,6 +124,14 @@ int create_keyset(int scheme, size_t k, size_t capacity, bool reserved, dsv_keys
 // its own; blocks.  *first_index (may be null) = the index of the first of them.
 int append_keyset(dsv_keyset* ks, size_t m, uint32_t* first_index,
                   const std::function<KeysetForm(int scheme)>& form_of);
+// dsv_keyset_replace*: the m keys of the form form_of(the set's scheme) take the places indices[0 .. m - 1] (host
+// array, pairwise distinct, each below k) of a live set, in place; blocks.  Two phases: under the
+// registry's shared lock the keys are staged and their tables built into a scratch of the call's own, on a stream of
+// its own, beside the verify calls; under the exclusive lock, after a device-wide wait, one kernel scatters the
+// scratch into the set and both indices are rebuilt from the set's own rows in the canonical layout.  Serialised
+// with the appends to the set (append_mu).  A HIP failure in the second phase leaves the set dead.
+int replace_keyset(dsv_keyset* ks, const uint32_t* indices, size_t m,
+                   const std::function<KeysetForm(int scheme)>& form_of);
 // the three forms over m keys
 KeysetForm keyset_form_affine(int scheme, const uint8_t* pk_uv, const uint8_t* pk2_uv, size_t m);
 KeysetForm keyset_form_wire(int scheme, const uint8_t* pk_bytes, size_t m);

@@ -961,6 +961,20 @@ def keyset_home_slot(scheme, k, key_a, key_b=None):
         ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k), _p(a), _p(b) if b is not None else ctypes.c_void_p(0)))
 
 
+def keyset_slots(ks, form):
+    """dsv_debug_keyset_slots: the slot array of one of a KeySet's indices — form 0 / "affine": over the affine
+    bytes, 1 / "record": over the compressed records — as uint32 [slots]; a slot holds a key index or KEY_NONE"""
+    form = {"affine": 0, "record": 1}.get(form, form)
+    L = _lib.load()
+    slots = ctypes.c_size_t()
+    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), ctypes.c_int(form), ctypes.c_void_p(0), ctypes.c_size_t(0),
+                                        ctypes.byref(slots)))
+    out = np.zeros(slots.value, dtype=np.uint32)
+    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), ctypes.c_int(form), _p(out), ctypes.c_size_t(out.shape[0]),
+                                        ctypes.byref(slots)))
+    return out
+
+
 def _keyed_mont_widths(scheme):
     """widths of a keyed typed batch's columns: u, R[, R'], key_idx, m"""
     return [32] + [96] * (2 if scheme == "double" else 1) + [4, 32]
@@ -1045,6 +1059,8 @@ class KeySet:
         ks = KeySet.reserved("single", 4096, PK)   # room for 4096 keys (PK may be omitted: an empty set)
         first = ks.append(PK_new)                  # in place: indices first .. first + m - 1; append_wire(records),
         ks.k, ks.capacity                          # append_mont_cols([pk96]) for the other key forms
+        ks.replace([3, 17], PK_two)                # eviction: new keys in the places of registered ones, in place;
+        ks.replace_wire([5], record)               # k and every other key's index stay
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None, capacity=None):
@@ -1126,6 +1142,33 @@ class KeySet:
         rc = _lib.load().dsv_keyset_append_mont_cols(self._handle(), arr, ctypes.c_size_t(m), ctypes.byref(first))
         del held
         return self._appended(rc, first)
+
+    @staticmethod
+    def _indices(indices, m):
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32).reshape(-1))
+        if idx.shape[0] != m:
+            raise ValueError("%d indices for %d keys" % (idx.shape[0], m))
+        return idx
+
+    def replace(self, indices, PK, PK2=None):
+        """dsv_keyset_replace: key j (affine points, uint8 [m, 64]; PK2 for the two-point schemes) takes the place
+        of key indices[j] — pairwise distinct indices below k — in place; blocks.  k, the capacity and every other
+        key's index stay; calls enqueued afterwards see the new keys.  No graph that holds the set may be replayed,
+        and no stream of the device may be capturing, while it runs."""
+        if (PK2 is None) != (self.scheme == "single"):
+            raise ValueError("scheme %s takes %s" % (self.scheme, "PK only" if self.scheme == "single" else "PK and PK2"))
+        arrs = [_arr(PK, 64)] + ([_arr(PK2, 64)] if PK2 is not None else [])
+        m = _same_n(*arrs)
+        idx = self._indices(indices, m)
+        _lib.check(_lib.load().dsv_keyset_replace(
+            self._handle(), _p(idx), _p(arrs[0]), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0),
+            ctypes.c_size_t(m)))
+
+    def replace_wire(self, indices, records):
+        """dsv_keyset_replace_wire: replace() for the reference's key records ([m, 32] or [m, 64])"""
+        rec = _arr(records, 32 if self.scheme == "single" else 64)
+        idx = self._indices(indices, rec.shape[0])
+        _lib.check(_lib.load().dsv_keyset_replace_wire(self._handle(), _p(idx), _p(rec), ctypes.c_size_t(rec.shape[0])))
 
     @classmethod
     def from_wire(cls, scheme, pk_bytes):
