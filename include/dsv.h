@@ -929,6 +929,68 @@ int dsv_verify_double_keyed_open_wire(const dsv_keyset *ks, const uint8_t *sig96
                                       const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
 int dsv_verify_vargen_keyed_open_wire(const dsv_keyset *ks, const uint8_t *sig64, const uint8_t *pk64,
                                       const uint8_t *m, size_t n, uint8_t *ok, size_t *misses);
+/* ---- the key cache for typed objects: open-set verify of verify_batch's arguments --------
+ * The caller that holds the reference's in-memory types and calls verify_batch(&[Signature], &[PublicKey],
+ * &[BlsScalar]): Montgomery limbs and projective points as described under "the reference's IN-MEMORY
+ * representation" above (scalar 32 B; point 96 B = limbs of u || v || z, t1 / t2 never read).  The key set carries
+ * its scheme, so there is one entry point per form.
+ *   Columns     those of dsv_verify_*_mont_cols, in their order and widths: single u, R, PK, m [4]; double u, R, R',
+ *               PK, PK', m [6]; var-generator u, R, PK, Gen, m [5]; widths 32 / 96 / 32.  The _dev form takes them as
+ *               arguments: key_a_uvz = PK, key_b_uvz = PK' (double) / Gen (var-generator), NULL and ignored for a
+ *               single set; Rp_uvz is required for a double set and ignored otherwise.
+ *   Verdicts    ok[i] = what dsv_verify_{single,double,vargen}_mont_dev writes for the same limbs, for every input.
+ *               Limbs not below their modulus and z = 0 give 0.  Registering a key changes how fast a verdict
+ *               arrives and never the verdict.
+ *   Hit         the item's key limbs are usable (every limb group < q, every z != 0) and its normalised affine bytes
+ *               (u/z, v/z, canonical) equal, byte for byte, those of a VALID registered key — the pair (PK, PK') for
+ *               the double scheme, (PK, Gen) for the var-generator scheme; the lowest such index wins.  The item's z
+ *               and the route by which the key was registered (affine, wire, typed, appended, replaced) do not
+ *               matter.  A hit is decided by that key's tables.  Every other item is a miss, not an error — an
+ *               unregistered key, a registered but invalid key, a registered PK beside another key's PK' / Gen, a
+ *               point off the curve, unusable key limbs — and is decided by the unkeyed equation in the same call.
+ *   misses      the number of items that took the unkeyed path, items with unusable key limbs INCLUDED (their
+ *               verdict is 0 either way).  _dev form: may be NULL; else one 4-byte-aligned uint32 on the set's
+ *               device, zeroed on the stream by a one-lane kernel and then added to.  Host form: a size_t, summed
+ *               over the chunks and read back once at the end of the call; may be NULL.
+ *   _dev form   checks, order, error codes and texts of dsv_verify_keyed_open_dev: a dead set
+ *               DSV_ERR_NOT_INITIALIZED; n = 0 DSV_OK with nothing enqueued; a NULL pointer with n > 0 (key_b_uvz of
+ *               a two-point set included), a short workspace, outputs that are not on the set's device:
+ *               DSV_ERR_INVALID_ARGUMENT, nothing launched, `ok` untouched.  Alignment: the kernel loads limbs in
+ *               16-byte loads — every input column must be 16-byte aligned, misses 4-byte aligned
+ *               (DSV_ERR_INVALID_ARGUMENT otherwise, nothing launched).  Enqueue-only on `stream`, one straight
+ *               chain, never synchronises, may be captured: ONE front kernel (normalisation of every point, the two
+ *               scalar conversions, the lookup of the normalised key in the set's affine index), the challenge hash
+ *               and the keyed kernel over all n (a miss gets 0 there), the miss list, the unkeyed equation over the
+ *               list on the normalised key columns, of which only the rows of misses are ever written.  A call
+ *               carries the k it was enqueued with (the stale-k rule of "key sets that grow"); an empty set (k = 0):
+ *               every item takes the unkeyed path.  DSV_OPEN_MONT_FUSED=0 (read by dsv_init) runs the front as two
+ *               launches — the *_mont forms' normalisation over all points, then dsv_keyset_lookup_dev's kernel —
+ *               and a gate that makes an item with unusable key limbs a miss whatever its normalised bytes are:
+ *               the same outputs for every input (A/B and cross-check).
+ *   Workspace   dsv_keyed_open_mont_workspace_bytes(scheme, n) = the index column (4 B per item) + the miss list (4 B
+ *               per item) + 256 (its length) + the unkeyed kernel's per-lane window tables (min(ceil(n / 64), 4096) *
+ *               64 lanes * 3888 B) + the key columns of the misses (64 B per item and key point) + the normalised
+ *               u (32 B), m (32 B), R (64 B)[, R' (64 B)] + the validity bytes (1 B per item) + the prefix products
+ *               of all points (points * (n + 32) * 36 B, points = 2 / 4 / 3) + dsv_keyed_workspace_bytes(n); each
+ *               part rounded up to 256 B, in this order: the index column is first, as in every by-value call;
+ *               device, 256-byte aligned; never smaller for a larger n; no GPU needed; 0 for an unknown scheme.
+ *   Host form   reads the objects where they lie and runs on the key set's device through the chunked host pipeline
+ *               (one front launch per chunk; hash, keyed kernel and miss branch per sub-batch; copy and compute
+ *               overlap; dsv_set_host_threads and the two-calls-in-flight rule apply); blocks; a set cannot be
+ *               destroyed or shut down under a running call.  Column checks as dsv_verify_*_mont_cols ("column k:
+ *               ...").
+ *   Submit      as dsv_verify_keyed_mont_cols_submit: the job holds the set from before submit returns.  The
+ *               submitted form reports no miss count.
+ *   Before dsv_init a call of this group with a NULL handle returns DSV_ERR_NOT_INITIALIZED. */
+size_t dsv_keyed_open_mont_workspace_bytes(int scheme, size_t n);
+int dsv_verify_keyed_open_mont_dev(const dsv_keyset *ks, const void *u, const void *R_uvz,
+                                   const void *Rp_uvz /* double only, else NULL */, const void *key_a_uvz,
+                                   const void *key_b_uvz /* PK' | Gen, NULL for single */, const void *m, size_t n,
+                                   void *ok, void *workspace, size_t workspace_bytes, void *stream, void *misses);
+int dsv_verify_keyed_open_mont_cols(const dsv_keyset *ks, const dsv_column *cols /*[4|6|5]*/, size_t n, uint8_t *ok,
+                                    size_t *misses /* may be NULL */);
+int dsv_verify_keyed_open_mont_cols_submit(const dsv_keyset *ks, const dsv_column *cols /*[4|6|5]*/, size_t n,
+                                           uint8_t *ok, dsv_job **job);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

@@ -952,8 +952,50 @@ class BasicKeySet {
     detail::same_len(sigs.size(), idx.size(), msgs.size(), "KeySet::verify_batch_submit");
     return verify_batch_submit(sigs.data(), idx.data(), msgs.data(), sigs.size());
   }
+  // The set as a key CACHE over exactly verify_batch's arguments (dsv_verify_keyed_open_mont_cols): the verdicts of
+  // the free function verify_batch* on the same objects, for every input — `keys.verify_batch_open(sigs, pks, msgs)
+  // == verify_batch(sigs, pks, msgs)`.  An item whose key equals a valid registered key (whatever its z) is decided by
+  // that key's tables, every other item by the unkeyed equation in the same call; *misses (may be null) counts those.
+  std::vector<uint8_t> verify_batch_open_bytes(const Sig* sigs, const Key* pks, const BlsScalar* msgs, size_t n,
+                                               size_t* misses = nullptr) const {
+    std::vector<uint8_t> ok(n);
+    if (misses) *misses = 0;
+    if (!n) return ok;
+    dsv_column cols[6];
+    open_columns(sigs, pks, msgs, cols);
+    detail::check(dsv_verify_keyed_open_mont_cols(ks_, cols, n, ok.data(), misses), "dsv_verify_keyed_open_mont_cols");
+    return ok;
+  }
+  std::vector<bool> verify_batch_open(const std::vector<Sig>& sigs, const std::vector<Key>& pks,
+                                      const std::vector<BlsScalar>& msgs, size_t* misses = nullptr) const {
+    detail::same_len(sigs.size(), pks.size(), msgs.size(), "KeySet::verify_batch_open");
+    return detail::to_bools(verify_batch_open_bytes(sigs.data(), pks.data(), msgs.data(), sigs.size(), misses));
+  }
+  // returns at once; `wait()` gives what verify_batch_open would have (no miss count).  The objects must outlive the
+  // wait; destroying the set waits for the job
+  BatchJob verify_batch_open_submit(const Sig* sigs, const Key* pks, const BlsScalar* msgs, size_t n) const {
+    BatchJob j;
+    j.ok_.assign(n, 0);
+    if (!n) return j;
+    dsv_column cols[6];
+    open_columns(sigs, pks, msgs, cols);
+    detail::check(dsv_verify_keyed_open_mont_cols_submit(ks_, cols, n, j.ok_.data(), &j.job_),
+                  "dsv_verify_keyed_open_mont_cols_submit");
+    return j;
+  }
+  BatchJob verify_batch_open_submit(const std::vector<Sig>& sigs, const std::vector<Key>& pks,
+                                    const std::vector<BlsScalar>& msgs) const {
+    detail::same_len(sigs.size(), pks.size(), msgs.size(), "KeySet::verify_batch_open_submit");
+    return verify_batch_open_submit(sigs.data(), pks.data(), msgs.data(), sigs.size());
+  }
 
  private:
+  // u, R[, R'], PK[, PK' | Gen], m: the columns of dsv_verify_*_mont_cols
+  static void open_columns(const Sig* sigs, const Key* pks, const BlsScalar* msgs, dsv_column* cols) {
+    const int c = T::sig_cols(sigs, cols);
+    T::key_cols(pks, cols + c);
+    cols[c + (T::scheme == 0 ? 1 : 2)] = {msgs, 32};
+  }
   static void columns(const Sig* sigs, const uint32_t* idx, const BlsScalar* msgs, dsv_column* cols) {
     const int c = T::sig_cols(sigs, cols);
     cols[c] = {idx, sizeof(uint32_t)};

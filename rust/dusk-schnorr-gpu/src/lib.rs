@@ -143,6 +143,19 @@ extern "C" {
                                              n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
     pub fn dsv_verify_vargen_keyed_open_wire(ks: *const c_void, sig64: *const u8, pk64: *const u8, m: *const u8,
                                              n: usize, ok: *mut u8, misses: *mut usize) -> c_int;
+    // the key cache for typed objects (include/dsv.h, "open-set verify of verify_batch's arguments"): the columns of
+    // dsv_verify_*_mont_cols — single u, R, PK, m | double u, R, R', PK, PK', m | var-generator u, R, PK, Gen, m
+    // (widths 32 / 96 / 32) — against a key set used as a cache.  The verdicts of dsv_verify_*_mont_dev for every
+    // input; misses (may be null) = the items that took the unkeyed path.
+    pub fn dsv_keyed_open_mont_workspace_bytes(scheme: c_int, n: usize) -> usize;
+    pub fn dsv_verify_keyed_open_mont_dev(ks: *const c_void, u: *const c_void, r_uvz: *const c_void,
+                                          rp_uvz: *const c_void, key_a_uvz: *const c_void, key_b_uvz: *const c_void,
+                                          m: *const c_void, n: usize, ok: *mut c_void, workspace: *mut c_void,
+                                          workspace_bytes: usize, stream: *mut c_void, misses: *mut c_void) -> c_int;
+    fn dsv_verify_keyed_open_mont_cols(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8,
+                                       misses: *mut usize) -> c_int;
+    fn dsv_verify_keyed_open_mont_cols_submit(ks: *const c_void, cols: *const Column, n: usize, ok: *mut u8,
+                                              job: *mut *mut c_void) -> c_int;
     // keys replaced in place (include/dsv.h, "keys replaced in place"): key j of the call takes the place of key
     // indices[j] (m pairwise distinct indices below k) of a live set; blocks, quiesces the set's device.  No graph
     // that holds the set may be replayed, and no stream of the device may be capturing, meanwhile.  Raw exports.
@@ -530,6 +543,72 @@ impl<K> KeySet<K> {
             check(dsv_verify_keyed_mont_cols_submit(self.ks, cols.as_ptr(), n, j.ok.as_mut_ptr(), &mut j.job))?;
         }
         Ok(j)
+    }
+}
+impl<K> KeySet<K> {
+    /// the open form over the columns of `verify_batch*` -> (verdicts, items that took the unkeyed path)
+    fn run_open(&self, cols: &[Column], n: usize) -> Result<(Vec<bool>, usize), EngineError> {
+        let mut ok = vec![0u8; n];
+        let mut misses = 0usize;
+        if n != 0 {
+            check(unsafe { dsv_verify_keyed_open_mont_cols(self.ks, cols.as_ptr(), n, ok.as_mut_ptr(), &mut misses) })?;
+        }
+        Ok((verdicts(ok), misses))
+    }
+    unsafe fn start_open<'a>(&'a self, cols: &[Column], n: usize) -> Result<BatchJob<'a>, EngineError> {
+        let mut j = BatchJob { job: core::ptr::null_mut(), ok: vec![0u8; n], _soa: None, _borrow: core::marker::PhantomData };
+        if n != 0 {
+            check(dsv_verify_keyed_open_mont_cols_submit(self.ks, cols.as_ptr(), n, j.ok.as_mut_ptr(), &mut j.job))?;
+        }
+        Ok(j)
+    }
+}
+/// The set as a key CACHE over exactly the arguments of [`verify_batch`]: `keys.verify_batch_open(sigs, pks, msgs)?.0
+/// == verify_batch(sigs, pks, msgs)` for every input.  An item whose key equals a valid registered key (whatever
+/// its z) is decided by that key's tables, every other item by the unkeyed equation in the same call; the second
+/// value counts those.
+impl KeySet<PublicKey> {
+    pub fn verify_batch_open(&self, sigs: &[Signature], pks: &[PublicKey], msgs: &[BlsScalar])
+        -> Result<(Vec<bool>, usize), EngineError> {
+        assert!(sigs.len() == pks.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok((Vec::new(), 0));
+        }
+        self.run_open(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(pks[0].as_ref(), pks), col(&msgs[0], msgs)],
+                      sigs.len())
+    }
+    /// # Safety
+    /// As for [`verify_batch_submit`]: the job must be waited for or dropped, never leaked.
+    pub unsafe fn verify_batch_open_submit<'a>(&'a self, sigs: &'a [Signature], pks: &'a [PublicKey],
+                                               msgs: &'a [BlsScalar]) -> Result<BatchJob<'a>, EngineError> {
+        assert!(sigs.len() == pks.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return self.start_open(&[], 0);
+        }
+        self.start_open(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(pks[0].as_ref(), pks),
+                          col(&msgs[0], msgs)], sigs.len())
+    }
+}
+impl KeySet<PublicKeyDouble> {
+    pub fn verify_batch_open(&self, sigs: &[SignatureDouble], pks: &[PublicKeyDouble], msgs: &[BlsScalar])
+        -> Result<(Vec<bool>, usize), EngineError> {
+        assert!(sigs.len() == pks.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok((Vec::new(), 0));
+        }
+        self.run_open(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(sigs[0].R_prime(), sigs),
+                        col(pks[0].pk(), pks), col(pks[0].pk_prime(), pks), col(&msgs[0], msgs)], sigs.len())
+    }
+}
+impl KeySet<PublicKeyVarGen> {
+    pub fn verify_batch_open(&self, sigs: &[SignatureVarGen], pks: &[PublicKeyVarGen], msgs: &[BlsScalar])
+        -> Result<(Vec<bool>, usize), EngineError> {
+        assert!(sigs.len() == pks.len() && sigs.len() == msgs.len());
+        if sigs.is_empty() {
+            return Ok((Vec::new(), 0));
+        }
+        self.run_open(&[col(sigs[0].u(), sigs), col(sigs[0].R(), sigs), col(pks[0].public_key(), pks),
+                        col(pks[0].generator(), pks), col(&msgs[0], msgs)], sigs.len())
     }
 }
 fn idx_col(idx: &[u32]) -> Column {

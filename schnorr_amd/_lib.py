@@ -86,6 +86,9 @@ SYMBOLS = [
     "dsv_verify_double_keyed_open_wire", "dsv_verify_vargen_keyed_open_wire",
     # keys replaced in place: the key cache's eviction
     "dsv_keyset_replace", "dsv_keyset_replace_wire", "dsv_debug_keyset_slots", "dsv_debug_keyset_replace_exclusive_ns",
+    # the key cache for typed objects: open-set verify of verify_batch's arguments
+    "dsv_keyed_open_mont_workspace_bytes", "dsv_verify_keyed_open_mont_dev", "dsv_verify_keyed_open_mont_cols",
+    "dsv_verify_keyed_open_mont_cols_submit",
 ]
 _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_scratch_bytes",
                  "dsv_ext_workspace_bytes", "dsv_wire_workspace_bytes", "dsv_mont_workspace_bytes",
@@ -93,7 +96,8 @@ _SIZE_T_FUNCS = ("dsv_workspace_bytes", "dsv_mixed_workspace_bytes", "dsv_split_
                  "dsv_keyset_bytes", "dsv_keyed_workspace_bytes", "dsv_keyed_rlc_workspace_bytes",
                  "dsv_keyed_wire_workspace_bytes", "dsv_keyed_mont_workspace_bytes",
                  "dsv_keyset_index_bytes", "dsv_keyed_lookup_workspace_bytes", "dsv_keyed_open_workspace_bytes",
-                 "dsv_keyset_wire_index_bytes", "dsv_keyed_open_wire_workspace_bytes")
+                 "dsv_keyset_wire_index_bytes", "dsv_keyed_open_wire_workspace_bytes",
+                 "dsv_keyed_open_mont_workspace_bytes")
 
 
 class Column(ctypes.Structure):
@@ -159,6 +163,11 @@ def load():
         getattr(L, "dsv_verify_%s_keyed_open_wire_dev" % scheme).argtypes = [vp] * 4 + [sz, vp, vp, sz, vp, vp]
         getattr(L, "dsv_verify_%s_keyed_open_wire" % scheme).argtypes = [vp] * 4 + [sz, vp, vp]
     L.dsv_keyset_lookup_wire_dev.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.dsv_keyed_open_mont_workspace_bytes.argtypes = [ctypes.c_int, sz]
+    # (ks, u, R, Rp, key_a, key_b, m, n, ok, workspace, workspace_bytes, stream, misses)
+    L.dsv_verify_keyed_open_mont_dev.argtypes = [vp] * 7 + [sz, vp, vp, sz, vp, vp]
+    L.dsv_verify_keyed_open_mont_cols.argtypes = [vp, vp, sz, vp, vp]         # (ks, cols, n, ok, misses)
+    L.dsv_verify_keyed_open_mont_cols_submit.argtypes = [vp, vp, sz, vp, vp]  # (ks, cols, n, ok, job)
     L.dsv_keyset_lookup_wire.argtypes = [vp, vp, sz, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported

@@ -280,6 +280,9 @@ void release_context(Context& ctx) {
   if (ctx.ts_hash) (void)hipFree(ctx.ts_hash);
   ctx.ts_cancel = nullptr;
   ctx.ts_hash = nullptr;
+  if (ctx.miss_words) (void)hipFree(ctx.miss_words);
+  ctx.miss_words = nullptr;
+  ctx.miss_words_used = 0;
   if (ctx.stage) {
     (void)hipMemset(ctx.stage, 0, ctx.stage_bytes);  // may hold secret keys / nonces
     (void)hipFree(ctx.stage);
@@ -401,6 +404,8 @@ int dsv_init(int device) {
   ctx.small_overlap = !(sov && strcmp(sov, "0") == 0);
   const char* fused = getenv("DSV_DOUBLE_FUSED");
   ctx.fuse_double = !(fused && strcmp(fused, "0") == 0);
+  const char* omf = getenv("DSV_OPEN_MONT_FUSED");
+  ctx.open_mont_fused = !(omf && strcmp(omf, "0") == 0);
   const char* pre = getenv("DSV_PIPE_PREP_STREAM");
   ctx.prep_stream = pre && strcmp(pre, "1") == 0;
   auto log2_env = [](const char* name, int lo, int hi, int dflt) {

@@ -14,6 +14,8 @@
 //   dsv_keyed_open.hip    key sets as a key cache: open-set verify, the misses take the unkeyed equation (keyed_open.h)
 //   dsv_keyed_open_wire.hip  the key cache for serialized records: open-set verify by
 //                         compressed key (keyed_open_wire.h)
+//   dsv_keyed_open_mont.hip  the key cache for typed objects: open-set verify of verify_batch's
+//                         arguments (keyed_open_mont.h)
 // The host pipeline itself (run_pipelined, run_multi) is a template: dsv_pipeline.h.
 // Nothing here is part of the C ABI (include/dsv.h); everything lives in namespace dsvh.
 #pragma once
@@ -118,6 +120,7 @@ struct Context {
   bool split = true;         // DSV_SPLIT=0: one stream, whole batch per launch
   bool fuse_double = true;   // DSV_DOUBLE_FUSED=0: two single-equation launches per double batch (r01; A/B)
   bool quad = true;          // DSV_QUAD=0: batches of <= 2^14 items also take the one-lane-per-signature kernel
+  bool open_mont_fused = true;  // DSV_OPEN_MONT_FUSED=0: the open typed form's front as two launches (A/B)
   bool small_overlap = true; // DSV_SMALL_OVERLAP=0: small batches build their window tables inside the verify kernel
   u32* table[2] = {nullptr, nullptr};  // fixed-base tables for G, G'
   u32* ts_cancel = nullptr;            // square-root tables (decode29.h)
@@ -170,6 +173,11 @@ struct Context {
   std::mutex rlc_pinned_mu;
   u32* rlc_pinned = nullptr;
   std::atomic<u32> rlc_slot{0};
+  // the open typed host form's miss counters (dsv_keyed_open_mont.hip): 64 device words, made on first use, one
+  // lent to a call from its first chunk to its read-back; bit w of miss_words_used: word w is out
+  std::mutex miss_words_mu;
+  u32* miss_words = nullptr;
+  uint64_t miss_words_used = 0;
 };
 extern Context g_ctx[kMaxDevices];
 extern std::mutex g_init_mu;               // dsv_init / dsv_shutdown

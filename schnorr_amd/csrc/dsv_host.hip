@@ -250,7 +250,7 @@ struct dsv_job {
   int rc = DSV_OK;
   std::string err;
   int kind = 0;
-  const dsv_keyset* ks = nullptr;  // the keyed typed-object form (keyed_mont.h); null: the unkeyed one of `kind`
+  const dsv_keyset* ks = nullptr;  // a keyed typed-object form (keyed_mont.h: `kind` says which); null: unkeyed
   int ncols = 0;
   dsv_column cols[6] = {};
   size_t n = 0;
@@ -294,8 +294,12 @@ int submit_cols_job(const dsv_keyset* ks, int kind, const dsv_column* cols, int 
         const int d = t_device >= 0 ? t_device : g_primary.load(std::memory_order_acquire);
         if (d >= 0 && d < kMaxDevices) (void)pin_this_thread(g_ctx[d].numa_cpus);
       }
-      j->rc = j->ks ? verify_keyed_mont_cols_locked(j->ks, j->cols, j->n, j->ok)
-                    : verify_host_cols(j->kind, kMont, j->cols, j->n, j->ok, true);
+      if (!j->ks)
+        j->rc = verify_host_cols(j->kind, kMont, j->cols, j->n, j->ok, true);
+      else if (j->kind == kOpenMontJob)
+        j->rc = verify_keyed_open_mont_cols_locked(j->ks, j->cols, j->n, j->ok, nullptr);
+      else
+        j->rc = verify_keyed_mont_cols_locked(j->ks, j->cols, j->n, j->ok);
       if (j->rc) j->err = g_err;  // the text lives in this thread's thread-local
       if (j->ks) registry.unlock();
       j->finished.store(true, std::memory_order_release);

@@ -40,9 +40,16 @@ int check_keyed_mont_cols(const dsv_keyset* ks, const dsv_column* cols, size_t n
 // the host form's body; the caller holds the registry's shared lock from here to the last verdict
 int verify_keyed_mont_cols_locked(const dsv_keyset* ks, const dsv_column* cols, size_t n, uint8_t* ok);
 
+// dsv_keyed_open_mont.hip: the open typed form's host body — cols: u, the scheme's points, m, as
+// dsv_verify_*_mont_cols takes them; *misses (may be null) = the items that took the unkeyed path.  The caller
+// holds the registry's shared lock from here to the last verdict
+int verify_keyed_open_mont_cols_locked(const dsv_keyset* ks, const dsv_column* cols, size_t n, uint8_t* ok,
+                                       size_t* misses);
+constexpr int kOpenMontJob = 1;  // submit_cols_job's `kind` of a keyed job that runs the open form (0: by index)
+
 // dsv_host.hip: a column batch as a job on a driver thread (dsv_job).  ks null: the unkeyed typed-object form
-// of scheme `kind`; else the keyed form, whose driver holds the registry's shared lock from before submit
-// returns until its last verdict
+// of scheme `kind`; else a keyed form (kind 0: by key index, kOpenMontJob: the open form), whose driver holds the
+// registry's shared lock from before submit returns until its last verdict
 int submit_cols_job(const dsv_keyset* ks, int kind, const dsv_column* cols, int ncols, size_t n, uint8_t* ok,
                     dsv_job** out);
 

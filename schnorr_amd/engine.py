@@ -927,6 +927,13 @@ def keyed_open_wire_workspace_bytes(scheme, n):
     return int(_lib.load().dsv_keyed_open_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
 
 
+def keyed_open_mont_workspace_bytes(scheme, n):
+    """dsv_keyed_open_mont_workspace_bytes: device bytes of KeySet.verify_open_mont_dev's workspace (no GPU needed)"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return int(_lib.load().dsv_keyed_open_mont_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+
+
 def keyset_wire_home_slot(scheme, capacity, record):
     """dsv_debug_keyset_wire_home_slot: where the probe for a key record (32 bytes per key point) starts in the
     wire index of a set of `capacity` keys (no GPU needed)"""
@@ -1011,6 +1018,20 @@ class KeyedMontColsJob(MontColsJob):
         self._ok = np.zeros(n, dtype=np.uint8)
         self._job = ctypes.c_void_p()
         _lib.check(_lib.load().dsv_verify_keyed_mont_cols_submit(
+            keyset._handle(), arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
+
+
+class KeyedOpenMontColsJob(MontColsJob):
+    """An open typed batch in flight (dsv_verify_keyed_open_mont_cols_submit): MontColsJob's interface; reports no
+    miss count.  Keeps the key set and the column arrays alive until the wait."""
+
+    def __init__(self, keyset, cols):  # noqa: D107 (does not call the base constructor: another entry point)
+        widths = _layout(keyset.scheme, "_mont")[1]
+        n, arr, held = _keyed_columns(cols, widths, "submit_open_mont_cols")
+        self._cols = (keyset, held)
+        self._ok = np.zeros(n, dtype=np.uint8)
+        self._job = ctypes.c_void_p()
+        _lib.check(_lib.load().dsv_verify_keyed_open_mont_cols_submit(
             keyset._handle(), arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
 
 
@@ -1575,3 +1596,46 @@ class KeySet:
             self._handle(), self._rec_ptr(sig, sb, "sig"), self._rec_ptr(pk, self._rec_bytes(), "pk"), _tp(m, 32),
             ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
             self._misses_ptr(misses, dev)))
+
+    # ---- the key cache for typed objects: verify_batch's arguments, Montgomery limbs ---------------------------
+    def verify_open_mont_cols(self, cols):
+        """Open-set verify of typed objects where they lie (dsv_verify_keyed_open_mont_cols): cols as for
+        verify_mont_cols of the module — single [u, R, PK, m], double [u, R, R', PK, PK', m], vargen [u, R, PK, Gen,
+        m]; uint8 views [n, 32 | 96 | 32] of Montgomery limbs with strided rows — -> (verdicts [n], misses).  The
+        verdicts are verify_mont_cols' for every input; an item whose normalised key is not a valid registered key
+        is decided by the unkeyed equation in the same call, and misses counts those."""
+        n, arr, held = _keyed_columns(cols, _layout(self.scheme, "_mont")[1], "verify_open_mont_cols")
+        ok = np.zeros(n, dtype=np.uint8)
+        misses = ctypes.c_size_t()
+        _lib.check(_lib.load().dsv_verify_keyed_open_mont_cols(self._handle(), arr, ctypes.c_size_t(n), _p(ok),
+                                                               ctypes.byref(misses)))
+        del held
+        return ok, misses.value
+
+    def submit_open_mont_cols(self, cols):
+        """Asynchronous verify_open_mont_cols (dsv_verify_keyed_open_mont_cols_submit): returns a job at once
+        (`wait()` -> verdicts, `done()`; no miss count); the set cannot be destroyed or shut down under it."""
+        return KeyedOpenMontColsJob(self, cols)
+
+    def verify_open_mont_dev(self, *args, misses=None, stream=None):
+        """Montgomery limbs in device memory (dsv_verify_keyed_open_mont_dev): CUDA tensors (u [n, 32], R [n, 96]
+        [, Rp], PK [n, 96][, PKp | Gen], m [n, 32], ok, workspace), every input 16-byte aligned; verify_*_mont_dev's
+        verdicts into ok, enqueued on `stream` (default: torch's current stream of the batch's device) as one chain
+        of launches; does not synchronise and may be captured.  workspace: >=
+        keyed_open_mont_workspace_bytes(scheme, n) bytes; misses as for lookup_dev."""
+        if len(args) < 2:
+            raise ValueError("verify_open_mont_dev takes the inputs, then ok and workspace")
+        ok, workspace = args[-2], args[-1]
+        u, pts, keys, m = self._by_value(args[:-2], "verify_open_mont_dev")
+        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
+        widths = [32] + [96] * (len(pts) + len(keys)) + [32]
+        n, dev = _rows(*zip([u] + pts + keys + [m], widths, names))
+        okp = _bytes_out(ok, n, dev, "ok")
+        wsp = _bytes_out(workspace, keyed_open_mont_workspace_bytes(self.scheme, n), dev, "workspace")
+        null = ctypes.c_void_p(0)
+        ptr = [self._rec_ptr(t, w, nm) for t, w, nm in zip([u] + pts + keys + [m], widths, names)]
+        ns = len(pts)
+        _lib.check(_lib.load().dsv_verify_keyed_open_mont_dev(
+            self._handle(), ptr[0], ptr[1], ptr[2] if ns == 2 else null, ptr[1 + ns],
+            ptr[2 + ns] if len(keys) == 2 else null, ptr[-1], ctypes.c_size_t(n), okp, wsp,
+            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
