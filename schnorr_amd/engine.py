@@ -20,7 +20,7 @@ def init(device=0):
     if device in _initialised:
         return
     L = _lib.load()
-    _lib.check(L.dsv_init(ctypes.c_int(device)))
+    _lib.check(L.dsv_init(device))
     _initialised.add(device)
 
 
@@ -37,7 +37,7 @@ def init_visible():
 
 def set_device(device):
     """Device of this thread's host-buffer entry points (default: the first one initialised)."""
-    _lib.check(_lib.load().dsv_set_device(ctypes.c_int(device)))
+    _lib.check(_lib.load().dsv_set_device(device))
 
 
 def initialized_devices():
@@ -52,7 +52,7 @@ def device_numa(device=0):
     cpus = (ctypes.c_int * 1024)()
     node = ctypes.c_int(-1)
     bdf = ctypes.create_string_buffer(32)
-    n = _lib.load().dsv_device_numa(ctypes.c_int(device), ctypes.byref(node), cpus, 1024, bdf)
+    n = _lib.load().dsv_device_numa(device, ctypes.byref(node), cpus, 1024, bdf)
     if n < 0:
         _lib.check(n)
     return {"bdf": bdf.value.decode(), "node": node.value, "cpus": [cpus[i] for i in range(min(n, 1024))]}
@@ -76,13 +76,13 @@ def shutdown(device=None):
         _lib.check(_lib.load().dsv_shutdown())
         _initialised.clear()
     else:
-        _lib.check(_lib.load().dsv_shutdown_device(ctypes.c_int(device)))
+        _lib.check(_lib.load().dsv_shutdown_device(device))
         _initialised.discard(device)
 
 
 def set_host_threads(n):
     """Copy threads of the host entry points (0 = default); returns the value in force."""
-    return int(_lib.load().dsv_set_host_threads(ctypes.c_int(n)))
+    return int(_lib.load().dsv_set_host_threads(n))
 
 
 def version():
@@ -99,7 +99,7 @@ def _arr(a, width):
 
 
 def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
+    return a.ctypes.data
 
 
 def _same_n(*arrs):
@@ -116,6 +116,7 @@ _SCHEMES = {"single": (("u", "R", "PK", "m"), (64, 32)),
             "double": (("u", "R", "Rp", "PK", "PKp", "m"), (96, 64)),
             "vargen": (("u", "R", "PK", "Gen", "m"), (64, 64))}
 _SCHEME_CODE = {"single": 0, "double": 1, "vargen": 2}  # the C ABI's scheme argument
+_KEY_POINTS = {"single": 1, "double": 2, "vargen": 2}  # points of a key: PK / PK, PK' / PK, Gen
 _POINT_WIDTH = {"": 64, "_ext": 96, "_mont": 96}
 
 
@@ -140,7 +141,7 @@ def _host(scheme, form, arrays, multi=False, rlc=False):
     name = "dsv_verify_%s%s%s" % (scheme, form, "_multi" if multi else "_rlc" if rlc else "")
     accepted = ctypes.c_int(0)
     tail = [ctypes.byref(accepted)] if rlc else []
-    _lib.check(getattr(_lib.load(), name)(*([_p(a) for a in arrs] + [ctypes.c_size_t(n), _p(ok)] + tail)))
+    _lib.check(getattr(_lib.load(), name)(*([_p(a) for a in arrs] + [n, _p(ok)] + tail)))
     return (ok, bool(accepted.value)) if rlc else ok
 
 
@@ -175,7 +176,7 @@ def to_hash_inputs(uvz):
     n = uvz.shape[0]
     out = np.zeros((n, 64), dtype=np.uint8)
     ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_to_hash_inputs(_p(uvz), ctypes.c_size_t(n), _p(out), _p(ok)))
+    _lib.check(_lib.load().dsv_to_hash_inputs(_p(uvz), n, _p(out), _p(ok)))
     return out, ok
 
 
@@ -230,7 +231,7 @@ def verify_mont_cols(scheme, cols):
     `records["R"][:, :96]`): only the last axis has to be contiguous, the row stride is passed on."""
     n, arr = _columns(scheme, cols)
     ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols" % scheme)(arr, ctypes.c_size_t(n), _p(ok)))
+    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols" % scheme)(arr, n, _p(ok)))
     return ok
 
 
@@ -239,7 +240,7 @@ def verify_mont_cols_rlc(scheme, cols):
     n, arr = _columns(scheme, cols)
     ok = np.zeros(n, dtype=np.uint8)
     accepted = ctypes.c_int(0)
-    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols_rlc" % scheme)(arr, ctypes.c_size_t(n), _p(ok),
+    _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols_rlc" % scheme)(arr, n, _p(ok),
                                                                           ctypes.byref(accepted)))
     return ok, bool(accepted.value)
 
@@ -254,7 +255,7 @@ class MontColsJob:
         self._ok = np.zeros(n, dtype=np.uint8)
         self._job = ctypes.c_void_p()
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_mont_cols_submit" % scheme)(
-            arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
+            arr, n, _p(self._ok), ctypes.byref(self._job)))
 
     def __del__(self):
         # a job dropped unwaited still reads the columns and writes the verdicts: wait before they go
@@ -289,7 +290,7 @@ def challenge_single(R, m):
     R, m = _arr(R, 64), _arr(m, 32)
     n = _same_n(R, m)
     c = np.zeros((n, 32), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_challenge_single(_p(R), _p(m), ctypes.c_size_t(n), _p(c)))
+    _lib.check(_lib.load().dsv_challenge_single(_p(R), _p(m), n, _p(c)))
     return c
 
 
@@ -297,7 +298,7 @@ def challenge_double(R, Rp, m):
     R, Rp, m = _arr(R, 64), _arr(Rp, 64), _arr(m, 32)
     n = _same_n(R, Rp, m)
     c = np.zeros((n, 32), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_challenge_double(_p(R), _p(Rp), _p(m), ctypes.c_size_t(n), _p(c)))
+    _lib.check(_lib.load().dsv_challenge_double(_p(R), _p(Rp), _p(m), n, _p(c)))
     return c
 
 
@@ -306,7 +307,7 @@ def sign_single(sk, m, r):
     n = _same_n(sk, m, r)
     u = np.zeros((n, 32), dtype=np.uint8)
     R = np.zeros((n, 64), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_sign_single(_p(sk), _p(m), _p(r), ctypes.c_size_t(n), _p(u), _p(R)))
+    _lib.check(_lib.load().dsv_sign_single(_p(sk), _p(m), _p(r), n, _p(u), _p(R)))
     return u, R
 
 
@@ -316,8 +317,7 @@ def sign_double(sk, m, r):
     u = np.zeros((n, 32), dtype=np.uint8)
     R = np.zeros((n, 64), dtype=np.uint8)
     Rp = np.zeros((n, 64), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_sign_double(_p(sk), _p(m), _p(r), ctypes.c_size_t(n), _p(u), _p(R),
-                                           _p(Rp)))
+    _lib.check(_lib.load().dsv_sign_double(_p(sk), _p(m), _p(r), n, _p(u), _p(R), _p(Rp)))
     return u, R, Rp
 
 
@@ -326,8 +326,7 @@ def sign_vargen(sk, Gen, m, r):
     n = _same_n(sk, Gen, m, r)
     u = np.zeros((n, 32), dtype=np.uint8)
     R = np.zeros((n, 64), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_sign_vargen(_p(sk), _p(Gen), _p(m), _p(r), ctypes.c_size_t(n),
-                                           _p(u), _p(R)))
+    _lib.check(_lib.load().dsv_sign_vargen(_p(sk), _p(Gen), _p(m), _p(r), n, _p(u), _p(R)))
     return u, R
 
 
@@ -339,9 +338,7 @@ def public_keys(sk, which=0, Gen=None):
     if Gen is not None:
         g = _arr(Gen, 64)
         _same_n(sk, g)
-    _lib.check(_lib.load().dsv_public_keys(_p(sk), ctypes.c_int(which),
-                                           _p(g) if g is not None else ctypes.c_void_p(0),
-                                           ctypes.c_size_t(n), _p(PK)))
+    _lib.check(_lib.load().dsv_public_keys(_p(sk), which, _p(g) if g is not None else None, n, _p(PK)))
     return PK
 
 
@@ -351,7 +348,7 @@ def decompress_points(comp):
     n = comp.shape[0]
     out = np.zeros((n, 64), dtype=np.uint8)
     ok = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_decompress_points(_p(comp), ctypes.c_size_t(n), _p(out), _p(ok)))
+    _lib.check(_lib.load().dsv_decompress_points(_p(comp), n, _p(out), _p(ok)))
     return out, ok
 
 
@@ -359,7 +356,7 @@ def compress_points(uv):
     """JubJubAffine::to_bytes: v with bit 255 = lowest bit of u (pure byte shuffling)."""
     uv = _arr(uv, 64)
     out = np.zeros((uv.shape[0], 32), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_compress_points(_p(uv), ctypes.c_size_t(uv.shape[0]), _p(out)))
+    _lib.check(_lib.load().dsv_compress_points(_p(uv), uv.shape[0], _p(out)))
     return out
 
 
@@ -386,22 +383,19 @@ def stdrng_sign_inputs(seed, n, first_item=0):
     sk = np.zeros((n, 32), dtype=np.uint8)
     m = np.zeros((n, 32), dtype=np.uint8)
     r = np.zeros((n, 32), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_stdrng_sign_inputs(ctypes.c_uint64(seed), ctypes.c_size_t(first_item),
-                                                  ctypes.c_size_t(n), _p(sk), _p(m), _p(r)))
+    _lib.check(_lib.load().dsv_stdrng_sign_inputs(seed, first_item, n, _p(sk), _p(m), _p(r)))
     return sk, m, r
 
 
 def stdrng_sign_inputs_dev(seed, sk, m, r, first_item=0, stream=None):
     n, dev = _rows((sk, 32, "sk"), (m, 32, "m"), (r, 32, "r"))
     _lib.check(_lib.load().dsv_stdrng_sign_inputs_dev(
-        ctypes.c_uint64(seed), ctypes.c_size_t(first_item), ctypes.c_size_t(n), _tp(sk, 32),
-        _tp(m, 32), _tp(r, 32), _stream_ptr(stream, dev)))
+        seed, first_item, n, _tp(sk, 32), _tp(m, 32), _tp(r, 32), _stream_ptr(stream, dev)))
 
 
 def debug_table_entry(which, window, digit):
     out = np.zeros(96, dtype=np.uint8)
-    _lib.check(_lib.load().dsv_debug_table_entry(ctypes.c_int(which), ctypes.c_int(window),
-                                                 ctypes.c_int(digit), _p(out)))
+    _lib.check(_lib.load().dsv_debug_table_entry(which, window, digit, _p(out)))
     return out
 
 
@@ -414,7 +408,7 @@ def debug_lattice3(u, c):
     u, c = _arr(u, 32), _arr(c, 32)
     n = _same_n(u, c)
     out = np.zeros((n, 128), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_debug_lattice3(_p(u), _p(c), ctypes.c_size_t(n), _p(out)))
+    _lib.check(_lib.load().dsv_debug_lattice3(_p(u), _p(c), n, _p(out)))
     res = []
     for row in out:
         v = [int.from_bytes(row[32 * k:32 * k + 32].tobytes(), "little") for k in range(3)]
@@ -427,7 +421,7 @@ def debug_half_scalars(c):
     c = _arr(c, 32)
     n = c.shape[0]
     out = np.zeros((n, 96), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_debug_half_scalars(_p(c), ctypes.c_size_t(n), _p(out)))
+    _lib.check(_lib.load().dsv_debug_half_scalars(_p(c), n, _p(out)))
     res = []
     for row in out:
         a, b = (int.from_bytes(row[32 * k:32 * k + 32].tobytes(), "little") for k in range(2))
@@ -439,7 +433,7 @@ def debug_fq_mul(a, b):
     a, b = _arr(a, 32), _arr(b, 32)
     n = _same_n(a, b)
     out = np.zeros((n, 32), dtype=np.uint8)
-    _lib.check(_lib.load().dsv_debug_fq_mul(_p(a), _p(b), ctypes.c_size_t(n), _p(out)))
+    _lib.check(_lib.load().dsv_debug_fq_mul(_p(a), _p(b), n, _p(out)))
     return out
 
 
@@ -480,38 +474,38 @@ def _bytes_out(t, need, dev, name):
                          % (name, need, t.dtype, t.numel()))
     if t.device != dev:
         raise ValueError("%s is on %s, the batch on %s" % (name, t.device, dev))
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def _tp(t, width):
-    return ctypes.c_void_p(_t(t, width).data_ptr())
+    return _t(t, width).data_ptr()
 
 
 def workspace_bytes(n):
-    return int(_lib.load().dsv_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_workspace_bytes(n))
 
 
 def mixed_workspace_bytes(n):
-    return int(_lib.load().dsv_mixed_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_mixed_workspace_bytes(n))
 
 
 def split_scratch_bytes(n):
-    return int(_lib.load().dsv_split_scratch_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_split_scratch_bytes(n))
 
 
 def ext_workspace_bytes(n):
-    return int(_lib.load().dsv_ext_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_ext_workspace_bytes(n))
 
 
 def wire_workspace_bytes(n):
-    return int(_lib.load().dsv_wire_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_wire_workspace_bytes(n))
 
 
 def _stream_ptr(stream, dev=None):
     import torch
 
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    return ctypes.c_void_p(s.cuda_stream)
+    return s.cuda_stream
 
 
 def _dev(scheme, form, arrays, ok, workspace, stream, rlc=None):
@@ -523,14 +517,14 @@ def _dev(scheme, form, arrays, ok, workspace, stream, rlc=None):
         window_bits, accepted_out = rlc
         arg, box = _accepted_arg(accepted_out, dev)
         ws_need = (wire_rlc_workspace_bytes if form == "_wire" else rlc_workspace_bytes)(n, window_bits)
-        tail, name = [ctypes.c_int(window_bits), arg], "dsv_verify_%s%s_rlc_dev" % (scheme, form)
+        tail, name = [window_bits, arg], "dsv_verify_%s%s_rlc_dev" % (scheme, form)
     else:
         box = None
         ws_need = {"": workspace_bytes, "_ext": ext_workspace_bytes, "_mont": mont_workspace_bytes,
                    "_wire": wire_workspace_bytes}[form](n)
         tail, name = [], "dsv_verify_%s%s_dev" % (scheme, form)
     _lib.check(getattr(_lib.load(), name)(
-        *[_tp(t, w) for t, w in zip(arrays, widths)], ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
+        *[_tp(t, w) for t, w in zip(arrays, widths)], n, _bytes_out(ok, n, dev, "ok"),
         _bytes_out(workspace, ws_need, dev, "workspace"), _stream_ptr(stream, dev), *tail))
     return bool(box.value) if box is not None else None
 
@@ -542,7 +536,7 @@ def verify_single_dev(u, R, PK, m, ok, workspace, stream=None):
 
 
 def rlc_workspace_bytes(n, window_bits=0):
-    b = int(_lib.load().dsv_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_int(window_bits)))
+    b = int(_lib.load().dsv_rlc_workspace_bytes(n, window_bits))
     if b == 0:
         raise ValueError("window_bits must be 0 or one of 4, 6, 8, 12, 14, 16")
     return b
@@ -557,13 +551,13 @@ _PLAN_FIELDS = ("c", "half", "wpk", "wr", "windows", "nseg", "nseg2", "fine_bits
 def _plan(fn, scheme, *args):
     """fn(scheme code, *args, out[24]) -> dict of _PLAN_FIELDS"""
     out = (ctypes.c_uint64 * 24)()
-    _lib.check(fn(ctypes.c_int(_SCHEME_CODE[scheme]), *args, out))
+    _lib.check(fn(_SCHEME_CODE[scheme], *args, out))
     return dict(zip(_PLAN_FIELDS, [int(x) for x in out]))
 
 
 def _history(fn, device, set_to):
     """a dsv_debug_*history* counter: its value before the call; set_to >= 0 overrides it"""
-    r = fn(ctypes.c_int(device), ctypes.c_int(set_to))
+    r = fn(device, set_to)
     if r < 0:
         _lib.check(r)
     return r
@@ -571,8 +565,7 @@ def _history(fn, device, set_to):
 
 def rlc_plan_info(scheme, n, window_bits=0, groups=1):
     """dsv_rlc_plan_info as a dict (no GPU needed)"""
-    return _plan(_lib.load().dsv_rlc_plan_info, scheme, ctypes.c_size_t(n), ctypes.c_int(window_bits),
-                 ctypes.c_int(groups))
+    return _plan(_lib.load().dsv_rlc_plan_info, scheme, n, window_bits, groups)
 
 
 def rlc_history(device=0, set_to=-1):
@@ -588,7 +581,7 @@ def rlc_history_long(device=0, set_to=-1):
 
 def rlc_subgroups(groups=-1):
     """dsv_debug_rlc_subgroups: force `groups` sub-groups per group (0: automatic); returns the previous setting"""
-    return int(_lib.load().dsv_debug_rlc_subgroups(ctypes.c_int(groups)))
+    return int(_lib.load().dsv_debug_rlc_subgroups(groups))
 
 
 def _accepted_arg(accepted_out, dev):
@@ -603,7 +596,7 @@ def _accepted_arg(accepted_out, dev):
     t = accepted_out
     if t.dtype != torch.int32 or t.numel() < 1 or not (t.is_cuda and t.device == dev or (not t.is_cuda and t.is_pinned())):
         raise ValueError("accepted_out: need an int32 tensor on the batch's device or in pinned host memory")
-    return ctypes.c_void_p(t.data_ptr()), None
+    return t.data_ptr(), None
 
 
 def verify_single_rlc_dev(u, R, PK, m, ok, workspace, stream=None, window_bits=0, accepted_out=None):
@@ -644,7 +637,7 @@ def verify_vargen_ext_dev(u, R_uvz, PK_uvz, Gen_uvz, m, ok, workspace, stream=No
 
 
 def mont_workspace_bytes(n):
-    return int(_lib.load().dsv_mont_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_mont_workspace_bytes(n))
 
 
 def verify_single_mont_dev(u, R_uvz, PK_uvz, m, ok, workspace, stream=None):
@@ -674,7 +667,7 @@ def verify_vargen_wire_dev(sig64, pk64, m, ok, workspace, stream=None):
 
 
 def wire_rlc_workspace_bytes(n, window_bits=0):
-    b = int(_lib.load().dsv_wire_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_int(window_bits)))
+    b = int(_lib.load().dsv_wire_rlc_workspace_bytes(n, window_bits))
     if b == 0:
         raise ValueError("window_bits must be 0 or one of 4, 6, 8, 12, 14, 16")
     return b
@@ -690,7 +683,7 @@ def verify_core_dev(u, c, valid, PK, R, ok, workspace, which=0, accumulate=False
     n, dev = _rows((u, 32, "u"), (c, 32, "c"), (PK, 64, "PK"), (R, 64, "R"))
     _lib.check(_lib.load().dsv_verify_core_dev(
         _tp(u, 32), _tp(c, 32), _bytes_out(valid, n, dev, "valid"), _tp(PK, 64), _tp(R, 64),
-        ctypes.c_int(which), ctypes.c_int(1 if accumulate else 0), ctypes.c_size_t(n),
+        which, 1 if accumulate else 0, n,
         _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, workspace_bytes(n), dev, "workspace"),
         _stream_ptr(stream, dev)))
 
@@ -700,7 +693,7 @@ def verify_core_double_dev(u, c, valid, PK, R, PKp, Rp, ok, workspace, stream=No
                    (Rp, 64, "Rp"))
     _lib.check(_lib.load().dsv_verify_core_double_dev(
         _tp(u, 32), _tp(c, 32), _bytes_out(valid, n, dev, "valid"), _tp(PK, 64), _tp(R, 64),
-        _tp(PKp, 64), _tp(Rp, 64), ctypes.c_size_t(n), _bytes_out(ok, n, dev, "ok"),
+        _tp(PKp, 64), _tp(Rp, 64), n, _bytes_out(ok, n, dev, "ok"),
         _bytes_out(workspace, workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)))
 
 
@@ -710,13 +703,13 @@ def verify_mixed_dev(kinds, u, R, Rp, PK, PKp, m, n_double, ok, workspace, strea
                    (m, 32, "m"))
     _lib.check(_lib.load().dsv_verify_mixed_dev(
         _bytes_out(kinds, n, dev, "kinds"), _tp(u, 32), _tp(R, 64), _tp(Rp, 64), _tp(PK, 64),
-        _tp(PKp, 64), _tp(m, 32), ctypes.c_size_t(n), ctypes.c_size_t(int(n_double)),
+        _tp(PKp, 64), _tp(m, 32), n, int(n_double),
         _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, mixed_workspace_bytes(n), dev, "workspace"),
         _stream_ptr(stream, dev)))
 
 
 def mixed_rlc_workspace_bytes(n):
-    return int(_lib.load().dsv_mixed_rlc_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_mixed_rlc_workspace_bytes(n))
 
 
 def verify_mixed_rlc_dev(kinds, u, R, Rp, PK, PKp, m, n_double, ok, workspace, stream=None):
@@ -728,7 +721,7 @@ def verify_mixed_rlc_dev(kinds, u, R, Rp, PK, PKp, m, n_double, ok, workspace, s
     accepted = ctypes.c_int(0)
     _lib.check(_lib.load().dsv_verify_mixed_rlc_dev(
         _bytes_out(kinds, n, dev, "kinds"), _tp(u, 32), _tp(R, 64), _tp(Rp, 64), _tp(PK, 64),
-        _tp(PKp, 64), _tp(m, 32), ctypes.c_size_t(n), ctypes.c_size_t(int(n_double)),
+        _tp(PKp, 64), _tp(m, 32), n, int(n_double),
         _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, mixed_rlc_workspace_bytes(n), dev, "workspace"),
         _stream_ptr(stream, dev), ctypes.byref(accepted)))
     return bool(accepted.value)
@@ -740,7 +733,15 @@ def _idx(t, need, dev, name):
     _t(t, None, name)
     if t.dtype not in (torch.int32, torch.uint32) or t.numel() < need or t.device != dev:
         raise ValueError("%s: need a 32-bit index tensor of >= %d elements on %s" % (name, need, dev))
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+def _col32(t, n, dev, name):
+    """an index or output column of a _dev form: a 32-bit tensor of shape [n] on `dev` -> its address"""
+    p = _idx(t, n, dev, name)
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError("%s: expected [n] = [%d], got %r" % (name, n, tuple(t.shape)))
+    return p
 
 
 def split_kinds_dev(kinds, idx_single, idx_double, scratch, stream=None):
@@ -749,9 +750,9 @@ def split_kinds_dev(kinds, idx_single, idx_double, scratch, stream=None):
     n = kinds.numel()
     dev = kinds.device
     _lib.check(_lib.load().dsv_split_kinds_dev(
-        _bytes_out(kinds, n, dev, "kinds"), ctypes.c_size_t(n),
-        _idx(idx_single, 0, dev, "idx_single"), ctypes.c_size_t(idx_single.numel()),
-        _idx(idx_double, 0, dev, "idx_double"), ctypes.c_size_t(idx_double.numel()),
+        _bytes_out(kinds, n, dev, "kinds"), n,
+        _idx(idx_single, 0, dev, "idx_single"), idx_single.numel(),
+        _idx(idx_double, 0, dev, "idx_double"), idx_double.numel(),
         _bytes_out(scratch, split_scratch_bytes(n), dev, "scratch"), _stream_ptr(stream, dev)))
 
 
@@ -766,11 +767,11 @@ def _limit_ptr(limit, dev):
     import torch
 
     if limit is None:
-        return ctypes.c_void_p(0)
+        return None
     if not (isinstance(limit, torch.Tensor) and limit.is_cuda and limit.device == dev
             and limit.dtype in (torch.int32, torch.uint32) and limit.numel() >= 1):
         raise ValueError("limit: need a 32-bit CUDA tensor of one element on %s" % dev)
-    return ctypes.c_void_p(limit.data_ptr())
+    return limit.data_ptr()
 
 
 def gather_rows_dev(src, idx, count, dst, limit=None, stream=None):
@@ -783,9 +784,8 @@ def gather_rows_dev(src, idx, count, dst, limit=None, stream=None):
     if dst.shape[0] < count or dst.device != dev:
         raise ValueError("dst too small or on another device")
     _lib.check(_lib.load().dsv_gather_rows_dev(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_size_t(src.shape[0]), ctypes.c_size_t(src.shape[1]),
-        _idx(idx, count, dev, "idx"), ctypes.c_size_t(count), _limit_ptr(limit, dev),
-        ctypes.c_void_p(dst.data_ptr()), _stream_ptr(stream, dev)))
+        src.data_ptr(), src.shape[0], src.shape[1], _idx(idx, count, dev, "idx"), count, _limit_ptr(limit, dev),
+        dst.data_ptr(), _stream_ptr(stream, dev)))
 
 
 def scatter_verdicts_dev(src, idx, count, dst, limit=None, stream=None):
@@ -793,24 +793,24 @@ def scatter_verdicts_dev(src, idx, count, dst, limit=None, stream=None):
     index >= dst.numel() is skipped."""
     dev = dst.device
     _lib.check(_lib.load().dsv_scatter_verdicts_dev(
-        _bytes_out(src, count, dev, "src"), _idx(idx, count, dev, "idx"), ctypes.c_size_t(count),
-        _limit_ptr(limit, dev), _bytes_out(dst, 0, dev, "dst"), ctypes.c_size_t(dst.numel()),
+        _bytes_out(src, count, dev, "src"), _idx(idx, count, dev, "idx"), count,
+        _limit_ptr(limit, dev), _bytes_out(dst, 0, dev, "dst"), dst.numel(),
         _stream_ptr(stream, dev)))
 
 
 def challenge_double_dev(R, Rp, m, c, valid=None, stream=None):
     n, dev = _rows((R, 64, "R"), (Rp, 64, "Rp"), (m, 32, "m"), (c, 32, "c"))
     _lib.check(_lib.load().dsv_challenge_double_dev(
-        _tp(R, 64), _tp(Rp, 64), _tp(m, 32), ctypes.c_size_t(n), _tp(c, 32),
-        _bytes_out(valid, n, dev, "valid") if valid is not None else ctypes.c_void_p(0),
+        _tp(R, 64), _tp(Rp, 64), _tp(m, 32), n, _tp(c, 32),
+        _bytes_out(valid, n, dev, "valid") if valid is not None else None,
         _stream_ptr(stream, dev)))
 
 
 def challenge_single_dev(R, m, c, valid=None, stream=None):
     n, dev = _rows((R, 64, "R"), (m, 32, "m"), (c, 32, "c"))
     _lib.check(_lib.load().dsv_challenge_single_dev(
-        _tp(R, 64), _tp(m, 32), ctypes.c_size_t(n), _tp(c, 32),
-        _bytes_out(valid, n, dev, "valid") if valid is not None else ctypes.c_void_p(0),
+        _tp(R, 64), _tp(m, 32), n, _tp(c, 32),
+        _bytes_out(valid, n, dev, "valid") if valid is not None else None,
         _stream_ptr(stream, dev)))
 
 
@@ -822,35 +822,34 @@ def decompress_points_dev(comp, out_uv, ok, in_stride=32, accumulate=False, stre
     if comp.numel() * comp.element_size() < (n - 1) * in_stride + 32 or comp.device != dev:
         raise ValueError("comp holds fewer than n records of stride %d (or is on another device)" % in_stride)
     _lib.check(_lib.load().dsv_decompress_points_dev(
-        ctypes.c_void_p(comp.data_ptr()), ctypes.c_size_t(in_stride), ctypes.c_size_t(n),
-        _tp(out_uv, 64), _bytes_out(ok, n, dev, "ok"), ctypes.c_int(1 if accumulate else 0),
+        comp.data_ptr(), in_stride, n, _tp(out_uv, 64), _bytes_out(ok, n, dev, "ok"), 1 if accumulate else 0,
         _stream_ptr(stream, dev)))
 
 
 def sign_single_dev(sk, m, r, u, R, stream=None):
     n, dev = _rows((sk, 32, "sk"), (m, 32, "m"), (r, 32, "r"), (u, 32, "u"), (R, 64, "R"))
     _lib.check(_lib.load().dsv_sign_single_dev(
-        _tp(sk, 32), _tp(m, 32), _tp(r, 32), ctypes.c_size_t(n), _tp(u, 32), _tp(R, 64),
+        _tp(sk, 32), _tp(m, 32), _tp(r, 32), n, _tp(u, 32), _tp(R, 64),
         _stream_ptr(stream, dev)))
 
 
 def sign_double_dev(sk, m, r, u, R, Rp, stream=None):
     n, dev = _rows((sk, 32, "sk"), (m, 32, "m"), (r, 32, "r"), (u, 32, "u"), (R, 64, "R"), (Rp, 64, "Rp"))
     _lib.check(_lib.load().dsv_sign_double_dev(
-        _tp(sk, 32), _tp(m, 32), _tp(r, 32), ctypes.c_size_t(n), _tp(u, 32), _tp(R, 64),
+        _tp(sk, 32), _tp(m, 32), _tp(r, 32), n, _tp(u, 32), _tp(R, 64),
         _tp(Rp, 64), _stream_ptr(stream, dev)))
 
 
 def public_keys_dev(sk, which, PK, stream=None):
     n, dev = _rows((sk, 32, "sk"), (PK, 64, "PK"))
     _lib.check(_lib.load().dsv_public_keys_dev(
-        _tp(sk, 32), ctypes.c_int(which), ctypes.c_size_t(n), _tp(PK, 64), _stream_ptr(stream, dev)))
+        _tp(sk, 32), which, n, _tp(PK, 64), _stream_ptr(stream, dev)))
 
 
 def public_keys_vargen_dev(sk, Gen, PK, workspace, stream=None):
     n, dev = _rows((sk, 32, "sk"), (Gen, 64, "Gen"), (PK, 64, "PK"))
     _lib.check(_lib.load().dsv_public_keys_vargen_dev(
-        _tp(sk, 32), _tp(Gen, 64), ctypes.c_size_t(n), _tp(PK, 64),
+        _tp(sk, 32), _tp(Gen, 64), n, _tp(PK, 64),
         _bytes_out(workspace, workspace_bytes(n), dev, "workspace"), _stream_ptr(stream, dev)))
 
 
@@ -858,7 +857,7 @@ def sign_vargen_dev(sk, Gen, m, r, u, R, workspace, stream=None):
     n, dev = _rows((sk, 32, "sk"), (Gen, 64, "Gen"), (m, 32, "m"), (r, 32, "r"), (u, 32, "u"),
                    (R, 64, "R"))
     _lib.check(_lib.load().dsv_sign_vargen_dev(
-        _tp(sk, 32), _tp(Gen, 64), _tp(m, 32), _tp(r, 32), ctypes.c_size_t(n), _tp(u, 32),
+        _tp(sk, 32), _tp(Gen, 64), _tp(m, 32), _tp(r, 32), n, _tp(u, 32),
         _tp(R, 64), _bytes_out(workspace, workspace_bytes(n), dev, "workspace"),
         _stream_ptr(stream, dev)))
 
@@ -866,85 +865,83 @@ def sign_vargen_dev(sk, Gen, m, r, u, R, workspace, stream=None):
 def stdrng_vargen_inputs_dev(seed, sk, g, m, r, first_item=0, stream=None):
     n, dev = _rows((sk, 32, "sk"), (g, 32, "g"), (m, 32, "m"), (r, 32, "r"))
     _lib.check(_lib.load().dsv_stdrng_vargen_inputs_dev(
-        ctypes.c_uint64(seed), ctypes.c_size_t(first_item), ctypes.c_size_t(n), _tp(sk, 32),
-        _tp(g, 32), _tp(m, 32), _tp(r, 32), _stream_ptr(stream, dev)))
+        seed, first_item, n, _tp(sk, 32), _tp(g, 32), _tp(m, 32), _tp(r, 32), _stream_ptr(stream, dev)))
 
 
 # ------------------------------------------------------------------ registered key sets
+def _code(scheme):
+    """the C ABI's scheme argument"""
+    if scheme not in _SCHEME_CODE:
+        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    return _SCHEME_CODE[scheme]
+
+
+def _slots(ptrs, slots=2):
+    """the pointers of a scheme's columns in an argument list with `slots` places for them: the rest are null"""
+    ptrs = list(ptrs)
+    return ptrs + [None] * (slots - len(ptrs))
+
+
 def keyset_bytes(scheme, k):
     """dsv_keyset_bytes: device bytes of a key set of k keys (no GPU needed)"""
-    return int(_lib.load().dsv_keyset_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
+    return int(_lib.load().dsv_keyset_bytes(_SCHEME_CODE[scheme], k))
 
 
 def keyed_workspace_bytes(n):
-    return int(_lib.load().dsv_keyed_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_workspace_bytes(n))
 
 
 def keyed_wire_workspace_bytes(scheme, n):
     """dsv_keyed_wire_workspace_bytes: device bytes of KeySet.verify_wire_dev's workspace (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyed_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_wire_workspace_bytes(_code(scheme), n))
 
 
 def keyed_mont_workspace_bytes(scheme, n):
     """dsv_keyed_mont_workspace_bytes: device bytes of KeySet.verify_mont_dev's workspace (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyed_mont_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_mont_workspace_bytes(_code(scheme), n))
 
 
 def keyset_index_bytes(scheme, k):
     """dsv_keyset_index_bytes: device bytes of the index over a key set's own keys (KeySet.lookup; no GPU needed);
     not part of keyset_bytes"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyset_index_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
+    return int(_lib.load().dsv_keyset_index_bytes(_code(scheme), k))
 
 
 def keyed_lookup_workspace_bytes(n):
     """dsv_keyed_lookup_workspace_bytes: device bytes of KeySet.verify_lookup_dev's workspace (no GPU needed)"""
-    return int(_lib.load().dsv_keyed_lookup_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_lookup_workspace_bytes(n))
 
 
 def keyed_open_workspace_bytes(n):
     """dsv_keyed_open_workspace_bytes: device bytes of KeySet.verify_open_dev's workspace (no GPU needed)"""
-    return int(_lib.load().dsv_keyed_open_workspace_bytes(ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_open_workspace_bytes(n))
 
 
 def keyset_wire_index_bytes(scheme, k):
     """dsv_keyset_wire_index_bytes: device bytes of the index over the compressed records of a key set's own keys
     (KeySet.lookup_wire; no GPU needed); not part of keyset_bytes or keyset_index_bytes"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyset_wire_index_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k)))
+    return int(_lib.load().dsv_keyset_wire_index_bytes(_code(scheme), k))
 
 
 def keyed_open_wire_workspace_bytes(scheme, n):
     """dsv_keyed_open_wire_workspace_bytes: device bytes of KeySet.verify_open_wire_dev's workspace (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyed_open_wire_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_open_wire_workspace_bytes(_code(scheme), n))
 
 
 def keyed_open_mont_workspace_bytes(scheme, n):
     """dsv_keyed_open_mont_workspace_bytes: device bytes of KeySet.verify_open_mont_dev's workspace (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
-    return int(_lib.load().dsv_keyed_open_mont_workspace_bytes(ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(n)))
+    return int(_lib.load().dsv_keyed_open_mont_workspace_bytes(_code(scheme), n))
 
 
 def keyset_wire_home_slot(scheme, capacity, record):
     """dsv_debug_keyset_wire_home_slot: where the probe for a key record (32 bytes per key point) starts in the
     wire index of a set of `capacity` keys (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    code = _code(scheme)
     rec = _arr(record, _SCHEMES[scheme][1][1])
     if rec.shape[0] != 1:
         raise ValueError("one key record at a time")
     slot = ctypes.c_uint64()
-    _lib.check(_lib.load().dsv_debug_keyset_wire_home_slot(
-        ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(capacity), _p(rec), ctypes.byref(slot)))
+    _lib.check(_lib.load().dsv_debug_keyset_wire_home_slot(code, capacity, _p(rec), ctypes.byref(slot)))
     return int(slot.value)
 
 
@@ -954,18 +951,15 @@ KEY_NONE = 0xFFFFFFFF  # DSV_KEY_NONE: the index of a key that is not in the set
 def keyset_home_slot(scheme, k, key_a, key_b=None):
     """dsv_debug_keyset_home_slot: where the probe for a key (64 bytes per point) starts in the index of a set of
     k keys (no GPU needed)"""
-    if scheme not in _SCHEME_CODE:
-        raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+    code = _code(scheme)
     if k < 1:
         raise ValueError("k must be at least 1")
     if (key_b is None) != (scheme == "single"):
         raise ValueError("scheme %s takes %s" % (scheme, "key_a only" if scheme == "single" else "key_a and key_b"))
-    a = _arr(key_a, 64)
-    b = _arr(key_b, 64) if key_b is not None else None
-    if a.shape[0] != 1 or (b is not None and b.shape[0] != 1):
+    keys = [_arr(key, 64) for key in (key_a, key_b) if key is not None]
+    if any(key.shape[0] != 1 for key in keys):
         raise ValueError("one key at a time")
-    return int(_lib.load().dsv_debug_keyset_home_slot(
-        ctypes.c_int(_SCHEME_CODE[scheme]), ctypes.c_size_t(k), _p(a), _p(b) if b is not None else ctypes.c_void_p(0)))
+    return int(_lib.load().dsv_debug_keyset_home_slot(code, k, *_slots(_p(key) for key in keys)))
 
 
 def keyset_slots(ks, form):
@@ -974,11 +968,9 @@ def keyset_slots(ks, form):
     form = {"affine": 0, "record": 1}.get(form, form)
     L = _lib.load()
     slots = ctypes.c_size_t()
-    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), ctypes.c_int(form), ctypes.c_void_p(0), ctypes.c_size_t(0),
-                                        ctypes.byref(slots)))
+    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), form, None, 0, ctypes.byref(slots)))
     out = np.zeros(slots.value, dtype=np.uint32)
-    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), ctypes.c_int(form), _p(out), ctypes.c_size_t(out.shape[0]),
-                                        ctypes.byref(slots)))
+    _lib.check(L.dsv_debug_keyset_slots(ks._handle(), form, _p(out), out.shape[0], ctypes.byref(slots)))
     return out
 
 
@@ -1011,33 +1003,26 @@ def _keyed_columns(cols, widths, what):
 class KeyedMontColsJob(MontColsJob):
     """A keyed typed batch in flight (dsv_verify_keyed_mont_cols_submit): MontColsJob's interface.  Keeps the
     key set and the column arrays alive until the wait."""
+    _symbol, _what, _widths = "dsv_verify_keyed_mont_cols_submit", "submit_mont_cols", staticmethod(_keyed_mont_widths)
 
     def __init__(self, keyset, cols):  # noqa: D107 (does not call the base constructor: another entry point)
-        n, arr, held = _keyed_columns(cols, _keyed_mont_widths(keyset.scheme), "submit_mont_cols")
+        n, arr, held = _keyed_columns(cols, self._widths(keyset.scheme), self._what)
         self._cols = (keyset, held)
         self._ok = np.zeros(n, dtype=np.uint8)
         self._job = ctypes.c_void_p()
-        _lib.check(_lib.load().dsv_verify_keyed_mont_cols_submit(
-            keyset._handle(), arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
+        _lib.check(getattr(_lib.load(), self._symbol)(keyset._handle(), arr, n, _p(self._ok), ctypes.byref(self._job)))
 
 
-class KeyedOpenMontColsJob(MontColsJob):
+class KeyedOpenMontColsJob(KeyedMontColsJob):
     """An open typed batch in flight (dsv_verify_keyed_open_mont_cols_submit): MontColsJob's interface; reports no
     miss count.  Keeps the key set and the column arrays alive until the wait."""
-
-    def __init__(self, keyset, cols):  # noqa: D107 (does not call the base constructor: another entry point)
-        widths = _layout(keyset.scheme, "_mont")[1]
-        n, arr, held = _keyed_columns(cols, widths, "submit_open_mont_cols")
-        self._cols = (keyset, held)
-        self._ok = np.zeros(n, dtype=np.uint8)
-        self._job = ctypes.c_void_p()
-        _lib.check(_lib.load().dsv_verify_keyed_open_mont_cols_submit(
-            keyset._handle(), arr, ctypes.c_size_t(n), _p(self._ok), ctypes.byref(self._job)))
+    _symbol, _what = "dsv_verify_keyed_open_mont_cols_submit", "submit_open_mont_cols"
+    _widths = staticmethod(lambda scheme: _layout(scheme, "_mont")[1])
 
 
 def keyed_rlc_workspace_bytes(n, k, window_bits=0):
     """dsv_keyed_rlc_workspace_bytes: device bytes of KeySet.verify_rlc_dev's workspace for n items over k keys"""
-    b = int(_lib.load().dsv_keyed_rlc_workspace_bytes(ctypes.c_size_t(n), ctypes.c_size_t(k), ctypes.c_int(window_bits)))
+    b = int(_lib.load().dsv_keyed_rlc_workspace_bytes(n, k, window_bits))
     if b == 0:
         raise ValueError("window_bits must be 0 or one of 4, 6, 8, 12, 14, 16")
     return b
@@ -1045,8 +1030,7 @@ def keyed_rlc_workspace_bytes(n, k, window_bits=0):
 
 def keyed_rlc_plan_info(scheme, n, k, window_bits=0, groups=1):
     """dsv_keyed_rlc_plan_info as a dict (no GPU needed): rlc_plan_info's fields for the keyed plan"""
-    return _plan(_lib.load().dsv_keyed_rlc_plan_info, scheme, ctypes.c_size_t(n), ctypes.c_size_t(k),
-                 ctypes.c_int(window_bits), ctypes.c_int(groups))
+    return _plan(_lib.load().dsv_keyed_rlc_plan_info, scheme, n, k, window_bits, groups)
 
 
 def keyed_rlc_history(device=0, set_to=-1):
@@ -1085,36 +1069,27 @@ class KeySet:
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None, capacity=None):
-        if scheme not in _SCHEME_CODE:
-            raise ValueError("scheme must be one of %s" % sorted(_SCHEME_CODE))
+        code = _code(scheme)
         self.scheme = scheme
         self._h = ctypes.c_void_p()
-        L = _lib.load()
-        code = ctypes.c_int(_SCHEME_CODE[scheme])
+        L, out = _lib.load(), ctypes.byref(self._h)
         if capacity is not None and (_mont_cols is not None or _wire is not None):
             raise ValueError("capacity goes with affine keys: reserve, then append_wire / append_mont_cols")
         if capacity is not None and PK is None and PK2 is None:
-            _lib.check(L.dsv_keyset_create_reserved(code, ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_size_t(0),
-                                                    ctypes.c_size_t(capacity), ctypes.byref(self._h)))
+            _lib.check(L.dsv_keyset_create_reserved(code, None, None, 0, capacity, out))
         elif _mont_cols is not None:
-            k, arr, held = _keyed_columns(_mont_cols, [96] * (1 if scheme == "single" else 2), "from_mont_cols")
-            _lib.check(L.dsv_keyset_create_mont_cols(code, arr, ctypes.c_size_t(k), ctypes.byref(self._h)))
+            k, arr, held = _keyed_columns(_mont_cols, [96] * _KEY_POINTS[scheme], "from_mont_cols")
+            _lib.check(L.dsv_keyset_create_mont_cols(code, arr, k, out))
             del held
         elif _wire is not None:
-            rec = _arr(_wire, 32 if scheme == "single" else 64)
-            _lib.check(L.dsv_keyset_create_wire(code, _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(self._h)))
+            rec = _arr(_wire, self._rec_bytes())
+            _lib.check(L.dsv_keyset_create_wire(code, _p(rec), rec.shape[0], out))
         else:
-            pk = _arr(PK, 64)
-            if (PK2 is None) != (scheme == "single"):
-                raise ValueError("scheme %s takes %s" % (scheme, "PK only" if scheme == "single" else "PK and PK2"))
-            arrs = [pk] + ([_arr(PK2, 64)] if PK2 is not None else [])
-            _same_n(*arrs)
-            pk2 = _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0)
+            k, keys = self._affine_keys(PK, PK2)
             if capacity is None:
-                _lib.check(L.dsv_keyset_create(code, _p(pk), pk2, ctypes.c_size_t(pk.shape[0]), ctypes.byref(self._h)))
+                _lib.check(L.dsv_keyset_create(code, *_slots(_p(a) for a in keys), k, out))
             else:
-                _lib.check(L.dsv_keyset_create_reserved(code, _p(pk), pk2, ctypes.c_size_t(pk.shape[0]),
-                                                        ctypes.c_size_t(capacity), ctypes.byref(self._h)))
+                _lib.check(L.dsv_keyset_create_reserved(code, *_slots(_p(a) for a in keys), k, capacity, out))
         self._refresh()
 
     def _refresh(self):
@@ -1131,6 +1106,14 @@ class KeySet:
         omitted for a set that starts empty.  append / append_wire / append_mont_cols register keys in place."""
         return cls(scheme, PK, PK2, capacity=int(capacity))
 
+    def _affine_keys(self, PK, PK2):
+        """keys as affine points (uint8 [m, 64]; PK2 for the two-point schemes) -> (m, their arrays)"""
+        if (PK2 is None) != (self.scheme == "single"):
+            raise ValueError("scheme %s takes %s"
+                             % (self.scheme, "PK only" if self.scheme == "single" else "PK and PK2"))
+        keys = [_arr(PK, 64)] + ([_arr(PK2, 64)] if PK2 is not None else [])
+        return _same_n(*keys), keys
+
     def _appended(self, rc, first):
         _lib.check(rc)
         self._refresh()
@@ -1140,27 +1123,23 @@ class KeySet:
         """dsv_keyset_append: m more keys as affine points (uint8 [m, 64]; PK2 for the two-point schemes) into the
         live set, in place; blocks.  Returns the index of the first of them (the k before the call); calls enqueued
         afterwards see the new keys, calls in flight and captured graphs keep the k they were enqueued with."""
-        if (PK2 is None) != (self.scheme == "single"):
-            raise ValueError("scheme %s takes %s" % (self.scheme, "PK only" if self.scheme == "single" else "PK and PK2"))
-        arrs = [_arr(PK, 64)] + ([_arr(PK2, 64)] if PK2 is not None else [])
-        m = _same_n(*arrs)
+        m, keys = self._affine_keys(PK, PK2)
         first = ctypes.c_uint32()
         return self._appended(_lib.load().dsv_keyset_append(
-            self._handle(), _p(arrs[0]), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0), ctypes.c_size_t(m),
-            ctypes.byref(first)), first)
+            self._handle(), *_slots(_p(a) for a in keys), m, ctypes.byref(first)), first)
 
     def append_wire(self, pk_bytes):
         """dsv_keyset_append_wire: append() for the reference's key records ([m, 32] or [m, 64])"""
-        rec = _arr(pk_bytes, 32 if self.scheme == "single" else 64)
+        rec = _arr(pk_bytes, self._rec_bytes())
         first = ctypes.c_uint32()
         return self._appended(_lib.load().dsv_keyset_append_wire(
-            self._handle(), _p(rec), ctypes.c_size_t(rec.shape[0]), ctypes.byref(first)), first)
+            self._handle(), _p(rec), rec.shape[0], ctypes.byref(first)), first)
 
     def append_mont_cols(self, cols):
         """dsv_keyset_append_mont_cols: append() for key OBJECTS where they lie (cols as for from_mont_cols)"""
-        m, arr, held = _keyed_columns(list(cols), [96] * (1 if self.scheme == "single" else 2), "append_mont_cols")
+        m, arr, held = _keyed_columns(list(cols), [96] * _KEY_POINTS[self.scheme], "append_mont_cols")
         first = ctypes.c_uint32()
-        rc = _lib.load().dsv_keyset_append_mont_cols(self._handle(), arr, ctypes.c_size_t(m), ctypes.byref(first))
+        rc = _lib.load().dsv_keyset_append_mont_cols(self._handle(), arr, m, ctypes.byref(first))
         del held
         return self._appended(rc, first)
 
@@ -1176,20 +1155,15 @@ class KeySet:
         of key indices[j] — pairwise distinct indices below k — in place; blocks.  k, the capacity and every other
         key's index stay; calls enqueued afterwards see the new keys.  No graph that holds the set may be replayed,
         and no stream of the device may be capturing, while it runs."""
-        if (PK2 is None) != (self.scheme == "single"):
-            raise ValueError("scheme %s takes %s" % (self.scheme, "PK only" if self.scheme == "single" else "PK and PK2"))
-        arrs = [_arr(PK, 64)] + ([_arr(PK2, 64)] if PK2 is not None else [])
-        m = _same_n(*arrs)
+        m, keys = self._affine_keys(PK, PK2)
         idx = self._indices(indices, m)
-        _lib.check(_lib.load().dsv_keyset_replace(
-            self._handle(), _p(idx), _p(arrs[0]), _p(arrs[1]) if len(arrs) > 1 else ctypes.c_void_p(0),
-            ctypes.c_size_t(m)))
+        _lib.check(_lib.load().dsv_keyset_replace(self._handle(), _p(idx), *_slots(_p(a) for a in keys), m))
 
     def replace_wire(self, indices, records):
         """dsv_keyset_replace_wire: replace() for the reference's key records ([m, 32] or [m, 64])"""
-        rec = _arr(records, 32 if self.scheme == "single" else 64)
+        rec = _arr(records, self._rec_bytes())
         idx = self._indices(indices, rec.shape[0])
-        _lib.check(_lib.load().dsv_keyset_replace_wire(self._handle(), _p(idx), _p(rec), ctypes.c_size_t(rec.shape[0])))
+        _lib.check(_lib.load().dsv_keyset_replace_wire(self._handle(), _p(idx), _p(rec), rec.shape[0]))
 
     @classmethod
     def from_wire(cls, scheme, pk_bytes):
@@ -1230,17 +1204,31 @@ class KeySet:
         changes, and cut to the k the library copied for — another thread's append may land at any time"""
         out = np.zeros(self.capacity, dtype=np.uint8)
         k = ctypes.c_size_t()
-        _lib.check(_lib.load().dsv_keyset_key_ok_n(self._handle(), _p(out), ctypes.c_size_t(out.shape[0]),
-                                                   ctypes.byref(k)))
+        _lib.check(_lib.load().dsv_keyset_key_ok_n(self._handle(), _p(out), out.shape[0], ctypes.byref(k)))
         return out[:min(k.value, out.shape[0])]
 
     def debug_entry(self, key, point, window, digit):
         """affine u || v of digit * 2^(8 * window) * point (0: PK, 1: PK' / Gen) from the key's table"""
         out = np.zeros(64, dtype=np.uint8)
-        _lib.check(_lib.load().dsv_debug_keyset_entry(self._handle(), ctypes.c_size_t(key), ctypes.c_int(point),
-                                                      ctypes.c_int(window), ctypes.c_int(digit), _p(out)))
+        _lib.check(_lib.load().dsv_debug_keyset_entry(self._handle(), key, point, window, digit, _p(out)))
         return out
 
+    # ---- the two bodies every verify method ends in ------------------------------------------------------------
+    def _host_call(self, symbol, ins, n, misses=False):
+        """symbol(ks, *ins, n, ok[, &misses]), a blocking host form -> verdicts [n] (misses: (verdicts, misses))"""
+        ok = np.zeros(n, dtype=np.uint8)
+        count = ctypes.c_size_t()
+        tail = [ctypes.byref(count)] if misses else []
+        _lib.check(getattr(_lib.load(), symbol)(self._handle(), *ins, n, _p(ok), *tail))
+        return (ok, count.value) if misses else ok
+
+    @staticmethod
+    def _dev_tail(n, dev, ok, workspace, ws_need, stream):
+        """what follows the inputs in every keyed _dev call, checked: n, ok, workspace, workspace_bytes, stream"""
+        return [n, _bytes_out(ok, n, dev, "ok"), _bytes_out(workspace, ws_need, dev, "workspace"), workspace.numel(),
+                _stream_ptr(stream, dev)]
+
+    # ---- by key index ------------------------------------------------------------------------------------------
     def _pts(self, args):
         """(u, R[, Rp], idx, m) split by scheme"""
         want = 5 if self.scheme == "double" else 4
@@ -1249,46 +1237,42 @@ class KeySet:
                 self.scheme, "(u, R, Rp, idx, m)" if want == 5 else "(u, R, idx, m)"))
         return args[0], args[1:-2], args[-2], args[-1]
 
+    @staticmethod
+    def _host_idx(idx, n):
+        """the index column of the host forms: uint32 [n]"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        if idx.shape[0] != n:
+            raise ValueError("idx has %d entries, the batch %d items" % (idx.shape[0], n))
+        return idx
+
     def verify(self, *args):
         """host arrays -> verdicts [n]; idx: key indices (uint32 [n]; an index >= k gives 0)"""
         u, pts, idx, m = self._pts(args)
         u, m = _arr(u, 32), _arr(m, 32)
         pts = [_arr(p, 64) for p in pts]
-        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
         n = _same_n(u, m, *pts)
-        if idx.shape[0] != n:
-            raise ValueError("idx has %d entries, the batch %d items" % (idx.shape[0], n))
-        ok = np.zeros(n, dtype=np.uint8)
-        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed" % self.scheme)(
-            self._handle(), _p(u), *[_p(p) for p in pts], _p(idx), _p(m), ctypes.c_size_t(n), _p(ok)))
-        return ok
+        idx = self._host_idx(idx, n)
+        return self._host_call("dsv_verify_%s_keyed" % self.scheme, [_p(u), *[_p(p) for p in pts], _p(idx), _p(m)], n)
 
-    def _dev_args(self, args, what):
-        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace), checked -> (n, dev, the input pointers in argument
-        order, ok, workspace)"""
+    def _dev_args(self, args, what, width=64):
+        """CUDA tensors (u, R[, Rp], idx, m, ok, workspace), points of `width` bytes, checked -> (n, dev, the input
+        pointers in argument order, ok, workspace)"""
         if len(args) < 2:
             raise ValueError("%s takes the inputs, then ok and workspace" % what)
         ok, workspace = args[-2], args[-1]
         u, pts, idx, m = self._pts(args[:-2])
-        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
-        tensors = [u] + list(pts) + [m]
-        n, dev = _rows(*zip(tensors, [32] + [64] * len(pts) + [32], names))
-        ip = _idx(idx, n, dev, "idx")
-        if idx.dim() != 1 or idx.shape[0] != n:
-            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
-        return n, dev, [_tp(u, 32)] + [_tp(p, 64) for p in pts] + [ip, _tp(m, 32)], ok, workspace
+        names = ["u"] + ["R", "Rp"][:len(pts)] + ["m"]
+        n, dev = _rows(*zip([u, *pts, m], [32] + [width] * len(pts) + [32], names))
+        ip = _col32(idx, n, dev, "idx")
+        return n, dev, [u.data_ptr(), *[p.data_ptr() for p in pts], ip, m.data_ptr()], ok, workspace
 
     def verify_dev(self, *args, stream=None):
         """CUDA tensors (u, R[, Rp], idx, m, ok, workspace): verdicts into ok, enqueued on `stream` (default:
         torch's current stream of the batch's device); does not synchronise.  idx: int32 [n], read as uint32;
         workspace: >= keyed_workspace_bytes(n) bytes."""
         n, dev, ins, ok, workspace = self._dev_args(args, "verify_dev")
-        ws_need = keyed_workspace_bytes(n)
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, ws_need, dev, "workspace")
-        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_dev" % self.scheme)(
-            self._handle(), *ins, ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
-            _stream_ptr(stream, dev)))
+        tail = self._dev_tail(n, dev, ok, workspace, keyed_workspace_bytes(n), stream)
+        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_dev" % self.scheme)(self._handle(), *ins, *tail))
 
     def verify_rlc_dev(self, *args, stream=None, window_bits=0, accepted_out=None):
         """The keyed fast accept (dsv_verify_*_keyed_rlc_dev): the verdicts of verify_dev, through one aggregate
@@ -1298,48 +1282,39 @@ class KeySet:
         by the device, the call does not block and returns None.  Never inside a graph capture (refused)."""
         n, dev, ins, ok, workspace = self._dev_args(args, "verify_rlc_dev")
         arg, box = _accepted_arg(accepted_out, dev)
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_rlc_workspace_bytes(n, self.k, window_bits), dev, "workspace")
+        tail = self._dev_tail(n, dev, ok, workspace, keyed_rlc_workspace_bytes(n, self.k, window_bits), stream)
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_rlc_dev" % self.scheme)(
-            self._handle(), *ins, ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
-            _stream_ptr(stream, dev), ctypes.c_int(window_bits), arg))
+            self._handle(), *ins, *tail, window_bits, arg))
         return bool(box.value) if box is not None else None
+
+    def _sig_bytes(self):
+        return _SCHEMES[self.scheme][1][0]
 
     def verify_wire(self, sig, idx, m):
         """Serialized signatures (dsv_verify_*_keyed_wire): host arrays sig [n, 64] (double: [n, 96]), idx
         uint32 [n], m [n, 32] -> verdicts [n], through the chunked host pipeline on the set's device."""
-        sig, m = _arr(sig, _SCHEMES[self.scheme][1][0]), _arr(m, 32)
-        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        sig, m = _arr(sig, self._sig_bytes()), _arr(m, 32)
         n = _same_n(sig, m)
-        if idx.shape[0] != n:
-            raise ValueError("idx has %d entries, the batch %d items" % (idx.shape[0], n))
-        ok = np.zeros(n, dtype=np.uint8)
-        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_wire" % self.scheme)(
-            self._handle(), _p(sig), _p(idx), _p(m), ctypes.c_size_t(n), _p(ok)))
-        return ok
+        idx = self._host_idx(idx, n)
+        return self._host_call("dsv_verify_%s_keyed_wire" % self.scheme, [_p(sig), _p(idx), _p(m)], n)
 
     def verify_wire_dev(self, sig, idx, m, ok, workspace, stream=None):
         """Serialized signatures in device memory (dsv_verify_*_keyed_wire_dev): CUDA tensors sig [n, 64]
         (double: [n, 96]), idx int32 [n] (read as uint32), m [n, 32]; verdicts into ok, enqueued on `stream`
         (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
         keyed_wire_workspace_bytes(scheme, n) bytes."""
-        n, dev = _rows((sig, _SCHEMES[self.scheme][1][0], "sig"), (m, 32, "m"))
-        ip = _idx(idx, n, dev, "idx")
-        if idx.dim() != 1 or idx.shape[0] != n:
-            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_wire_workspace_bytes(self.scheme, n), dev, "workspace")
+        n, dev = _rows((sig, self._sig_bytes(), "sig"), (m, 32, "m"))
+        ip = _col32(idx, n, dev, "idx")
+        tail = self._dev_tail(n, dev, ok, workspace, keyed_wire_workspace_bytes(self.scheme, n), stream)
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_wire_dev" % self.scheme)(
-            self._handle(), _tp(sig, _SCHEMES[self.scheme][1][0]), ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev)))
+            self._handle(), sig.data_ptr(), ip, m.data_ptr(), *tail))
 
     def verify_mont_cols(self, cols):
         """`Signature*` objects where they lie (dsv_verify_keyed_mont_cols): cols = [u, R, idx, m] (double:
         [u, R, R', idx, m]), uint8 views [n, 32 | 96 | 4 | 32] of Montgomery limbs with strided rows (idx may be a
         uint32 [n] array or view) -> verdicts [n], through the chunked host pipeline on the set's device."""
         n, arr, held = _keyed_columns(cols, _keyed_mont_widths(self.scheme), "verify_mont_cols")
-        ok = np.zeros(n, dtype=np.uint8)
-        _lib.check(_lib.load().dsv_verify_keyed_mont_cols(self._handle(), arr, ctypes.c_size_t(n), _p(ok)))
+        ok = self._host_call("dsv_verify_keyed_mont_cols", [arr], n)
         del held
         return ok
 
@@ -1353,26 +1328,15 @@ class KeySet:
         [, Rp [n, 96]], idx int32 [n] read as uint32, m [n, 32], ok, workspace); verdicts into ok, enqueued on
         `stream` (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
         keyed_mont_workspace_bytes(scheme, n) bytes."""
-        if len(args) < 2:
-            raise ValueError("verify_mont_dev takes the inputs, then ok and workspace")
-        ok, workspace = args[-2], args[-1]
-        u, pts, idx, m = self._pts(args[:-2])
-        names = ["u"] + (["R", "Rp"] if len(pts) == 2 else ["R"]) + ["m"]
-        n, dev = _rows(*zip([u] + list(pts) + [m], [32] + [96] * len(pts) + [32], names))
-        ip = _idx(idx, n, dev, "idx")
-        if idx.dim() != 1 or idx.shape[0] != n:
-            raise ValueError("idx: expected [n] = [%d], got %r" % (n, tuple(idx.shape)))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_mont_workspace_bytes(self.scheme, n), dev, "workspace")
-        _lib.check(_lib.load().dsv_verify_keyed_mont_dev(
-            self._handle(), _tp(u, 32), _tp(pts[0], 96), _tp(pts[1], 96) if len(pts) == 2 else ctypes.c_void_p(0),
-            ip, _tp(m, 32), ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()),
-            _stream_ptr(stream, dev)))
+        n, dev, ins, ok, workspace = self._dev_args(args, "verify_mont_dev", 96)
+        tail = self._dev_tail(n, dev, ok, workspace, keyed_mont_workspace_bytes(self.scheme, n), stream)
+        # one call for every scheme: (u, R, Rp or null, idx, m)
+        _lib.check(_lib.load().dsv_verify_keyed_mont_dev(self._handle(), ins[0], *_slots(ins[1:-2]), *ins[-2:], *tail))
 
     # ---- by key value: the index over the set's own keys -----------------------------------------------------
     def _key_cols(self, keys, what):
         """(key_a[, key_b]) by scheme"""
-        want = 1 if self.scheme == "single" else 2
+        want = _KEY_POINTS[self.scheme]
         if len(keys) != want:
             raise ValueError("%s key set: %s takes %s" % (
                 self.scheme, what, "key_a" if want == 1 else "key_a and key_b (PK' / Gen)"))
@@ -1392,8 +1356,7 @@ class KeySet:
         idx = np.zeros(n, dtype=np.uint32)
         misses = ctypes.c_size_t()
         _lib.check(_lib.load().dsv_keyset_lookup(
-            self._handle(), _p(cols[0]), _p(cols[1]) if len(cols) == 2 else ctypes.c_void_p(0), ctypes.c_size_t(n),
-            _p(idx), ctypes.byref(misses)))
+            self._handle(), *_slots(_p(c) for c in cols), n, _p(idx), ctypes.byref(misses)))
         return idx, misses.value
 
     @staticmethod
@@ -1401,12 +1364,12 @@ class KeySet:
         """a key column of the _dev forms: uint8 [n, 64], 16-byte aligned (the lookup reads it in 16-byte loads)"""
         if _t(t, 64, name).data_ptr() % 16:
             raise ValueError("%s: key columns must be 16-byte aligned" % name)
-        return ctypes.c_void_p(t.data_ptr())
+        return t.data_ptr()
 
     @staticmethod
     def _misses_ptr(misses, dev):
         if misses is None:
-            return ctypes.c_void_p(0)
+            return None
         return _idx(misses, 1, dev, "misses")
 
     def lookup_dev(self, *args, misses=None, stream=None):
@@ -1416,136 +1379,110 @@ class KeySet:
         if len(args) < 1:
             raise ValueError("lookup_dev takes the key columns, then idx_out")
         cols, out = self._key_cols(args[:-1], "lookup_dev"), args[-1]
-        n, dev = _rows(*zip(cols, [64] * len(cols), ["key_a", "key_b"]))
-        op = _idx(out, n, dev, "idx_out")
-        if out.dim() != 1 or out.shape[0] != n:
-            raise ValueError("idx_out: expected [n] = [%d], got %r" % (n, tuple(out.shape)))
+        names = ["key_a", "key_b"][:len(cols)]
+        n, dev = _rows(*zip(cols, [64] * len(cols), names))
+        op = _col32(out, n, dev, "idx_out")
         _lib.check(_lib.load().dsv_keyset_lookup_dev(
-            self._handle(), self._key_ptr(cols[0], "key_a"),
-            self._key_ptr(cols[1], "key_b") if len(cols) == 2 else ctypes.c_void_p(0), ctypes.c_size_t(n), op, self._misses_ptr(misses, dev), _stream_ptr(stream, dev)))
+            self._handle(), *_slots(self._key_ptr(c, name) for c, name in zip(cols, names)), n, op,
+            self._misses_ptr(misses, dev), _stream_ptr(stream, dev)))
 
-    def _by_value(self, args, what):
-        """(u, R[, Rp], key_a[, key_b], m) split by scheme -> u, nonce points, key columns, m"""
-        ns, nk = (2 if self.scheme == "double" else 1), (1 if self.scheme == "single" else 2)
+    def _by_value(self, args, what, scheme=None):
+        """(u, R[, Rp], key_a[, key_b], m) split by scheme (default: the set's) -> u, nonce points, key columns, m"""
+        scheme = scheme or self.scheme
+        ns, nk = (2 if scheme == "double" else 1), _KEY_POINTS[scheme]
         if len(args) != 2 + ns + nk:
-            raise ValueError("%s key set: %s takes (%s)" % (
-                self.scheme, what, ", ".join(_SCHEMES[self.scheme][0])))
+            raise ValueError("%s key set: %s takes (%s)" % (self.scheme, what, ", ".join(_SCHEMES[scheme][0])))
         return args[0], list(args[1:1 + ns]), list(args[1 + ns:-1]), args[-1]
+
+    @staticmethod
+    def _value_ins(ptrs, ns, scheme):
+        """the pointers (u, ns nonce points, the key columns, m) as a by-value call takes them.  scheme None: one
+        of the calls that serve every scheme, with two places for the nonce points and two for the key columns
+        (null where the set's scheme has one); else that scheme's own call, which takes exactly its columns"""
+        if scheme is not None:
+            return ptrs
+        return [ptrs[0], *_slots(ptrs[1:1 + ns]), *_slots(ptrs[1 + ns:-1]), ptrs[-1]]
+
+    def _verify_by_value(self, symbol, args, what, scheme=None):
+        """a by-value verify over host arrays -> (verdicts [n], misses); scheme as for _value_ins"""
+        u, pts, keys, m = self._by_value(args, what, scheme)
+        u, m = _arr(u, 32), _arr(m, 32)
+        pts, keys = [_arr(p, 64) for p in pts], [_arr(c, 64) for c in keys]
+        n = _same_n(u, m, *pts, *keys)
+        ins = self._value_ins([_p(a) for a in (u, *pts, *keys, m)], len(pts), scheme)
+        return self._host_call(symbol, ins, n, misses=True)
+
+    def _verify_by_value_dev(self, symbol, args, what, ws_bytes, misses, stream, width=64, scheme=None):
+        """a by-value verify over CUDA tensors (..., ok, workspace), points of `width` bytes, workspace of
+        ws_bytes(n) bytes; scheme as for _value_ins"""
+        if len(args) < 2:
+            raise ValueError("%s takes the inputs, then ok and workspace" % what)
+        ok, workspace = args[-2], args[-1]
+        u, pts, keys, m = self._by_value(args[:-2], what, scheme)
+        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
+        cols = list(zip([u, *pts, *keys, m], [32] + [width] * (len(pts) + len(keys)) + [32], names))
+        n, dev = _rows(*cols)
+        tail = self._dev_tail(n, dev, ok, workspace, ws_bytes(n), stream)
+        if width == 96:  # the typed form reads every input in 16-byte loads, the affine forms the key columns
+            ptrs = [self._rec_ptr(t, w, name) for t, w, name in cols]
+        else:
+            ptrs = [self._key_ptr(t, name) if name.startswith("key") else t.data_ptr() for t, w, name in cols]
+        _lib.check(getattr(_lib.load(), symbol)(
+            self._handle(), *self._value_ins(ptrs, len(pts), scheme), *tail, self._misses_ptr(misses, dev)))
 
     def verify_lookup(self, *args):
         """Closed-set verify by key value (dsv_verify_keyed_lookup): host arrays (u, R, PK, m) — double (u, R, Rp,
         PK, PKp, m), vargen (u, R, PK, Gen, m), the unkeyed entry points' arguments — -> (verdicts [n], misses).
         An item whose key is not a valid registered key of the set is rejected."""
-        u, pts, keys, m = self._by_value(args, "verify_lookup")
-        u, m = _arr(u, 32), _arr(m, 32)
-        pts, keys = [_arr(p, 64) for p in pts], [_arr(c, 64) for c in keys]
-        n = _same_n(u, m, *pts, *keys)
-        ok = np.zeros(n, dtype=np.uint8)
-        misses = ctypes.c_size_t()
-        null = ctypes.c_void_p(0)
-        _lib.check(_lib.load().dsv_verify_keyed_lookup(
-            self._handle(), _p(u), _p(pts[0]), _p(pts[1]) if len(pts) == 2 else null, _p(keys[0]),
-            _p(keys[1]) if len(keys) == 2 else null, _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
-        return ok, misses.value
+        return self._verify_by_value("dsv_verify_keyed_lookup", args, "verify_lookup")
 
     def verify_lookup_dev(self, *args, misses=None, stream=None):
         """CUDA tensors (u, R[, Rp], key_a[, key_b], m, ok, workspace): verify_lookup's verdicts into ok, enqueued
         on `stream` (default: torch's current stream of the batch's device); does not synchronise.  workspace: >=
         keyed_lookup_workspace_bytes(n) bytes; misses as for lookup_dev."""
-        if len(args) < 2:
-            raise ValueError("verify_lookup_dev takes the inputs, then ok and workspace")
-        ok, workspace = args[-2], args[-1]
-        u, pts, keys, m = self._by_value(args[:-2], "verify_lookup_dev")
-        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
-        n, dev = _rows(*zip([u] + pts + keys + [m], [32] + [64] * (len(pts) + len(keys)) + [32], names))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_lookup_workspace_bytes(n), dev, "workspace")
-        null = ctypes.c_void_p(0)
-        _lib.check(_lib.load().dsv_verify_keyed_lookup_dev(
-            self._handle(), _tp(u, 32), _tp(pts[0], 64), _tp(pts[1], 64) if len(pts) == 2 else null,
-            self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
-            ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
+        self._verify_by_value_dev("dsv_verify_keyed_lookup_dev", args, "verify_lookup_dev",
+                                  keyed_lookup_workspace_bytes, misses, stream)
 
     def verify_open(self, *args):
         """Open-set verify by key value (dsv_verify_keyed_open; single and double sets): host arrays (u, R, PK, m) —
         double (u, R, Rp, PK, PKp, m), the unkeyed entry points' arguments — -> (verdicts [n], misses).  The
         verdicts are the unkeyed entry point's for every input: the set is a key cache.  An item whose key is not
         a valid registered key is decided by the unkeyed equation in the same call; misses counts those."""
-        u, pts, keys, m = self._by_value(args, "verify_open")
-        u, m = _arr(u, 32), _arr(m, 32)
-        pts, keys = [_arr(p, 64) for p in pts], [_arr(c, 64) for c in keys]
-        n = _same_n(u, m, *pts, *keys)
-        ok = np.zeros(n, dtype=np.uint8)
-        misses = ctypes.c_size_t()
-        null = ctypes.c_void_p(0)
-        _lib.check(_lib.load().dsv_verify_keyed_open(
-            self._handle(), _p(u), _p(pts[0]), _p(pts[1]) if len(pts) == 2 else null, _p(keys[0]),
-            _p(keys[1]) if len(keys) == 2 else null, _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
-        return ok, misses.value
+        return self._verify_by_value("dsv_verify_keyed_open", args, "verify_open")
 
     def verify_open_dev(self, *args, misses=None, stream=None):
         """CUDA tensors (u, R[, Rp], key_a[, key_b], m, ok, workspace): verify_open's verdicts into ok, enqueued
         on `stream` (default: torch's current stream of the batch's device) as one chain of launches; does not
         synchronise and may be captured.  workspace: >= keyed_open_workspace_bytes(n) bytes; misses as for
         lookup_dev."""
-        if len(args) < 2:
-            raise ValueError("verify_open_dev takes the inputs, then ok and workspace")
-        ok, workspace = args[-2], args[-1]
-        u, pts, keys, m = self._by_value(args[:-2], "verify_open_dev")
-        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
-        n, dev = _rows(*zip([u] + pts + keys + [m], [32] + [64] * (len(pts) + len(keys)) + [32], names))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_open_workspace_bytes(n), dev, "workspace")
-        null = ctypes.c_void_p(0)
-        _lib.check(_lib.load().dsv_verify_keyed_open_dev(
-            self._handle(), _tp(u, 32), _tp(pts[0], 64), _tp(pts[1], 64) if len(pts) == 2 else null,
-            self._key_ptr(keys[0], "key_a"), self._key_ptr(keys[1], "key_b") if len(keys) == 2 else null, _tp(m, 32),
-            ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
+        self._verify_by_value_dev("dsv_verify_keyed_open_dev", args, "verify_open_dev",
+                                  keyed_open_workspace_bytes, misses, stream)
 
     def verify_vargen_open(self, *args):
         """verify_vargen_open(u, R, PK, Gen, m) -> (verdicts [n], misses): the var-generator scheme's open-set
         verify by key value (dsv_verify_vargen_keyed_open; var-generator sets — verify_open refuses them), host
         arrays.  The verdicts are verify_vargen's for every input; an item whose (PK, Gen) bytes are not those of a
         valid registered key is decided by the unkeyed equation in the same call, and misses counts those."""
-        if len(args) != 5:
-            raise ValueError("verify_vargen_open takes (u, R, PK, Gen, m)")
-        u, R, PK, Gen, m = args
-        u, m = _arr(u, 32), _arr(m, 32)
-        R, PK, Gen = _arr(R, 64), _arr(PK, 64), _arr(Gen, 64)
-        n = _same_n(u, m, R, PK, Gen)
-        ok = np.zeros(n, dtype=np.uint8)
-        misses = ctypes.c_size_t()
-        _lib.check(_lib.load().dsv_verify_vargen_keyed_open(
-            self._handle(), _p(u), _p(R), _p(PK), _p(Gen), _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
-        return ok, misses.value
+        return self._verify_by_value("dsv_verify_vargen_keyed_open", args, "verify_vargen_open", "vargen")
 
     def verify_vargen_open_dev(self, *args, misses=None, stream=None):
         """verify_vargen_open_dev(u, R, PK, Gen, m, ok, workspace, misses=None, stream=None): CUDA tensors;
         verify_vargen_open's verdicts into ok, enqueued on `stream` (default: torch's current stream of the batch's
         device) as one chain of launches; does not synchronise and may be captured.  workspace: >=
         keyed_open_workspace_bytes(n) bytes; misses as for lookup_dev."""
-        if len(args) != 7:
-            raise ValueError("verify_vargen_open_dev takes (u, R, PK, Gen, m), then ok and workspace")
-        u, R, PK, Gen, m, ok, workspace = args
-        n, dev = _rows(*zip([u, R, PK, Gen, m], [32, 64, 64, 64, 32], ["u", "R", "PK", "Gen", "m"]))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_open_workspace_bytes(n), dev, "workspace")
-        _lib.check(_lib.load().dsv_verify_vargen_keyed_open_dev(
-            self._handle(), _tp(u, 32), _tp(R, 64), self._key_ptr(PK, "PK"), self._key_ptr(Gen, "Gen"), _tp(m, 32),
-            ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
-            self._misses_ptr(misses, dev)))
+        self._verify_by_value_dev("dsv_verify_vargen_keyed_open_dev", args, "verify_vargen_open_dev",
+                                  keyed_open_workspace_bytes, misses, stream, scheme="vargen")
 
     # ---- by key record: the index over the compressed records of the set's own keys ----------------------------
     def _rec_bytes(self):
         return _SCHEMES[self.scheme][1][1]
 
-    def _rec_ptr(self, t, width, name):
+    @staticmethod
+    def _rec_ptr(t, width, name):
         """a record column of the _dev forms: uint8 [n, width], 16-byte aligned (read in 16-byte loads)"""
         if _t(t, width, name).data_ptr() % 16:
             raise ValueError("%s: records must be 16-byte aligned" % name)
-        return ctypes.c_void_p(t.data_ptr())
+        return t.data_ptr()
 
     def lookup_wire(self, pk):
         """host array pk [n, 32] (two-point sets: [n, 64]) of key records -> (idx uint32 [n], misses): the lowest
@@ -1554,8 +1491,7 @@ class KeySet:
         n = rec.shape[0]
         idx = np.zeros(n, dtype=np.uint32)
         misses = ctypes.c_size_t()
-        _lib.check(_lib.load().dsv_keyset_lookup_wire(self._handle(), _p(rec), ctypes.c_size_t(n), _p(idx),
-                                                      ctypes.byref(misses)))
+        _lib.check(_lib.load().dsv_keyset_lookup_wire(self._handle(), _p(rec), n, _p(idx), ctypes.byref(misses)))
         return idx, misses.value
 
     def lookup_wire_dev(self, pk, idx_out, misses=None, stream=None):
@@ -1563,38 +1499,31 @@ class KeySet:
         lookup_dev.  Enqueued on `stream` (default: torch's current stream of the batch's device); does not
         synchronise."""
         n, dev = _rows((pk, self._rec_bytes(), "pk"))
-        op = _idx(idx_out, n, dev, "idx_out")
-        if idx_out.dim() != 1 or idx_out.shape[0] != n:
-            raise ValueError("idx_out: expected [n] = [%d], got %r" % (n, tuple(idx_out.shape)))
+        op = _col32(idx_out, n, dev, "idx_out")
         _lib.check(_lib.load().dsv_keyset_lookup_wire_dev(
-            self._handle(), self._rec_ptr(pk, self._rec_bytes(), "pk"), ctypes.c_size_t(n), op,
-            self._misses_ptr(misses, dev), _stream_ptr(stream, dev)))
+            self._handle(), self._rec_ptr(pk, self._rec_bytes(), "pk"), n, op, self._misses_ptr(misses, dev),
+            _stream_ptr(stream, dev)))
 
     def verify_open_wire(self, sig, pk, m):
         """Open-set verify of serialized triples (dsv_verify_*_keyed_open_wire; every scheme): host arrays sig
         [n, 64] (double: [n, 96]), pk [n, 32] (two-point sets: [n, 64]), m [n, 32] -> (verdicts [n], misses).  The
         verdicts are verify_*_wire's for every input; an item whose key record is not the canonical record of a
         valid registered key is decided by the unkeyed equation in the same call, and misses counts those."""
-        sig, rec, m = _arr(sig, _SCHEMES[self.scheme][1][0]), _arr(pk, self._rec_bytes()), _arr(m, 32)
+        sig, rec, m = _arr(sig, self._sig_bytes()), _arr(pk, self._rec_bytes()), _arr(m, 32)
         n = _same_n(sig, rec, m)
-        ok = np.zeros(n, dtype=np.uint8)
-        misses = ctypes.c_size_t()
-        _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_open_wire" % self.scheme)(
-            self._handle(), _p(sig), _p(rec), _p(m), ctypes.c_size_t(n), _p(ok), ctypes.byref(misses)))
-        return ok, misses.value
+        return self._host_call("dsv_verify_%s_keyed_open_wire" % self.scheme, [_p(sig), _p(rec), _p(m)], n,
+                               misses=True)
 
     def verify_open_wire_dev(self, sig, pk, m, ok, workspace, misses=None, stream=None):
         """CUDA tensors sig [n, 64 | 96], pk [n, 32 | 64], m [n, 32]: verify_open_wire's verdicts into ok, enqueued
         on `stream` (default: torch's current stream of the batch's device) as one chain of launches; does not
         synchronise and may be captured.  workspace: >= keyed_open_wire_workspace_bytes(scheme, n) bytes; misses
         as for lookup_dev."""
-        sb = _SCHEMES[self.scheme][1][0]
-        n, dev = _rows((sig, sb, "sig"), (pk, self._rec_bytes(), "pk"), (m, 32, "m"))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_open_wire_workspace_bytes(self.scheme, n), dev, "workspace")
+        sb, rb = self._sig_bytes(), self._rec_bytes()
+        n, dev = _rows((sig, sb, "sig"), (pk, rb, "pk"), (m, 32, "m"))
+        tail = self._dev_tail(n, dev, ok, workspace, keyed_open_wire_workspace_bytes(self.scheme, n), stream)
         _lib.check(getattr(_lib.load(), "dsv_verify_%s_keyed_open_wire_dev" % self.scheme)(
-            self._handle(), self._rec_ptr(sig, sb, "sig"), self._rec_ptr(pk, self._rec_bytes(), "pk"), _tp(m, 32),
-            ctypes.c_size_t(n), okp, wsp, ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev),
+            self._handle(), self._rec_ptr(sig, sb, "sig"), self._rec_ptr(pk, rb, "pk"), m.data_ptr(), *tail,
             self._misses_ptr(misses, dev)))
 
     # ---- the key cache for typed objects: verify_batch's arguments, Montgomery limbs ---------------------------
@@ -1605,12 +1534,9 @@ class KeySet:
         verdicts are verify_mont_cols' for every input; an item whose normalised key is not a valid registered key
         is decided by the unkeyed equation in the same call, and misses counts those."""
         n, arr, held = _keyed_columns(cols, _layout(self.scheme, "_mont")[1], "verify_open_mont_cols")
-        ok = np.zeros(n, dtype=np.uint8)
-        misses = ctypes.c_size_t()
-        _lib.check(_lib.load().dsv_verify_keyed_open_mont_cols(self._handle(), arr, ctypes.c_size_t(n), _p(ok),
-                                                               ctypes.byref(misses)))
+        res = self._host_call("dsv_verify_keyed_open_mont_cols", [arr], n, misses=True)
         del held
-        return ok, misses.value
+        return res
 
     def submit_open_mont_cols(self, cols):
         """Asynchronous verify_open_mont_cols (dsv_verify_keyed_open_mont_cols_submit): returns a job at once
@@ -1623,19 +1549,5 @@ class KeySet:
         verdicts into ok, enqueued on `stream` (default: torch's current stream of the batch's device) as one chain
         of launches; does not synchronise and may be captured.  workspace: >=
         keyed_open_mont_workspace_bytes(scheme, n) bytes; misses as for lookup_dev."""
-        if len(args) < 2:
-            raise ValueError("verify_open_mont_dev takes the inputs, then ok and workspace")
-        ok, workspace = args[-2], args[-1]
-        u, pts, keys, m = self._by_value(args[:-2], "verify_open_mont_dev")
-        names = ["u"] + ["R", "Rp"][:len(pts)] + ["key_a", "key_b"][:len(keys)] + ["m"]
-        widths = [32] + [96] * (len(pts) + len(keys)) + [32]
-        n, dev = _rows(*zip([u] + pts + keys + [m], widths, names))
-        okp = _bytes_out(ok, n, dev, "ok")
-        wsp = _bytes_out(workspace, keyed_open_mont_workspace_bytes(self.scheme, n), dev, "workspace")
-        null = ctypes.c_void_p(0)
-        ptr = [self._rec_ptr(t, w, nm) for t, w, nm in zip([u] + pts + keys + [m], widths, names)]
-        ns = len(pts)
-        _lib.check(_lib.load().dsv_verify_keyed_open_mont_dev(
-            self._handle(), ptr[0], ptr[1], ptr[2] if ns == 2 else null, ptr[1 + ns],
-            ptr[2 + ns] if len(keys) == 2 else null, ptr[-1], ctypes.c_size_t(n), okp, wsp,
-            ctypes.c_size_t(workspace.numel()), _stream_ptr(stream, dev), self._misses_ptr(misses, dev)))
+        self._verify_by_value_dev("dsv_verify_keyed_open_mont_dev", args, "verify_open_mont_dev",
+                                  lambda n: keyed_open_mont_workspace_bytes(self.scheme, n), misses, stream, width=96)
