@@ -395,6 +395,9 @@ inline JubJubExtended derive(const JubJubScalar& sk, int which, const JubJubExte
   }
   return JubJubExtended::from(JubJubAffine::from_canonical(out));
 }
+// `verify` of the three key types (defined below SchemeTraits, the per-scheme table)
+template <class Key, class Sig>
+bool verify_one(const Key& pk, const Sig& sig, const BlsScalar& message);
 }  // namespace detail
 
 struct SecretKey {
@@ -443,13 +446,7 @@ struct PublicKey {
     return PublicKey{*p};
   }
   // u*G + c*PK == R  with c = H(R || m): the limbs of (u, R, pk, m) go to the engine as they are
-  bool verify(const Signature& sig, const BlsScalar& message) const {
-    detail::ensure_init();
-    uint8_t ok = 0;
-    const dsv_column cols[4] = {{&sig.u_, sizeof sig}, {&sig.R_, sizeof sig}, {&pk, sizeof *this}, {&message, 32}};
-    detail::check(dsv_verify_single_mont_cols(cols, 1, &ok), "dsv_verify_single_mont_cols");
-    return ok == 1;
-  }
+  bool verify(const Signature& sig, const BlsScalar& message) const { return detail::verify_one(*this, sig, message); }
   bool operator==(const PublicKey& o) const { return pk == o.pk; }
 };
 
@@ -477,12 +474,7 @@ struct PublicKeyDouble {
     return PublicKeyDouble{*p, *pp};
   }
   bool verify(const SignatureDouble& sig, const BlsScalar& message) const {
-    detail::ensure_init();
-    uint8_t ok = 0;
-    const dsv_column cols[6] = {{&sig.u_, sizeof sig},        {&sig.R_, sizeof sig}, {&sig.R_prime_, sizeof sig},
-                                {&pk_, sizeof *this},         {&pk_prime_, sizeof *this}, {&message, 32}};
-    detail::check(dsv_verify_double_mont_cols(cols, 1, &ok), "dsv_verify_double_mont_cols");
-    return ok == 1;
+    return detail::verify_one(*this, sig, message);
   }
 };
 
@@ -551,16 +543,120 @@ struct PublicKeyVarGen {
     return PublicKeyVarGen{*p, *g};
   }
   bool verify(const SignatureVarGen& sig, const BlsScalar& message) const {
-    detail::ensure_init();
-    uint8_t ok = 0;
-    const dsv_column cols[5] = {{&sig.u_, sizeof sig}, {&sig.R_, sizeof sig}, {&pk_, sizeof *this},
-                                {&generator_, sizeof *this}, {&message, 32}};
-    detail::check(dsv_verify_vargen_mont_cols(cols, 1, &ok), "dsv_verify_vargen_mont_cols");
-    return ok == 1;
+    return detail::verify_one(*this, sig, message);
   }
 };
 static_assert(sizeof(PublicKey) == 160 && sizeof(PublicKeyDouble) == 320 && sizeof(PublicKeyVarGen) == 320,
               "the Rust structs' sizes");
+
+// ---- the one per-scheme table: SchemeTraits<Key> -----------------------------------------------------
+// The signature type, the engine's scheme number, the fields of a signature and of a key as strided columns
+// (sig_cols / key_cols append them) and the three C entry points over typed objects, each with the name
+// detail::check reports it under.
+namespace detail {
+struct Columns {  // item 0's fields, each with the stride of the struct it lives in
+  dsv_column c[6];
+  int count = 0;
+  void add(const void* base, size_t stride) { c[count++] = {base, stride}; }
+};
+template <class F>
+struct Entry {
+  F* fn;
+  const char* name;
+};
+#define DUSK_SCHNORR_ENTRY(member, f) static constexpr Entry<decltype(f)> member = {&f, #f}
+template <class Key>
+struct SchemeTraits;
+template <>
+struct SchemeTraits<PublicKey> {
+  using Sig = Signature;
+  static constexpr int scheme = 0;
+  DUSK_SCHNORR_ENTRY(verify, dsv_verify_single_mont_cols);
+  DUSK_SCHNORR_ENTRY(rlc, dsv_verify_single_mont_cols_rlc);
+  DUSK_SCHNORR_ENTRY(submit, dsv_verify_single_mont_cols_submit);
+  static void sig_cols(const Signature* s, Columns& c) { c.add(&s->u_, sizeof *s), c.add(&s->R_, sizeof *s); }
+  static void key_cols(const PublicKey* k, Columns& c) { c.add(&k->pk, sizeof *k); }
+};
+template <>
+struct SchemeTraits<PublicKeyDouble> {
+  using Sig = SignatureDouble;
+  static constexpr int scheme = 1;
+  DUSK_SCHNORR_ENTRY(verify, dsv_verify_double_mont_cols);
+  DUSK_SCHNORR_ENTRY(rlc, dsv_verify_double_mont_cols_rlc);
+  DUSK_SCHNORR_ENTRY(submit, dsv_verify_double_mont_cols_submit);
+  static void sig_cols(const SignatureDouble* s, Columns& c) {
+    c.add(&s->u_, sizeof *s), c.add(&s->R_, sizeof *s), c.add(&s->R_prime_, sizeof *s);
+  }
+  static void key_cols(const PublicKeyDouble* k, Columns& c) {
+    c.add(&k->pk_, sizeof *k), c.add(&k->pk_prime_, sizeof *k);
+  }
+};
+template <>
+struct SchemeTraits<PublicKeyVarGen> {
+  using Sig = SignatureVarGen;
+  static constexpr int scheme = 2;
+  DUSK_SCHNORR_ENTRY(verify, dsv_verify_vargen_mont_cols);
+  DUSK_SCHNORR_ENTRY(rlc, dsv_verify_vargen_mont_cols_rlc);
+  DUSK_SCHNORR_ENTRY(submit, dsv_verify_vargen_mont_cols_submit);
+  static void sig_cols(const SignatureVarGen* s, Columns& c) { c.add(&s->u_, sizeof *s), c.add(&s->R_, sizeof *s); }
+  static void key_cols(const PublicKeyVarGen* k, Columns& c) {
+    c.add(&k->pk_, sizeof *k), c.add(&k->generator_, sizeof *k);
+  }
+};
+#undef DUSK_SCHNORR_ENTRY
+template <class Key>
+using SigOf = typename SchemeTraits<Key>::Sig;
+
+// u, R[, R'], PK[, PK' | Gen], m: the columns of dsv_verify_*_mont_cols[_rlc|_submit] and of the key sets' open forms
+template <class Key>
+Columns open_columns(const SigOf<Key>* sigs, const Key* pks, const BlsScalar* msgs) {
+  Columns cols;
+  SchemeTraits<Key>::sig_cols(sigs, cols);
+  SchemeTraits<Key>::key_cols(pks, cols);
+  cols.add(msgs, sizeof *msgs);
+  return cols;
+}
+// u, R[, R'], idx, m: the columns of dsv_verify_keyed_mont_cols[_submit]
+template <class Key>
+Columns keyed_columns(const SigOf<Key>* sigs, const uint32_t* idx, const BlsScalar* msgs) {
+  Columns cols;
+  SchemeTraits<Key>::sig_cols(sigs, cols);
+  cols.add(idx, sizeof *idx);
+  cols.add(msgs, sizeof *msgs);
+  return cols;
+}
+
+// One body per form of (sigs, pks, msgs, n).  Blocking: the verdict bytes into ok[0 .. n)
+template <class Key>
+void verify_into(const SigOf<Key>* sigs, const Key* pks, const BlsScalar* msgs, size_t n, uint8_t* ok) {
+  using T = SchemeTraits<Key>;
+  ensure_init();
+  if (n) check(T::verify.fn(open_columns(sigs, pks, msgs).c, n, ok), T::verify.name);
+}
+template <class Key>
+std::vector<uint8_t> verify_bytes(const SigOf<Key>* sigs, const Key* pks, const BlsScalar* msgs, size_t n) {
+  std::vector<uint8_t> ok(n);
+  verify_into(sigs, pks, msgs, n, ok.data());
+  return ok;
+}
+template <class Key, class Sig>
+bool verify_one(const Key& pk, const Sig& sig, const BlsScalar& message) {  // no allocation: a stack byte
+  uint8_t ok = 0;
+  verify_into(&sig, &pk, &message, 1, &ok);
+  return ok == 1;
+}
+// Fast accept: the same bytes; *accepted (may be null) = the aggregate decided
+template <class Key>
+std::vector<uint8_t> fast_bytes(const SigOf<Key>* sigs, const Key* pks, const BlsScalar* msgs, size_t n, bool* accepted) {
+  using T = SchemeTraits<Key>;
+  ensure_init();
+  std::vector<uint8_t> ok(n);
+  int acc = 0;
+  if (n) check(T::rlc.fn(open_columns(sigs, pks, msgs).c, n, ok.data(), &acc), T::rlc.name);
+  if (accepted) *accepted = acc == 1;
+  return ok;
+}
+}  // namespace detail
 
 // ---- the new batch entry points (north_star): out[i] == pks[i].verify(sigs[i], msgs[i]) --------
 // No copy and no arithmetic here: the engine reads u / R / pk / m out of the typed objects through
@@ -569,32 +665,15 @@ static_assert(sizeof(PublicKey) == 160 && sizeof(PublicKeyDouble) == 320 && size
 // the std::vector<bool> packing pass.
 inline std::vector<uint8_t> verify_batch_bytes(const Signature* sigs, const PublicKey* pks,
                                                const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  if (!n) return ok;
-  const dsv_column cols[4] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk, sizeof *pks}, {msgs, 32}};
-  detail::check(dsv_verify_single_mont_cols(cols, n, ok.data()), "dsv_verify_single_mont_cols");
-  return ok;
+  return detail::verify_bytes(sigs, pks, msgs, n);
 }
 inline std::vector<uint8_t> verify_batch_double_bytes(const SignatureDouble* sigs, const PublicKeyDouble* pks,
                                                       const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  if (!n) return ok;
-  const dsv_column cols[6] = {{&sigs->u_, sizeof *sigs},  {&sigs->R_, sizeof *sigs},       {&sigs->R_prime_, sizeof *sigs},
-                              {&pks->pk_, sizeof *pks},   {&pks->pk_prime_, sizeof *pks},  {msgs, 32}};
-  detail::check(dsv_verify_double_mont_cols(cols, n, ok.data()), "dsv_verify_double_mont_cols");
-  return ok;
+  return detail::verify_bytes(sigs, pks, msgs, n);
 }
 inline std::vector<uint8_t> verify_batch_var_gen_bytes(const SignatureVarGen* sigs, const PublicKeyVarGen* pks,
                                                        const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  if (!n) return ok;
-  const dsv_column cols[5] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk_, sizeof *pks},
-                              {&pks->generator_, sizeof *pks}, {msgs, 32}};
-  detail::check(dsv_verify_vargen_mont_cols(cols, n, ok.data()), "dsv_verify_vargen_mont_cols");
-  return ok;
+  return detail::verify_bytes(sigs, pks, msgs, n);
 }
 namespace detail {
 // verdict bytes -> std::vector<bool> (true iff the byte is 1).  The element-wise loop costs ~2 ms per
@@ -656,41 +735,15 @@ inline std::vector<bool> verify_batch_var_gen(const std::vector<SignatureVarGen>
 // wrong accept <= 2^-112 (weights from getrandom, fresh per call); verify_batch* has none.
 inline std::vector<uint8_t> verify_batch_fast_bytes(const Signature* sigs, const PublicKey* pks,
                                                     const BlsScalar* msgs, size_t n, bool* accepted = nullptr) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  int acc = 0;
-  if (n) {
-    const dsv_column cols[4] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk, sizeof *pks}, {msgs, 32}};
-    detail::check(dsv_verify_single_mont_cols_rlc(cols, n, ok.data(), &acc), "dsv_verify_single_mont_cols_rlc");
-  }
-  if (accepted) *accepted = acc == 1;
-  return ok;
+  return detail::fast_bytes(sigs, pks, msgs, n, accepted);
 }
 inline std::vector<uint8_t> verify_batch_double_fast_bytes(const SignatureDouble* sigs, const PublicKeyDouble* pks,
                                                            const BlsScalar* msgs, size_t n, bool* accepted = nullptr) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  int acc = 0;
-  if (n) {
-    const dsv_column cols[6] = {{&sigs->u_, sizeof *sigs},  {&sigs->R_, sizeof *sigs},       {&sigs->R_prime_, sizeof *sigs},
-                                {&pks->pk_, sizeof *pks},   {&pks->pk_prime_, sizeof *pks},  {msgs, 32}};
-    detail::check(dsv_verify_double_mont_cols_rlc(cols, n, ok.data(), &acc), "dsv_verify_double_mont_cols_rlc");
-  }
-  if (accepted) *accepted = acc == 1;
-  return ok;
+  return detail::fast_bytes(sigs, pks, msgs, n, accepted);
 }
 inline std::vector<uint8_t> verify_batch_var_gen_fast_bytes(const SignatureVarGen* sigs, const PublicKeyVarGen* pks,
                                                             const BlsScalar* msgs, size_t n, bool* accepted = nullptr) {
-  detail::ensure_init();
-  std::vector<uint8_t> ok(n);
-  int acc = 0;
-  if (n) {
-    const dsv_column cols[5] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk_, sizeof *pks},
-                                {&pks->generator_, sizeof *pks}, {msgs, 32}};
-    detail::check(dsv_verify_vargen_mont_cols_rlc(cols, n, ok.data(), &acc), "dsv_verify_vargen_mont_cols_rlc");
-  }
-  if (accepted) *accepted = acc == 1;
-  return ok;
+  return detail::fast_bytes(sigs, pks, msgs, n, accepted);
 }
 inline std::vector<bool> verify_batch_fast(const std::vector<Signature>& sigs, const std::vector<PublicKey>& pks,
                                            const std::vector<BlsScalar>& msgs, bool* accepted = nullptr) {
@@ -715,8 +768,11 @@ inline std::vector<bool> verify_batch_var_gen_fast(const std::vector<SignatureVa
 // (gathering and transferring its first chunk, small first sub-batches) runs while the first one's
 // last chunks are on the GPU (dsv.h: dsv_verify_*_mont_cols_submit).  The typed objects must outlive
 // the wait; a BatchJob that is dropped waits in its destructor.
-template <class Key>
-class BasicKeySet;
+class BatchJob;
+namespace detail {
+template <class Start>
+BatchJob submit_job(size_t n, const char* what, Start start);  // (defined below the class)
+}
 class BatchJob {
  public:
   BatchJob() = default;
@@ -745,11 +801,8 @@ class BatchJob {
   std::vector<bool> wait() { return detail::to_bools(wait_bytes()); }
 
  private:
-  friend BatchJob verify_batch_submit(const Signature*, const PublicKey*, const BlsScalar*, size_t);
-  friend BatchJob verify_batch_double_submit(const SignatureDouble*, const PublicKeyDouble*, const BlsScalar*, size_t);
-  friend BatchJob verify_batch_var_gen_submit(const SignatureVarGen*, const PublicKeyVarGen*, const BlsScalar*, size_t);
-  template <class Key>
-  friend class BasicKeySet;
+  template <class Start>
+  friend BatchJob detail::submit_job(size_t n, const char* what, Start start);
   void drop() noexcept {
     if (job_) (void)dsv_job_wait(job_);
     job_ = nullptr;
@@ -757,36 +810,34 @@ class BatchJob {
   dsv_job* job_ = nullptr;
   std::vector<uint8_t> ok_;
 };
-inline BatchJob verify_batch_submit(const Signature* sigs, const PublicKey* pks, const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
+namespace detail {
+// The one place a BatchJob is filled: start(ok, &job) hands n > 0 items to one of the engine's *_submit calls
+template <class Start>
+BatchJob submit_job(size_t n, const char* what, Start start) {
   BatchJob j;
   j.ok_.assign(n, 0);
-  if (!n) return j;
-  const dsv_column cols[4] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk, sizeof *pks}, {msgs, 32}};
-  detail::check(dsv_verify_single_mont_cols_submit(cols, n, j.ok_.data(), &j.job_), "dsv_verify_single_mont_cols_submit");
+  if (n) check(start(j.ok_.data(), &j.job_), what);
   return j;
+}
+template <class Key>
+BatchJob submit(const SigOf<Key>* sigs, const Key* pks, const BlsScalar* msgs, size_t n) {
+  using T = SchemeTraits<Key>;
+  ensure_init();
+  return submit_job(n, T::submit.name, [&](uint8_t* ok, dsv_job** job) {
+    return T::submit.fn(open_columns(sigs, pks, msgs).c, n, ok, job);
+  });
+}
+}  // namespace detail
+inline BatchJob verify_batch_submit(const Signature* sigs, const PublicKey* pks, const BlsScalar* msgs, size_t n) {
+  return detail::submit(sigs, pks, msgs, n);
 }
 inline BatchJob verify_batch_double_submit(const SignatureDouble* sigs, const PublicKeyDouble* pks,
                                            const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
-  BatchJob j;
-  j.ok_.assign(n, 0);
-  if (!n) return j;
-  const dsv_column cols[6] = {{&sigs->u_, sizeof *sigs},  {&sigs->R_, sizeof *sigs},       {&sigs->R_prime_, sizeof *sigs},
-                              {&pks->pk_, sizeof *pks},   {&pks->pk_prime_, sizeof *pks},  {msgs, 32}};
-  detail::check(dsv_verify_double_mont_cols_submit(cols, n, j.ok_.data(), &j.job_), "dsv_verify_double_mont_cols_submit");
-  return j;
+  return detail::submit(sigs, pks, msgs, n);
 }
 inline BatchJob verify_batch_var_gen_submit(const SignatureVarGen* sigs, const PublicKeyVarGen* pks,
                                             const BlsScalar* msgs, size_t n) {
-  detail::ensure_init();
-  BatchJob j;
-  j.ok_.assign(n, 0);
-  if (!n) return j;
-  const dsv_column cols[5] = {{&sigs->u_, sizeof *sigs}, {&sigs->R_, sizeof *sigs}, {&pks->pk_, sizeof *pks},
-                              {&pks->generator_, sizeof *pks}, {msgs, 32}};
-  detail::check(dsv_verify_vargen_mont_cols_submit(cols, n, j.ok_.data(), &j.job_), "dsv_verify_vargen_mont_cols_submit");
-  return j;
+  return detail::submit(sigs, pks, msgs, n);
 }
 inline BatchJob verify_batch_submit(const std::vector<Signature>& sigs, const std::vector<PublicKey>& pks,
                                     const std::vector<BlsScalar>& msgs) {
@@ -817,56 +868,17 @@ inline BatchJob verify_batch_var_gen_submit(const std::vector<SignatureVarGen>& 
 // construction.  `KeySet keys(pks, capacity);` reserves room for `capacity` keys, and `keys.append(more)` then
 // registers further keys in place (dsv_keyset_append_mont_cols): it returns the index of the first of them, no
 // registered key moves, and batches submitted before the append returned keep the set they were submitted with.
-namespace detail {
-template <class Key>
-struct KeyedTraits;
-template <>
-struct KeyedTraits<PublicKey> {
-  using Sig = Signature;
-  static constexpr int scheme = 0;
-  static void key_cols(const PublicKey* k, dsv_column* c) { c[0] = {&k->pk, sizeof *k}; }
-  static int sig_cols(const Signature* s, dsv_column* c) {
-    c[0] = {&s->u_, sizeof *s}, c[1] = {&s->R_, sizeof *s};
-    return 2;
-  }
-};
-template <>
-struct KeyedTraits<PublicKeyDouble> {
-  using Sig = SignatureDouble;
-  static constexpr int scheme = 1;
-  static void key_cols(const PublicKeyDouble* k, dsv_column* c) {
-    c[0] = {&k->pk_, sizeof *k}, c[1] = {&k->pk_prime_, sizeof *k};
-  }
-  static int sig_cols(const SignatureDouble* s, dsv_column* c) {
-    c[0] = {&s->u_, sizeof *s}, c[1] = {&s->R_, sizeof *s}, c[2] = {&s->R_prime_, sizeof *s};
-    return 3;
-  }
-};
-template <>
-struct KeyedTraits<PublicKeyVarGen> {
-  using Sig = SignatureVarGen;
-  static constexpr int scheme = 2;
-  static void key_cols(const PublicKeyVarGen* k, dsv_column* c) {
-    c[0] = {&k->pk_, sizeof *k}, c[1] = {&k->generator_, sizeof *k};
-  }
-  static int sig_cols(const SignatureVarGen* s, dsv_column* c) {
-    c[0] = {&s->u_, sizeof *s}, c[1] = {&s->R_, sizeof *s};
-    return 2;
-  }
-};
-}  // namespace detail
-
 template <class Key>
 class BasicKeySet {
-  using T = detail::KeyedTraits<Key>;
+  using T = detail::SchemeTraits<Key>;
 
  public:
   using Sig = typename T::Sig;
   explicit BasicKeySet(const std::vector<Key>& keys) {
     detail::ensure_init();
-    dsv_column cols[2] = {};
+    detail::Columns cols{};
     if (!keys.empty()) T::key_cols(keys.data(), cols);
-    detail::check(dsv_keyset_create_mont_cols(T::scheme, cols, keys.size(), &ks_), "dsv_keyset_create_mont_cols");
+    detail::check(dsv_keyset_create_mont_cols(T::scheme, cols.c, keys.size(), &ks_), "dsv_keyset_create_mont_cols");
   }
   // room for `capacity` >= keys.size() keys: append() registers the others later, in place
   BasicKeySet(const std::vector<Key>& keys, size_t capacity) {
@@ -906,10 +918,10 @@ class BasicKeySet {
   // registers `keys` behind the ones the set holds and returns the index of the first of them (size() before the
   // call); throws when the set has no room for them, and the set is then unchanged.  Blocks.
   uint32_t append(const std::vector<Key>& keys) {
-    dsv_column cols[2] = {};
+    detail::Columns cols{};
     if (!keys.empty()) T::key_cols(keys.data(), cols);
     uint32_t first = 0;
-    detail::check(dsv_keyset_append_mont_cols(ks_, cols, keys.size(), &first), "dsv_keyset_append_mont_cols");
+    detail::check(dsv_keyset_append_mont_cols(ks_, cols.c, keys.size(), &first), "dsv_keyset_append_mont_cols");
     return first;
   }
   // per key: 1 = usable; 0 = a coordinate the Rust types cannot hold, z = 0 or a point off the curve
@@ -924,10 +936,8 @@ class BasicKeySet {
   // the engine's verdict bytes (1 = true); idx[i]: the key of item i
   std::vector<uint8_t> verify_batch_bytes(const Sig* sigs, const uint32_t* idx, const BlsScalar* msgs, size_t n) const {
     std::vector<uint8_t> ok(n);
-    if (!n) return ok;
-    dsv_column cols[5];
-    columns(sigs, idx, msgs, cols);
-    detail::check(dsv_verify_keyed_mont_cols(ks_, cols, n, ok.data()), "dsv_verify_keyed_mont_cols");
+    if (n) detail::check(dsv_verify_keyed_mont_cols(ks_, detail::keyed_columns<Key>(sigs, idx, msgs).c, n, ok.data()),
+                         "dsv_verify_keyed_mont_cols");
     return ok;
   }
   std::vector<bool> verify_batch(const std::vector<Sig>& sigs, const std::vector<uint32_t>& idx,
@@ -938,14 +948,9 @@ class BasicKeySet {
   // returns at once; `wait()` gives what verify_batch would have.  The objects and idx must outlive the wait;
   // destroying the set waits for the job
   BatchJob verify_batch_submit(const Sig* sigs, const uint32_t* idx, const BlsScalar* msgs, size_t n) const {
-    BatchJob j;
-    j.ok_.assign(n, 0);
-    if (!n) return j;
-    dsv_column cols[5];
-    columns(sigs, idx, msgs, cols);
-    detail::check(dsv_verify_keyed_mont_cols_submit(ks_, cols, n, j.ok_.data(), &j.job_),
-                  "dsv_verify_keyed_mont_cols_submit");
-    return j;
+    return detail::submit_job(n, "dsv_verify_keyed_mont_cols_submit", [&](uint8_t* ok, dsv_job** job) {
+      return dsv_verify_keyed_mont_cols_submit(ks_, detail::keyed_columns<Key>(sigs, idx, msgs).c, n, ok, job);
+    });
   }
   BatchJob verify_batch_submit(const std::vector<Sig>& sigs, const std::vector<uint32_t>& idx,
                                const std::vector<BlsScalar>& msgs) const {
@@ -960,10 +965,8 @@ class BasicKeySet {
                                                size_t* misses = nullptr) const {
     std::vector<uint8_t> ok(n);
     if (misses) *misses = 0;
-    if (!n) return ok;
-    dsv_column cols[6];
-    open_columns(sigs, pks, msgs, cols);
-    detail::check(dsv_verify_keyed_open_mont_cols(ks_, cols, n, ok.data(), misses), "dsv_verify_keyed_open_mont_cols");
+    if (n) detail::check(dsv_verify_keyed_open_mont_cols(ks_, detail::open_columns(sigs, pks, msgs).c, n, ok.data(),
+                                                         misses), "dsv_verify_keyed_open_mont_cols");
     return ok;
   }
   std::vector<bool> verify_batch_open(const std::vector<Sig>& sigs, const std::vector<Key>& pks,
@@ -974,14 +977,9 @@ class BasicKeySet {
   // returns at once; `wait()` gives what verify_batch_open would have (no miss count).  The objects must outlive the
   // wait; destroying the set waits for the job
   BatchJob verify_batch_open_submit(const Sig* sigs, const Key* pks, const BlsScalar* msgs, size_t n) const {
-    BatchJob j;
-    j.ok_.assign(n, 0);
-    if (!n) return j;
-    dsv_column cols[6];
-    open_columns(sigs, pks, msgs, cols);
-    detail::check(dsv_verify_keyed_open_mont_cols_submit(ks_, cols, n, j.ok_.data(), &j.job_),
-                  "dsv_verify_keyed_open_mont_cols_submit");
-    return j;
+    return detail::submit_job(n, "dsv_verify_keyed_open_mont_cols_submit", [&](uint8_t* ok, dsv_job** job) {
+      return dsv_verify_keyed_open_mont_cols_submit(ks_, detail::open_columns(sigs, pks, msgs).c, n, ok, job);
+    });
   }
   BatchJob verify_batch_open_submit(const std::vector<Sig>& sigs, const std::vector<Key>& pks,
                                     const std::vector<BlsScalar>& msgs) const {
@@ -990,17 +988,6 @@ class BasicKeySet {
   }
 
  private:
-  // u, R[, R'], PK[, PK' | Gen], m: the columns of dsv_verify_*_mont_cols
-  static void open_columns(const Sig* sigs, const Key* pks, const BlsScalar* msgs, dsv_column* cols) {
-    const int c = T::sig_cols(sigs, cols);
-    T::key_cols(pks, cols + c);
-    cols[c + (T::scheme == 0 ? 1 : 2)] = {msgs, 32};
-  }
-  static void columns(const Sig* sigs, const uint32_t* idx, const BlsScalar* msgs, dsv_column* cols) {
-    const int c = T::sig_cols(sigs, cols);
-    cols[c] = {idx, sizeof(uint32_t)};
-    cols[c + 1] = {msgs, 32};
-  }
   void drop() noexcept {
     if (ks_) (void)dsv_keyset_destroy(ks_);
     ks_ = nullptr;

@@ -2,24 +2,11 @@
 // reference's in-memory representation: Montgomery limbs, R = 2^256) for tests/test_cpp_mirror.py,
 // which re-computes every line with Python integers.  No GPU call is made.
 //   <field> <a> <b> <a*b> <a+b> <a-b> <-a> <1/a> <from_bytes_wide(w)> <limbs of a>      (hex, canonical LE)
-#include <cstdio>
-
 #include "dusk_schnorr.hpp"
+#include "support.hpp"
 
 using namespace dusk_schnorr;
 
-struct Rng {
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  void operator()(uint8_t* out, size_t n) {
-    for (size_t i = 0; i < n; i++) out[i] = (uint8_t)(next() >> 32);
-  }
-};
 static void hex(const uint8_t* b, size_t n) {
   for (size_t i = 0; i < n; i++) std::printf("%02x", b[i]);
   std::printf(" ");

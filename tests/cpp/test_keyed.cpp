@@ -2,35 +2,10 @@
 // of the reference's native tests (tests/schnorr.rs, schnorr_double.rs, schnorr_var_generator.rs: sign_verify,
 // test_wrong_keys) with few keys signing many messages.  Every verdict of KeySet*::verify_batch is compared
 // bool for bool with the per-object `PublicKey*::verify` of the key the index names.  Exit code 0 = all passed.
-#include <cstdio>
-#include <cstdlib>
-
 #include "dusk_schnorr.hpp"
+#include "support.hpp"
 
 using namespace dusk_schnorr;
-
-// deterministic test RNG (splitmix64); the reference uses StdRng::seed_from_u64(2321)
-struct Rng {
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed) {}
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  void operator()(uint8_t* out, size_t n) {
-    for (size_t i = 0; i < n; i++) out[i] = (uint8_t)(next() >> 32);
-  }
-};
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
 
 constexpr size_t kKeys = 5, kItems = 240;
 

@@ -2,36 +2,12 @@
 // exactly the arguments of the free verify_batch* — (signature, public key, message) triples, most under registered
 // keys, some under keys the set has never seen, some tampered.  Every verdict is compared bool for bool with the
 // free verify_batch* on the same objects; the miss count is what the batch was built with.  Exit code 0 = all passed.
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "dusk_schnorr.hpp"
+#include "support.hpp"
 
 using namespace dusk_schnorr;
-
-// deterministic test RNG (splitmix64); the reference uses StdRng::seed_from_u64(2321)
-struct Rng {
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed) {}
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  void operator()(uint8_t* out, size_t n) {
-    for (size_t i = 0; i < n; i++) out[i] = (uint8_t)(next() >> 32);
-  }
-};
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
 
 constexpr size_t kKeys = 7, kRegistered = 5, kItems = 240;
 

@@ -5,35 +5,10 @@
 //   to_from_bytes of all three (tests/schnorr.rs:42-51, schnorr_double.rs:43-52,
 //   schnorr_var_generator.rs:43-52) and of the key types, with the Err cases
 // plus the new verify_batch entry points.  Exit code 0 = all passed.
-#include <cstdio>
-#include <cstdlib>
-
 #include "dusk_schnorr.hpp"
+#include "support.hpp"
 
 using namespace dusk_schnorr;
-
-// deterministic test RNG (splitmix64); the reference uses StdRng::seed_from_u64(2321)
-struct Rng {
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed) {}
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  void operator()(uint8_t* out, size_t n) {
-    for (size_t i = 0; i < n; i++) out[i] = (uint8_t)(next() >> 32);
-  }
-};
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
 
 static void sign_verify() {
   Rng rng(2321);
@@ -126,6 +101,82 @@ static void batch() {
   CHECK(threw);
   CHECK(verify_batch({}, {}, {}).empty());
 }
+// what() of the exception of type E that f throws; empty if it throws nothing
+template <class E, class F>
+static std::string thrown(F f) {
+  try {
+    f();
+  } catch (const E& e) {
+    return e.what();
+  }
+  return "";
+}
+// The forms of the double and var-generator schemes nothing above goes through, over the tampered batches of
+// batch_double_vargen_and_chunks (okd / okv: their verify_batch_double / verify_batch_var_gen verdicts), and the two
+// ways every form of every scheme fails: slices of unequal length, and an error of the engine itself
+static void submit_forms_and_errors(const std::vector<SignatureDouble>& dsigs, const std::vector<PublicKeyDouble>& dpks,
+                                    const std::vector<SignatureVarGen>& vsigs, const std::vector<PublicKeyVarGen>& vpks,
+                                    const std::vector<Signature>& sigs, const std::vector<PublicKey>& pks,
+                                    const std::vector<BlsScalar>& msgs, const std::vector<bool>& okd,
+                                    const std::vector<bool>& okv) {
+  const size_t n = msgs.size();
+  CHECK(verify_batch_double_submit(dsigs, dpks, msgs).wait() == okd);
+  CHECK(verify_batch_var_gen_submit(vsigs, vpks, msgs).wait() == okv);
+  const std::vector<uint8_t> bd = verify_batch_double_bytes(dsigs.data(), dpks.data(), msgs.data(), n);
+  const std::vector<uint8_t> bv = verify_batch_var_gen_bytes(vsigs.data(), vpks.data(), msgs.data(), n);
+  for (size_t i = 0; i < n; i++) CHECK(bd[i] == (okd[i] ? 1 : 0) && bv[i] == (okv[i] ? 1 : 0));
+  CHECK(verify_batch_double_submit(dsigs.data(), dpks.data(), msgs.data(), n).wait_bytes() == bd);
+  CHECK(verify_batch_var_gen_submit(vsigs.data(), vpks.data(), msgs.data(), n).wait_bytes() == bv);
+  // an empty submit: a finished job, an empty vector
+  BatchJob empty = verify_batch_submit(std::vector<Signature>{}, {}, {});
+  CHECK(empty.done() && empty.wait().empty());
+  CHECK(verify_batch_double_submit(std::vector<SignatureDouble>{}, {}, {}).wait().empty());
+  CHECK(verify_batch_var_gen_submit(std::vector<SignatureVarGen>{}, {}, {}).wait().empty());
+  CHECK(verify_batch_double_submit(nullptr, nullptr, nullptr, 0).wait_bytes().empty());
+  CHECK(verify_batch_var_gen_submit(nullptr, nullptr, nullptr, 0).wait_bytes().empty());
+
+  // slices of unequal length: each of the nine vector overloads throws std::invalid_argument under its own name
+  const std::vector<BlsScalar> fewer(msgs.begin(), msgs.end() - 1);
+  using IA = std::invalid_argument;
+  CHECK(thrown<IA>([&] { verify_batch(sigs, pks, fewer); }) == "verify_batch: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_double(dsigs, dpks, fewer); }) == "verify_batch_double: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_var_gen(vsigs, vpks, fewer); }) == "verify_batch_var_gen: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_fast(sigs, pks, fewer); }) == "verify_batch_fast: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_double_fast(dsigs, dpks, fewer); }) == "verify_batch_double_fast: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_var_gen_fast(vsigs, vpks, fewer); }) ==
+        "verify_batch_var_gen_fast: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_submit(sigs, pks, fewer); }) == "verify_batch_submit: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_double_submit(dsigs, dpks, fewer); }) ==
+        "verify_batch_double_submit: slice lengths differ");
+  CHECK(thrown<IA>([&] { verify_batch_var_gen_submit(vsigs, vpks, fewer); }) ==
+        "verify_batch_var_gen_submit: slice lengths differ");
+
+  // an error of the engine is no verdict: a null message column with n = 1, which the C API turns down before it
+  // touches the device, is a std::runtime_error that names the C function of that scheme and form
+  using RE = std::runtime_error;
+  const BlsScalar* none = nullptr;
+  auto names = [](const std::string& what, const char* fn) {
+    return what.rfind(std::string(fn) + ": dsv error ", 0) == 0 && what.find("column") != std::string::npos;
+  };
+  bool accepted = true;
+  CHECK(names(thrown<RE>([&] { verify_batch_bytes(sigs.data(), pks.data(), none, 1); }), "dsv_verify_single_mont_cols"));
+  CHECK(names(thrown<RE>([&] { verify_batch_double_bytes(dsigs.data(), dpks.data(), none, 1); }),
+              "dsv_verify_double_mont_cols"));
+  CHECK(names(thrown<RE>([&] { verify_batch_var_gen_bytes(vsigs.data(), vpks.data(), none, 1); }),
+              "dsv_verify_vargen_mont_cols"));
+  CHECK(names(thrown<RE>([&] { verify_batch_fast_bytes(sigs.data(), pks.data(), none, 1, &accepted); }),
+              "dsv_verify_single_mont_cols_rlc"));
+  CHECK(names(thrown<RE>([&] { verify_batch_double_fast_bytes(dsigs.data(), dpks.data(), none, 1, &accepted); }),
+              "dsv_verify_double_mont_cols_rlc"));
+  CHECK(names(thrown<RE>([&] { verify_batch_var_gen_fast_bytes(vsigs.data(), vpks.data(), none, 1, &accepted); }),
+              "dsv_verify_vargen_mont_cols_rlc"));
+  CHECK(names(thrown<RE>([&] { verify_batch_submit(sigs.data(), pks.data(), none, 1); }),
+              "dsv_verify_single_mont_cols_submit"));
+  CHECK(names(thrown<RE>([&] { verify_batch_double_submit(dsigs.data(), dpks.data(), none, 1); }),
+              "dsv_verify_double_mont_cols_submit"));
+  CHECK(names(thrown<RE>([&] { verify_batch_var_gen_submit(vsigs.data(), vpks.data(), none, 1); }),
+              "dsv_verify_vargen_mont_cols_submit"));
+}
 // verify_batch_double / verify_batch_var_gen over typed objects (six and five strided columns), and a
 // batch long enough for several pipeline chunks (the objects of a small signed set repeated)
 static void batch_double_vargen_and_chunks() {
@@ -159,6 +210,7 @@ static void batch_double_vargen_and_chunks() {
     CHECK(okd[i] == !(i == 5 || i == 11) && okd[i] == dpks[i].verify(dsigs[i], msgs[i]));
     CHECK(okv[i] == !(i == 7 || i == 20) && okv[i] == vpks[i].verify(vsigs[i], msgs[i]));
   }
+  submit_forms_and_errors(dsigs, dpks, vsigs, vpks, sigs, pks, msgs, okd, okv);
   // 70 020 single signatures: two chunks and a ragged sub-batch through the strided gather
   sigs[3].R_ = sigs[4].R_;
   const size_t reps = 1167;

@@ -6,27 +6,15 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "test_keyed.cpp")
-EXE = os.path.join(ROOT, "tests", "cpp", "test_keyed")
-
-
-def _compile():
-    from schnorr_amd import _lib
-    _lib.load()
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", EXE, SRC,
-           "-L", os.path.join(ROOT, "schnorr_amd"), "-ldsv", "-Wl,-rpath," + os.path.join(ROOT, "schnorr_amd")]
-    subprocess.check_call(cmd)
+from cpp_build import compile_program
 
 
 def test_cpp_keyed_compiles():
-    _compile()
-    assert os.path.exists(EXE)
+    assert os.path.exists(compile_program("test_keyed"))
 
 
 @pytest.mark.gpu
 def test_cpp_keyed_matches_per_object_verify_on_gpu():
-    _compile()
-    out = subprocess.run([EXE], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([compile_program("test_keyed")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("ok:")

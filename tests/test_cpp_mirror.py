@@ -6,23 +6,20 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "test_schnorr.cpp")
-EXE = os.path.join(ROOT, "tests", "cpp", "test_schnorr")
-
-
-def _compile():
-    from schnorr_amd import _lib
-    _lib.load()
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", EXE, SRC,
-           "-L", os.path.join(ROOT, "schnorr_amd"), "-ldsv",
-           "-Wl,-rpath," + os.path.join(ROOT, "schnorr_amd")]
-    subprocess.check_call(cmd)
+from cpp_build import compile_program
 
 
 def test_cpp_mirror_compiles():
-    _compile()
-    assert os.path.exists(EXE)
+    assert os.path.exists(compile_program("test_schnorr"))
+
+
+def test_cpp_mirror_column_layout():
+    """The header reads every argument of verify / verify_batch* / KeySet* through two column builders over one
+    field list per scheme: tests/cpp/column_layout.cpp checks count, order, base and stride of both for the three
+    schemes.  Runs without a GPU: the program makes no engine call."""
+    out = subprocess.run([compile_program("column_layout")], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.strip() == "ok"
 
 
 def test_cpp_mirror_host_arithmetic_matches_python_integers():
@@ -31,13 +28,7 @@ def test_cpp_mirror_host_arithmetic_matches_python_integers():
     from_bytes_wide = lo R^2 + hi R^3, *, +, -, invert) is checked line by line against Python
     integers.  Runs without a GPU: the program makes no engine call."""
     import pymodel as M
-    from schnorr_amd import _lib
-    _lib.load()
-    exe = os.path.join(ROOT, "tests", "cpp", "field_vectors")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "field_vectors.cpp"),
-                           "-L", os.path.join(ROOT, "schnorr_amd"), "-ldsv",
-                           "-Wl,-rpath," + os.path.join(ROOT, "schnorr_amd")])
+    exe = compile_program("field_vectors")
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
     le = lambda h: int.from_bytes(bytes.fromhex(h), "little")
     seen = {"fq": 0, "fr": 0}
@@ -58,7 +49,6 @@ def test_cpp_mirror_host_arithmetic_matches_python_integers():
 
 @pytest.mark.gpu
 def test_cpp_mirror_reference_tests_pass_on_gpu():
-    _compile()
-    out = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
+    out = subprocess.run([compile_program("test_schnorr")], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("ok:")
