@@ -72,11 +72,8 @@ k_index_append(const uint8_t* __restrict__ P0, const uint8_t* __restrict__ P1, c
 }
 
 // ------------------------------------------------------------------------------------------
-// One lane per item, grid-stride: the item's row in registers, a walk from the home slot that compares against
-// the index's copy of each occupant's row and ends at the first empty slot.  k: the set's key count when the call
-// was enqueued.  An occupant >= k was appended since: it is read as an empty slot and ends the walk.  That is
-// exact: every key below k whose walk passes this slot was placed while the slot was still empty, so it sits in
-// front of it.
+// One lane per item, grid-stride: the item's row in registers and walk_index (keyed_lookup.h) from its home slot.
+// k: the set's key count when the call was enqueued.
 // ------------------------------------------------------------------------------------------
 template <class Form>
 __global__ void __launch_bounds__(kLookupBlock)
@@ -91,19 +88,7 @@ k_index_lookup(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ ke
 #pragma unroll 1
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const Words<W> w = Form::item(key_a, key_b, i);
-    size_t slot = home_hash<W>(w) & mask;
-    uint32_t found = kSlotEmpty;
-#pragma unroll 1
-    for (size_t probe = 0;; probe++) {
-      const uint32_t occ = slots[slot];
-      if (occ >= k) break;  // empty (kSlotEmpty >= k), or a key newer than this call
-      if (same_words<W>(w, load_row<W>(rows, occ))) {
-        found = occ;
-        break;
-      }
-      if (probe == mask) break;  // unreachable for the same reason: an empty slot ends the walk first
-      slot = (slot + 1) & mask;
-    }
+    const uint32_t found = walk_index<W>(w, rows, slots, mask, k);
     key_idx[i] = found;
     missed += found == kSlotEmpty ? 1u : 0u;
   }

@@ -30,79 +30,27 @@ k_miss_list(const u32* __restrict__ key_idx, size_t n, u32* __restrict__ list, u
 }
 
 // ------------------------------------------------------------------------------------------
-// The verdict of item i = list[base + lane]: valid[i] & [every chain's equation holds]; tbl: the lane's window table.  This is the
-// body of k_verify_fixed_half's loop (k_verify.hip, where the method is described), statement for statement, and
-// it is a COPY on purpose: with the body moved into a forced-inline function that both kernels call, the
-// compiled k_verify_fixed_half<1> and <2> came out with another register allocation (same budget, other
-// instruction text), and the headline kernel is not to change for this one.  A change to either
-// body belongs in both.
+// The verdict of item i = list[base + lane]: valid[i] & [every chain's equation holds]; tbl: the lane's window table.  The
+// body is k_verify_fixed_half's (k_verify.hip, where the method is described): one text, verify_half_item_body.h,
+// included by both.
 // ------------------------------------------------------------------------------------------
 template <int NCHAIN>
 DSV_DEV bool listed_item_ok(const uint8_t* u, const uint8_t* c, const ChainOperands& op0, const ChainOperands& op1,
                             const uint8_t* valid, size_t i, const JointTable& tbl,
                             const u32* list, size_t base) {
   bool good = valid[i] != 0;
-  u32 ya[8], yb[8], w[8];
-  bool b_neg;
-  int top;
-  {
-    u32 cs[8], a[8], b[8];
-    load_words8(cs, c, i);
-    half_scalars(a, b, b_neg, cs);
-    // signed 2-bit digits of a and |b| (the sign of the R term goes into the point: -R below)
-    recode_signed2(ya, a);
-    recode_signed2(yb, b);
-    u32 nz[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) nz[k] = (ya[k] ^ 0x55555555u) | (yb[k] ^ 0x55555555u);
-    top = top_digit2(nz);
-    u32 us[8];
-    load_words8(us, u, i);
-    const bool u_ok = words_lt(us, kR32);
-    good &= u_ok;
-    if (!u_ok) us[7] &= 0x0fffffffu;  // keep fr_mul's inputs below r-ish; verdict is 0 anyway
-    fr_mul(w, b, us);                 // |b| * u mod r
-    if (b_neg) {                      // (b*u) mod r with b < 0
-      const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      u32 t[8];
-      fr_sub(t, zero, w);
-#pragma unroll
-      for (int k = 0; k < 8; k++) w[k] = t[k];
-    }
-  }
-#pragma unroll 1
-  for (int h = 0; h < NCHAIN; h++) {
-    const ChainOperands op = h ? op1 : op0;
-    {
-      // The chain's points are addressed by the row read from the list AGAIN (as for the store of the verdict in
-      // k_verify_listed): the kernel this one mirrors rebuilds its row from the workgroup's base and the lane,
-      // here it would stay in a register — with the addresses made from it — across the first chain's window
-      // loop, and the two-chain kernel spilled more than k_verify_fixed_half<2> (tests/test_keyset_open_abi.py).
-      u32 lane = threadIdx.x;
-      asm volatile("" : "+v"(lane));
-      const size_t r = list[base + lane];
-      Fe pku, pkv, ru, rv;
-      good &= load_fq(pku, op.PK_uv, 2 * r);
-      good &= load_fq(pkv, op.PK_uv, 2 * r + 1);
-      good &= load_fq_signed(ru, op.R_uv, 2 * r, !b_neg);  // the chain adds -|b| * R unless b < 0
-      good &= load_fq(rv, op.R_uv, 2 * r + 1);
-      build_joint_table(tbl, pku, pkv, ru, rv);
-    }
-    // T = a*PK + |b|*(-+R) (+ w*G below): one joint entry per 2-bit window, loaded one window ahead
-    Ext acc = ext_from_niels(load_joint_entry(tbl, joint_digit(ya, yb, top)));
-    {
-      RawJoint e = load_joint_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
-#pragma unroll 1
-      for (int k = top - 1; k >= 0; k--) {
-        acc = ext_mul4(acc);
-        const Niels cur = finish_joint_entry(e);
-        e = load_joint_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
-        acc = ext_add_niels(acc, cur);
-      }
-    }
-    // T + w*G == O  (T == O  <=>  u == 0 and v == z, decided inside the last addition)
-    good &= fixed_base_accumulate_is_identity(acc, w, op.table);
-  }
+  // The chain's points are addressed by the row read from the list AGAIN (as for the store of the verdict in
+  // k_verify_listed): k_verify_fixed_half rebuilds its row from the workgroup's base and the lane, here it would
+  // stay in a register — with the addresses made from it — across the first chain's window loop, and the
+  // two-chain kernel spilled more than k_verify_fixed_half<2> (tests/test_keyset_open_abi.py).
+#define DSV_ITEM_ROW_SETUP       \
+  u32 lane = threadIdx.x;        \
+  asm volatile("" : "+v"(lane)); \
+  const size_t r = list[base + lane];
+#define DSV_ITEM_ROW r
+#include "verify_half_item_body.h"
+#undef DSV_ITEM_ROW
+#undef DSV_ITEM_ROW_SETUP
   return good;
 }
 

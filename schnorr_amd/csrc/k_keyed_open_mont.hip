@@ -7,71 +7,9 @@
 #include "keyed_open_mont.h"
 #include "common.h"
 #include "inv29.h"
+#include "normalize_items.h"
 
 namespace dsv {
-namespace {
-
-// ------------------------------------------------------------------------------------------
-// COPIES of k_misc.hip's load_z_for_product, kTwo5 and scalars_from_mont_item, on purpose ("One
-// body or two"; §10.9): k_misc.hip stays byte for byte what the typed forms were measured with.  A change to
-// either copy belongs in both.
-// ------------------------------------------------------------------------------------------
-DSV_DEV Fe load_z_for_product(const uint8_t* in, size_t i, bool& ok) {
-  u32 w[8];
-  load_words8(w, in, 3 * i + 2);
-  const bool usable = words_lt(w, kQ32) & ((w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0);
-  ok &= usable;
-  const Fe z = fe_to_mont(fe_from_words_plain(w));
-  return fe_select(usable, z, fe_one());
-}
-__device__ constexpr u32 kTwo5[NL] = {32, 0, 0, 0, 0, 0, 0, 0, 0};
-DSV_DEV void scalars_from_mont_item(const uint8_t* __restrict__ u_mont, const uint8_t* __restrict__ m_mont, size_t i,
-                                    uint8_t* __restrict__ u_out, uint8_t* __restrict__ m_out) {
-  u32 w[8], o[8];
-  load_words8(w, u_mont, i);
-  if (words_lt(w, kR32)) {
-    const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-    fr_mont_mul(o, w, one);
-    store_words8(u_out, i, o);
-  } else {
-    store_poison(u_out, i);
-  }
-  load_words8(w, m_mont, i);
-  if (words_lt(w, kQ32)) {
-    fe_to_words_plain(o, fe_canon(fe_mul(fe_from_words_plain(w), fe_const(kTwo5))));
-    store_words8(m_out, i, o);
-  } else {
-    store_poison(m_out, i);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// A COPY of k_index_lookup's walk (k_keyed_lookup.hip), for the same reason: the row of the item in registers, a
-// walk from its home slot that compares against the index's copy of each occupant's row and ends at the first
-// empty slot; an occupant >= k was appended since the call was enqueued and is read as an empty slot.  k = 0: the
-// set has no index, nothing is read.
-// ------------------------------------------------------------------------------------------
-template <int W>
-DSV_DEV uint32_t walk_index(const Words<W>& w, const uint8_t* __restrict__ rows, const uint32_t* __restrict__ slots,
-                            size_t mask, size_t k) {
-  uint32_t found = kSlotEmpty;
-  if (k == 0) return found;
-  size_t slot = home_hash<W>(w) & mask;
-#pragma unroll 1
-  for (size_t probe = 0;; probe++) {
-    const uint32_t occ = slots[slot];
-    if (occ >= k) break;  // empty (kSlotEmpty >= k), or a key newer than this call
-    if (same_words<W>(w, load_row<W>(rows, occ))) {
-      found = occ;
-      break;
-    }
-    if (probe == mask) break;  // unreachable: the table is at most half full, an empty slot ends the walk first
-    slot = (slot + 1) & mask;
-  }
-  return found;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------------------------------
 // k_normalize_uvz<NPS + NPK>'s lanes, per_lane, prefix layout and grid (k_misc.hip: Montgomery's trick over the
@@ -155,7 +93,8 @@ k_normalize_lookup(NormalizeArgs a, size_t n, size_t lanes, int per_lane, uint8_
       };
       if (NPK > 1) down_key(1);
       down_key(0);
-      const uint32_t found = key_ok ? walk_index<W>(row, rows, slots, mask, nkeys) : kSlotEmpty;
+      // (a set without an index has nkeys = 0 and no rows or slots: nothing is read)
+      const uint32_t found = key_ok && nkeys ? walk_index<W>(row, rows, slots, mask, nkeys) : kSlotEmpty;
       key_idx[i] = found;
       if (found == kSlotEmpty) {
         missed++;

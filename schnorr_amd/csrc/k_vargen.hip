@@ -30,66 +30,8 @@ k_verify_var(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c,
     const size_t i = base + threadIdx.x;
     if (i >= n) continue;
     bool good = valid[i] != 0;
-    u32 yx[8], yy[8], yz[8];
-    int sx, sy, sz, top;
-    {
-      u32 us[8], cs[8], mx[8], my[8], mz[8];
-      bool nx, ny, nz;
-      load_words8(us, u, i);
-      load_words8(cs, c, i);
-      good &= words_lt(us, kR32);
-      if (!words_lt(us, kR32)) us[7] &= 0x0fffffffu;  // keep the scalars in range; verdict is 0 anyway
-      lattice3_scalars(mx, my, mz, nx, ny, nz, us, cs);
-      recode_signed4(yx, mx);
-      recode_signed4(yy, my);
-      recode_signed4(yz, mz);
-      u32 nzd[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        nzd[k] = (yx[k] ^ 0x88888888u) | (yy[k] ^ 0x88888888u) | (yz[k] ^ 0x88888888u);
-      top = top_digit4(nzd);
-      sx = nx ? -1 : 1;
-      sy = ny ? -1 : 1;
-      sz = nz ? 1 : -1;  // the chain adds (-z) * R
-    }
-    {
-      Fe gu, gv;
-      good &= load_fq(gu, Gen_uv, 2 * i);
-      good &= load_fq(gv, Gen_uv, 2 * i + 1);
-      build_var_table(tg, gu, gv);
-    }
-    {
-      Fe pku, pkv;
-      good &= load_fq(pku, PK_uv, 2 * i);
-      good &= load_fq(pkv, PK_uv, 2 * i + 1);
-      build_var_table(tp, pku, pkv);
-    }
-    {
-      Fe ru, rv;
-      good &= load_fq(ru, R_uv, 2 * i);
-      good &= load_fq(rv, R_uv, 2 * i + 1);
-      build_var_table(tr, ru, rv);
-    }
-    Ext acc = ext_from_niels(load_var_entry(tg, sx * sdigit4(yx, top)));
-    acc = ext_add_niels(acc, load_var_entry(tp, sy * sdigit4(yy, top)));
-    acc = ext_add_niels(acc, load_var_entry(tr, sz * sdigit4(yz, top)));
-    {
-      const int k0 = top > 0 ? top - 1 : 0;
-      RawNiels ea = load_var_entry_raw(tg, sx * sdigit4(yx, k0));
-#pragma unroll 1
-      for (int k = top - 1; k >= 0; k--) {
-        acc = ext_mul16(acc);
-        const RawNiels eb = load_var_entry_raw(tp, sy * sdigit4(yy, k));
-        acc = ext_add_niels(acc, finish_var_entry(ea));
-        const RawNiels ec = load_var_entry_raw(tr, sz * sdigit4(yz, k));
-        acc = ext_add_niels(acc, finish_var_entry(eb));
-        const int kn = k > 0 ? k - 1 : 0;  // last round: reloads its own entry, unused
-        ea = load_var_entry_raw(tg, sx * sdigit4(yx, kn));
-        acc = ext_add_niels(acc, finish_var_entry(ec));
-      }
-    }
-    // T == O  <=>  u == 0 and v == z
-    good &= (bool)((int)fe_is_zero_canon(fe_canon(acc.u)) & (int)fe_equal(acc.v, acc.z));
+    // the per-item body, shared as text with k_verify_var_listed (k_keyed_open_var.hip)
+#include "verify_var_item_body.h"
     ok[i] = good ? 1 : 0;
   }
 }

@@ -35,60 +35,12 @@ k_verify_fixed_half(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c
     const size_t i = base + threadIdx.x;
     if (i >= n) continue;
     bool good = accumulate ? (ok[i] != 0) : (valid[i] != 0);
-    u32 ya[8], yb[8], w[8];
-    bool b_neg;
-    int top;
-    {
-      u32 cs[8], a[8], b[8];
-      load_words8(cs, c, i);
-      half_scalars(a, b, b_neg, cs);
-      // signed 2-bit digits of a and |b| (the sign of the R term goes into the point: -R below)
-      recode_signed2(ya, a);
-      recode_signed2(yb, b);
-      u32 nz[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) nz[k] = (ya[k] ^ 0x55555555u) | (yb[k] ^ 0x55555555u);
-      top = top_digit2(nz);
-      u32 us[8];
-      load_words8(us, u, i);
-      const bool u_ok = words_lt(us, kR32);
-      good &= u_ok;
-      if (!u_ok) us[7] &= 0x0fffffffu;  // keep fr_mul's inputs below r-ish; verdict is 0 anyway
-      fr_mul(w, b, us);                 // |b| * u mod r
-      if (b_neg) {                      // (b*u) mod r with b < 0
-        const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        u32 t[8];
-        fr_sub(t, zero, w);
-#pragma unroll
-        for (int k = 0; k < 8; k++) w[k] = t[k];
-      }
-    }
-#pragma unroll 1
-    for (int h = 0; h < NCHAIN; h++) {
-      const ChainOperands op = h ? op1 : op0;
-      {
-        Fe pku, pkv, ru, rv;
-        good &= load_fq(pku, op.PK_uv, 2 * i);
-        good &= load_fq(pkv, op.PK_uv, 2 * i + 1);
-        good &= load_fq_signed(ru, op.R_uv, 2 * i, !b_neg);  // the chain adds -|b| * R unless b < 0
-        good &= load_fq(rv, op.R_uv, 2 * i + 1);
-        build_joint_table(tbl, pku, pkv, ru, rv);
-      }
-      // T = a*PK + |b|*(-+R) (+ w*G below): one joint entry per 2-bit window, loaded one window ahead
-      Ext acc = ext_from_niels(load_joint_entry(tbl, joint_digit(ya, yb, top)));
-      {
-        RawJoint e = load_joint_entry_raw(tbl, joint_digit(ya, yb, top > 0 ? top - 1 : 0));
-#pragma unroll 1
-        for (int k = top - 1; k >= 0; k--) {
-          acc = ext_mul4(acc);
-          const Niels cur = finish_joint_entry(e);
-          e = load_joint_entry_raw(tbl, joint_digit(ya, yb, k > 0 ? k - 1 : 0));  // last: unused
-          acc = ext_add_niels(acc, cur);
-        }
-      }
-      // T + w*G == O  (T == O  <=>  u == 0 and v == z, decided inside the last addition)
-      good &= fixed_base_accumulate_is_identity(acc, w, op.table);
-    }
+    // the per-item body, shared as text with k_verify_listed (k_keyed_open.hip); the points lie at the item's row
+#define DSV_ITEM_ROW_SETUP
+#define DSV_ITEM_ROW i
+#include "verify_half_item_body.h"
+#undef DSV_ITEM_ROW
+#undef DSV_ITEM_ROW_SETUP
     ok[i] = good ? 1 : 0;
   }
 }

@@ -108,7 +108,7 @@ void launch_index_reinsert(KeyForm form, int npoints, const uint8_t* affine_rows
 }  // namespace dsv
 
 #ifdef DSV_INDEX_KERNELS
-// what the kernel units of the indices share (k_keyed_lookup.hip, k_keyed_replace.hip)
+// what the kernel units of the indices share (k_keyed_lookup.hip, k_keyed_replace.hip, k_keyed_open_mont.hip)
 namespace dsv {
 namespace {
 
@@ -146,6 +146,33 @@ __device__ __forceinline__ uint32_t home_hash(const Words<W>& w) {
     h.word(w.q[j].w);
   }
   return h.finish();
+}
+
+// ------------------------------------------------------------------------------------------
+// The lookup's walk (k_index_lookup, k_keyed_lookup.hip; k_normalize_lookup, k_keyed_open_mont.hip): from the home
+// slot of the row w, compare against the index's copy of each occupant's row; the walk ends at the first empty
+// slot.  k (> 0): the set's key count when the call was enqueued.  An occupant >= k was appended since: it is read
+// as an empty slot and ends the walk.  That is exact: every key below k whose walk passes this slot was placed
+// while the slot was still empty, so it sits in front of it.  Returns the occupant's index, or kSlotEmpty.  A set
+// without an index (k = 0, no rows, no slots) is the caller's to keep away.
+// ------------------------------------------------------------------------------------------
+template <int W>
+__device__ __forceinline__ uint32_t walk_index(const Words<W>& w, const uint8_t* __restrict__ rows,
+                                               const uint32_t* __restrict__ slots, size_t mask, size_t k) {
+  uint32_t found = kSlotEmpty;
+  size_t slot = home_hash<W>(w) & mask;
+#pragma unroll 1
+  for (size_t probe = 0;; probe++) {
+    const uint32_t occ = slots[slot];
+    if (occ >= k) break;  // empty (kSlotEmpty >= k), or a key newer than this call
+    if (same_words<W>(w, load_row<W>(rows, occ))) {
+      found = occ;
+      break;
+    }
+    if (probe == mask) break;  // unreachable: the table is at most half full, an empty slot ends the walk first
+    slot = (slot + 1) & mask;
+  }
+  return found;
 }
 
 // ---- the key forms: W = 16-byte words per row; source(P0, P1, j) = the row of the affine source key j (u || v,

@@ -108,3 +108,56 @@ def test_open_kernels_register_budget():
         assert k["vgpr_spill_count"] <= ref["vgpr_spill_count"], (chains, k, ref)
     miss = one(listed, "k_miss_list")
     assert miss["scratch"] == 0 and miss["vgpr_spill_count"] == 0, miss
+
+
+# ---- one source per item body (DESIGN.md §10.5 "One body or two", §10.9) ---------------------------------
+def test_item_bodies_have_one_source():
+    """The unkeyed equations and the helpers of the typed-object front exist once in csrc/: each miss-branch kernel
+    includes the fragment its unkeyed kernel includes and neither restates it, and the shared helpers are defined
+    once, in a header."""
+    import re
+
+    from test_isa_guard import CSRC
+
+    files = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))}
+    code = {f: re.sub(r"//[^\n]*", "", s) for f, s in files.items()}  # (comments may name what they like)
+    count = lambda name: {f: n for f, n in ((f, len(re.findall(r"(?<![A-Za-z0-9_])%s\(" % name, s)))
+                                            for f, s in code.items()) if n}
+    includes = lambda f: set(re.findall(r'^\s*#\s*include\s+"([^"]+)"', code[f], re.M))
+
+    # the fixed-generator body: the scalar preparation and the window loop are written in the fragment alone — the
+    # other callers of half_scalars are another method (the eight-lane kernel, k_quad.hip) and the introspection
+    # kernel of the tests (k_vargen.hip: k_debug_half_scalars)
+    half = "verify_half_item_body.h"
+    assert count("half_scalars") == {"halfgcd.h": 1, half: 1, "k_quad.hip": 1, "k_vargen.hip": 1}
+    assert count("ext_mul4") == {"common.h": 1, half: 1}
+    assert count("build_joint_table") == {"common.h": 1, half: 1}
+    for unit in ("k_verify.hip", "k_keyed_open.hip"):
+        assert half in includes(unit), unit
+        assert code[unit].count('#include "%s"' % half) == 1, unit
+    # the var-generator body: k_vargen.hip keeps two calls of its own — k_verify_var_hex, another method, and the
+    # introspection kernel k_debug_lattice3 — and the listed unit none
+    var = "verify_var_item_body.h"
+    assert count("lattice3_scalars") == {"lattice3.h": 1, var: 1, "k_vargen.hip": 2}
+    assert count("load_var_entry_raw").keys() == {"common.h", var}
+    for unit in ("k_vargen.hip", "k_keyed_open_var.hip"):
+        assert var in includes(unit), unit
+        assert code[unit].count('#include "%s"' % var) == 1, unit
+    # a fragment is text for its two kernels and nobody else's
+    for frag, users in ((half, {"k_verify.hip", "k_keyed_open.hip"}), (var, {"k_vargen.hip", "k_keyed_open_var.hip"})):
+        assert {f for f in code if frag in includes(f)} == users, frag
+        assert "#pragma once" not in code[frag] and "namespace" not in code[frag], frag
+
+    # the typed-object helpers and the index walk: one definition each, in a header both users include
+    defined = lambda name: [f for f, s in code.items()
+                            if re.search(r"^(?:DSV_DEV|__device__)[^;{}()]*\b%s\(" % name, s, re.M)]
+    assert defined("load_z_for_product") == ["normalize_items.h"]
+    assert defined("scalars_from_mont_item") == ["normalize_items.h"]
+    assert defined("walk_index") == ["keyed_lookup.h"]
+    assert [f for f, s in code.items() if re.search(r"\bkTwo5\[", s)] == ["normalize_items.h"]
+    for unit in ("k_misc.hip", "k_keyed_open_mont.hip"):
+        assert "normalize_items.h" in includes(unit), unit
+    assert {f for f, s in code.items() if re.search(r"\bwalk_index\b", s)} == {
+        "keyed_lookup.h", "k_keyed_lookup.hip", "k_keyed_open_mont.hip"}
+    # a set without an index reads nothing: the guard stands at the fused kernel's call site, not in the walk
+    assert re.search(r"key_ok && nkeys \? walk_index<W>\(", code["k_keyed_open_mont.hip"])
