@@ -74,8 +74,8 @@ def _grid(scheme, seed):
 
 def _torsion(scheme, d, seed):
     """rows of d with an order-8 / order-4 / order-2 component added to one point each"""
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
+    import torsion_model as TM
+    t8 = TM.order8_point()
     rnd = random.Random(seed)
     out = {k: v[:24].copy() for k, v in d.items()}
     for i in range(24):

@@ -8,17 +8,11 @@ import subprocess
 import pytest
 import torch
 
+from abi_model import declared_symbols
 from schnorr_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dsv.h")
 NO_GPU = not torch.cuda.is_available()
-
-
-def declared_symbols():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dsv_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_header_symbols_are_all_exported():

@@ -111,8 +111,8 @@ def test_shared_sum_and_difference_of_the_joint_table_build():
 def test_identity_decided_inside_the_last_addition():
     """ext_add_aniels_is_identity(p, n) == [p + n == O], for p = -n (true), p = -n + torsion and
     random p (false), affine and projective p"""
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
+    import torsion_model as TM
+    t8 = TM.order8_point()
     for trial in range(6):
         N = M.pmul(M.GEN, rnd.randrange(1, M.R_ORDER))
         n_ext = F.ext_from_affine(F.to_mont_int(N[0]), F.to_mont_int(N[1]))
@@ -158,8 +158,8 @@ def test_quad_group_law_matches_the_affine_model():
     """quad29.h (qext_double<true/false>, qext_add_niels, qext_add_aniels) and the octet combine of
     k_quad.hip against pymodel's point arithmetic, including the identity, the point of order 2 and a
     point with an order-8 component; t must stay u v / z wherever it is produced"""
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
+    import torsion_model as TM
+    t8 = TM.order8_point()
     pts = [M.IDENTITY, (0, F.Q - 1), t8, M.padd(M.pmul(M.GEN, 77), t8)]
     pts += [M.pmul(M.GEN, rnd.randrange(1, M.R_ORDER)) for _ in range(3)]
     for P in pts:

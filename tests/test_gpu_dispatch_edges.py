@@ -17,6 +17,7 @@ import dispatch_edges as D
 import edge_sets as ES
 import mont_cases as MC
 import oracle_lib as O
+from keyed_cases import _diff, _poison
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -60,18 +61,6 @@ def _slice(scheme, form, variant, n, device=True, nmax=None):
     big, w, length = _tile(scheme, form, variant, max(n, nmax or n), device)
     r = _rot(n, length)
     return [a[r:r + n] for a in big], w[r:r + n]
-
-
-def _diff(got, want):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
-    want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
-    bad = np.flatnonzero(got != want)
-    return "%d verdicts differ, first at %s (got %s, want %s)" % (
-        len(bad), bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
-
-
-def _poison(n):
-    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
 
 
 def _dev_call(engine, scheme, form, arrs, n):

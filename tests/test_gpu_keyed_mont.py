@@ -16,12 +16,10 @@ import pytest
 import torch
 
 import dispatch_edges as D
-import edge_sets as ES
-import harness as H
 import mont_cases as MC
-import oracle_lib as O
 import pymodel as M
-import test_gpu_keyset as TK
+import keyed_cases as KC
+from keyed_cases import _diff, _limbs, _oracle_mont_cols, _poison, _to_dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,15 +28,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCHEMES = ("single", "double", "vargen")
 NS = (1, 63, 64, 65, 4099, (1 << 16) + 3)
 Q, R_ORDER = M.Q, M.R_ORDER
-
-
-def _diff(got, want):
-    return TK._diff(np.asarray(got), np.asarray(want))
-
-
-def _limb_points(points, rng):
-    """affine [n, 64] -> limbs [n, 96] of the same points with a random z each (Python integers)"""
-    return MC.to_limbs_py(H.projective(points, rng)[0], Q)
 
 
 def _reduced(arr, mod):
@@ -56,27 +45,25 @@ def _oracle_mont(scheme, b, keys, idx=None, rows=slice(None)):
     idx = b["idx"] if idx is None else idx
     pts = [b["Rl"]] + ([b["Rpl"]] if scheme == "double" else [])
     cols = [b["ul"]] + pts + [kp[idx] for kp in keys] + [b["ml"]]
-    cols = [np.ascontiguousarray(c[rows]) for c in cols]
-    fn = getattr(O, "verify_%s_mont" % scheme)
-    return fn(*cols) if len(cols[0]) < 64 else ES._par(fn, *cols)
+    return _oracle_mont_cols(scheme, [c[rows] for c in cols])
 
 
 _MONT = {}
 
 
 def _mont_batch(engine, scheme, k, n):
-    """test_gpu_keyset._batch in the reference's in-memory form: every point re-represented with a random z,
+    """keyed_cases._batch in the reference's in-memory form: every point re-represented with a random z,
     everything converted to limbs with Python integers; `want` from the oracle's typed verify"""
     key = (scheme, k, n)
     if key not in _MONT:
-        b = TK._batch(engine, scheme, k, n)
+        b = KC._batch(engine, scheme, k, n)
         rng = np.random.default_rng(5 * k + n)
         out = {"idx": b["idx"].copy(), "P0": b["P0"], "P1": b["P1"], "R": b["R"], "Rp": b["Rp"],
                "u": _reduced(b["u"], R_ORDER), "m": _reduced(b["m"], Q)}
         out["ul"], out["ml"] = MC.to_limbs_py(out["u"], R_ORDER), MC.to_limbs_py(out["m"], Q)
-        out["Rl"] = _limb_points(b["R"], rng)
-        out["Rpl"] = _limb_points(b["Rp"], rng) if scheme == "double" else None
-        out["keys"] = [_limb_points(b["P0"], rng)] + ([_limb_points(b["P1"], rng)] if b["P1"] is not None else [])
+        out["Rl"] = _limbs(b["R"], rng)
+        out["Rpl"] = _limbs(b["Rp"], rng) if scheme == "double" else None
+        out["keys"] = [_limbs(b["P0"], rng)] + ([_limbs(b["P1"], rng)] if b["P1"] is not None else [])
         out["want"] = _oracle_mont(scheme, out, out["keys"])
         if len(_MONT) > 3:
             _MONT.pop(next(iter(_MONT)))
@@ -89,15 +76,6 @@ def _cols(scheme, b, rows=slice(None), idx=None):
     idx = b["idx"] if idx is None else idx
     pts = [b["Rl"][rows]] + ([b["Rpl"][rows]] if scheme == "double" else [])
     return [b["ul"][rows]] + pts + [idx[rows], b["ml"][rows]]
-
-
-def _to_dev(a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
-
-
-def _poison(n):
-    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
 
 
 def _run_dev(engine, ks, darrs, n, stream=None):
@@ -181,7 +159,7 @@ def test_unholdable_keys_give_zero(engine, scheme):
     # off the curve: u + 1 in the affine point, re-represented
     off = b["P0"][11:12].copy()
     off[0, :32] = np.frombuffer(M.le32((M.from_le(off[0, :32]) + 1) % Q), np.uint8)
-    keys[0][11] = _limb_points(off, np.random.default_rng(3))[0]
+    keys[0][11] = _limbs(off, np.random.default_rng(3))[0]
     bad = [3, 5, 7, 11]
     under = np.isin(b["idx"], bad)
     assert all((b["want"][b["idx"] == j] == 1).any() for j in bad)
@@ -255,7 +233,7 @@ def test_same_set_as_affine_constructor(engine, scheme):
     off = P0[11:12].copy()
     off[0, 32:] = np.frombuffer(M.le32((M.from_le(off[0, 32:]) + 2) % Q), np.uint8)  # off the curve in both sets
     P0[11] = off[0]
-    keys[0][11] = _limb_points(off, np.random.default_rng(4))[0]
+    keys[0][11] = _limbs(off, np.random.default_rng(4))[0]
     npts = len(keys)
     with engine.KeySet.from_mont_cols(scheme, keys) as typed, engine.KeySet(scheme, P0, b["P1"]) as affine:
         assert typed.k == affine.k == 37 and typed.nbytes == affine.nbytes
@@ -285,7 +263,7 @@ def test_two_pow_20_matches_existing_paths(engine, scheme):
         assert (got == want).all(), _diff(got, want)
         # the affine keyed call on the canonical bytes of the same values
         pts = [b["R"]] + ([b["Rp"]] if scheme == "double" else [])
-        affine = TK._run_dev(engine, ks, [tile(c) for c in [b["u"]] + pts + [b["idx"], b["m"]]], n)
+        affine = KC._run_dev(engine, ks, [tile(c) for c in [b["u"]] + pts + [b["idx"], b["m"]]], n)
         assert (affine == got).all(), _diff(affine, got)
     # the unkeyed typed call with the keys gathered per item
     unkeyed = [tile(c) for c in _unkeyed_cols(scheme, b, b["keys"])]
@@ -495,11 +473,11 @@ def _host_batch(engine, scheme):
         _HOST.clear()
         nmax, k = max(D.edges("host/mont_cols/%s" % scheme)), 37
         assert nmax <= D.HOST_MAX
-        sk, gen, P0, P1 = TK._keys(engine, scheme, k, 777)
+        sk, gen, P0, P1 = KC._keys(engine, scheme, k, 777)
         rng = np.random.default_rng(20261017)
         idx = rng.integers(0, k, size=HOST_BLOCK).astype(np.uint32)
-        m = TK._scalars(rng, HOST_BLOCK, 0x3F)
-        r = TK._scalars(rng, HOST_BLOCK, 0x07)
+        m = KC._scalars(rng, HOST_BLOCK, 0x3F)
+        r = KC._scalars(rng, HOST_BLOCK, 0x07)
         Rp = None
         if scheme == "single":
             u, R = engine.sign_single(sk[idx], m, r)
@@ -509,8 +487,8 @@ def _host_batch(engine, scheme):
             u, R = engine.sign_vargen(sk[idx], gen[idx], m, r)
         times = -(-nmax // HOST_BLOCK)
         tile = lambda a: np.ascontiguousarray(np.tile(a, (times,) + (1,) * (a.ndim - 1))[:nmax])
-        pts = [tile(_limb_points(R, rng))] + ([tile(_limb_points(Rp, rng))] if Rp is not None else [])
-        keys = [_limb_points(P0, rng)] + ([_limb_points(P1, rng)] if P1 is not None else [])
+        pts = [tile(_limbs(R, rng))] + ([tile(_limbs(Rp, rng))] if Rp is not None else [])
+        keys = [_limbs(P0, rng)] + ([_limbs(P1, rng)] if P1 is not None else [])
         _HOST[scheme] = {"cols": [tile(MC.to_limbs_py(u, R_ORDER))] + pts + [tile(idx), tile(MC.to_limbs_py(m, Q))],
                          "ks": engine.KeySet.from_mont_cols(scheme, keys)}
     return _HOST[scheme]

@@ -12,7 +12,7 @@ import torch
 
 import oracle_lib as O
 import pymodel as M
-import test_gpu_keyset as TK
+import keyed_cases as KC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -28,11 +28,11 @@ def _signed(engine, scheme, k, n, seed=0):
     key = (scheme, k, n, seed)
     if key in _BATCHES:
         return {a: (v.copy() if isinstance(v, np.ndarray) else v) for a, v in _BATCHES[key].items()}
-    sk, gen, P0, P1 = TK._keys(engine, scheme, k, 5000 + 17 * k + seed)
+    sk, gen, P0, P1 = KC._keys(engine, scheme, k, 5000 + 17 * k + seed)
     rng = np.random.default_rng(n * 7 + k + seed)
     idx = rng.integers(0, k, size=n).astype(np.uint32)
-    m = TK._scalars(rng, n, 0x3F)
-    r = TK._scalars(rng, n, 0x07)
+    m = KC._scalars(rng, n, 0x3F)
+    r = KC._scalars(rng, n, 0x07)
     Rp = None
     if scheme == "single":
         u, R = engine.sign_single(sk[idx], m, r)
@@ -53,7 +53,7 @@ def _set(engine, scheme, b):
 
 def _args(b):
     pts = [b["R"]] + ([b["Rp"]] if b["Rp"] is not None else [])
-    return TK._dev([b["u"]] + pts + [b["idx"], b["m"]])
+    return KC._dev([b["u"]] + pts + [b["idx"], b["m"]])
 
 
 def _rlc(engine, ks, b, window_bits=0, stream=None, accepted_out=None):
@@ -68,12 +68,12 @@ def _rlc(engine, ks, b, window_bits=0, stream=None, accepted_out=None):
 
 def _per_sig(engine, ks, b):
     n = b["u"].shape[0]
-    return TK._run_dev(engine, ks, _args(b), n)
+    return KC._run_dev(engine, ks, _args(b), n)
 
 
 def _oracle(scheme, b):
     g1 = b["P1"][b["idx"]] if b["P1"] is not None else None
-    return TK._oracle(scheme, b["u"], b["R"], b["Rp"], b["P0"][b["idx"]], g1, b["m"])
+    return KC._oracle(scheme, b["u"], b["R"], b["Rp"], b["P0"][b["idx"]], g1, b["m"])
 
 
 def _wrong(b, i):
@@ -98,7 +98,7 @@ def test_all_valid_is_accepted(engine, scheme):
             with _set(engine, scheme, b) as ks:
                 acc, ok = _rlc(engine, ks, b, bits)
                 assert acc is True, (scheme, k, bits)
-                assert ok.all(), TK._diff(ok, np.ones(n, np.uint8))
+                assert ok.all(), KC._diff(ok, np.ones(n, np.uint8))
     b = _signed(engine, scheme, 3, 1500)
     with _set(engine, scheme, b) as ks:
         assert np.array_equal(_rlc(engine, ks, b, 8)[1], _per_sig(engine, ks, b))
@@ -117,7 +117,7 @@ def test_one_wrong_signature_in_forced_sub_groups(engine, scheme, subgroups):
         with _set(engine, scheme, b) as ks:
             acc, ok = _rlc(engine, ks, b, 8)
             assert acc is False, (scheme, groups)
-            assert np.array_equal(ok, want), TK._diff(ok, want)
+            assert np.array_equal(ok, want), KC._diff(ok, want)
             assert np.array_equal(ok, _per_sig(engine, ks, b))
 
 
@@ -141,7 +141,7 @@ def test_malformed_items_stay_out_of_the_sum(engine, scheme):
         want = np.ones(n, np.uint8)
         want[[5, 60, 1100, 300, 301]] = 0
         want[under_bad] = 0
-        assert np.array_equal(ok, want), TK._diff(ok, want)
+        assert np.array_equal(ok, want), KC._diff(ok, want)
         assert acc is True
         assert np.array_equal(ok, _per_sig(engine, ks, b2))
 
@@ -149,9 +149,9 @@ def test_malformed_items_stay_out_of_the_sum(engine, scheme):
 def _torsion_items(engine, count, cancel, key_torsion, rnd):
     """single-scheme items whose key (key_torsion) or nonce point carries an order-8 component; cancel: valid
     under the reference's cofactorless equation.  Returns (PK rows, u, R, m)."""
-    import test_halfgcd as TH
+    import torsion_model as TM
 
-    t8 = TH.order8_point()
+    t8 = TM.order8_point()
     rows = {"PK": [], "u": [], "R": [], "m": []}
     while len(rows["u"]) < count:
         sk, m, rr = rnd.randrange(1, M.R_ORDER), rnd.randrange(M.Q), rnd.randrange(1, M.R_ORDER)
@@ -184,7 +184,7 @@ def test_order8_components_are_never_accepted(engine):
         with _set(engine, "single", b) as ks:
             acc, ok = _rlc(engine, ks, b, 8)
             assert acc is False, (key_torsion, cancel)
-            assert np.array_equal(ok, want), TK._diff(ok, want)
+            assert np.array_equal(ok, want), KC._diff(ok, want)
             assert np.array_equal(ok, _per_sig(engine, ks, b))
 
 
@@ -211,7 +211,7 @@ def test_2p20_items(engine, scheme, k):
             assert want.sum() == n - 1 and want[777777] == 0
             acc, ok = _rlc(engine, ks, b)
             assert acc is False
-            assert np.array_equal(ok, want), TK._diff(ok, want)
+            assert np.array_equal(ok, want), KC._diff(ok, want)
 
 
 @pytest.mark.parametrize("scheme", SCHEMES)
@@ -349,16 +349,16 @@ def test_capture_is_refused_unkeyed(engine, form):
     n, PK = len(b["m"]), b["P0"][b["idx"]]
     if form == "wire":
         cp = engine.compress_points
-        args = TK._dev([np.concatenate([b["u"], cp(b["R"])], axis=1), cp(PK), b["m"]])
+        args = KC._dev([np.concatenate([b["u"], cp(b["R"])], axis=1), cp(PK), b["m"]])
         ws = torch.empty(engine.wire_rlc_workspace_bytes(n, 8), dtype=torch.uint8, device=DEV)
         call = lambda ok: engine.verify_wire_rlc_dev("single", *args, ok, ws, window_bits=8)
     elif form == "mixed":
-        u, R, PKt, m = TK._dev([b["u"], b["R"], PK, b["m"]])
+        u, R, PKt, m = KC._dev([b["u"], b["R"], PK, b["m"]])
         kinds = torch.zeros(n, dtype=torch.uint8, device=DEV)
         ws = torch.empty(engine.mixed_rlc_workspace_bytes(n), dtype=torch.uint8, device=DEV)
         call = lambda ok: engine.verify_mixed_rlc_dev(kinds, u, R, R, PKt, PKt, m, 0, ok, ws)
     else:
-        args = TK._dev([b["u"], b["R"], PK, b["m"]])
+        args = KC._dev([b["u"], b["R"], PK, b["m"]])
         ws = torch.empty(engine.rlc_workspace_bytes(n, 8), dtype=torch.uint8, device=DEV)
         call = lambda ok: engine.verify_single_rlc_dev(*args, ok, ws, window_bits=8)
     ok = torch.full((n,), 7, dtype=torch.uint8, device=DEV)

@@ -15,9 +15,9 @@ import torch
 
 import dispatch_edges as D
 import edge_sets as ES
-import oracle_lib as O
 import pymodel as M
-import test_gpu_keyset as TK
+import keyed_cases as KC
+from keyed_cases import _diff, _enc, _key_records, _non_squares, _oracle_wire, _poison, _sig, _to_dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -29,36 +29,14 @@ SIG_BYTES = {"single": 64, "double": 96, "vargen": 64}
 Q = M.Q
 
 
-def _diff(got, want):
-    return TK._diff(np.asarray(got), np.asarray(want))
-
-
-def _sig(u, R, Rp=None):
-    """Signature*::to_bytes: u, then the nonce points compressed"""
-    cols = [u, O.compress(R)] + ([O.compress(Rp)] if Rp is not None else [])
-    return np.ascontiguousarray(np.concatenate(cols, axis=1))
-
-
-def _key_records(P0, P1):
-    """PublicKey*::to_bytes of the keys"""
-    return np.ascontiguousarray(O.compress(P0) if P1 is None else np.hstack([O.compress(P0), O.compress(P1)]))
-
-
-def _oracle_wire(scheme, sig, pk, m):
-    fn = getattr(O, "verify_%s_wire" % scheme)
-    if len(m) < 64:
-        return fn(sig, pk, m)
-    return ES._par(fn, sig, pk, m)
-
-
 _WIRE = {}
 
 
 def _wire_batch(engine, scheme, k, n):
-    """test_gpu_keyset._batch serialized: sig, idx, m, the key records and the oracle's wire verdicts"""
+    """keyed_cases._batch serialized: sig, idx, m, the key records and the oracle's wire verdicts"""
     key = (scheme, k, n)
     if key not in _WIRE:
-        b = TK._batch(engine, scheme, k, n)
+        b = KC._batch(engine, scheme, k, n)
         sig = _sig(b["u"], b["R"], b["Rp"])
         rec = _key_records(b["P0"], b["P1"])
         want = _oracle_wire(scheme, sig, rec[b["idx"]], b["m"])
@@ -67,15 +45,6 @@ def _wire_batch(engine, scheme, k, n):
         _WIRE[key] = {"sig": sig, "idx": b["idx"].copy(), "m": b["m"], "rec": rec, "want": want, "P0": b["P0"],
                       "P1": b["P1"]}
     return _WIRE[key]
-
-
-def _to_dev(a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
-
-
-def _poison(n):
-    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
 
 
 def _run_wire_dev(engine, ks, dsig, didx, dm, n, stream=None):
@@ -127,21 +96,6 @@ def test_adversarial_wire_set(engine, scheme):
 
 
 # ---- the composed path: decompress, keyed verify, AND of the decode flags ---------------------------------
-def _enc(v, sign):
-    b = bytearray(M.le32(v))
-    b[31] |= sign << 7
-    return np.frombuffer(bytes(b), np.uint8)
-
-
-def _non_squares(count):
-    """encodings v whose u^2 = (v^2 - 1) / (1 + d v^2) has no root, by the oracle's decoder"""
-    cand = np.stack([_enc(v, v & 1) for v in range(2, 200)])
-    _, ok = O.decompress(cand)
-    bad = cand[ok == 0]
-    assert len(bad) >= count
-    return bad[:count]
-
-
 def _plant_undecodable(scheme, sig, want_rows):
     """rows of honest items -> sig with undecodable and special nonce encodings planted; returns the planted
     (row, what) list.  Column 32:64 is R, 64:96 (double) R'."""
@@ -186,8 +140,8 @@ def test_equals_composed_path(engine, scheme, k):
         assert flags[i] == (1 if decodable else 0), (i, what)
     assert (flags == 0).sum() == sum(1 for p in planted if not p[2])
     u = np.ascontiguousarray(sig[:, :32])
-    with TK._keyset(engine, scheme, b) as ks:
-        composed = TK._run_dev(engine, ks, TK._dev([u] + cols + [b["idx"], b["m"]]), n) & flags
+    with KC._keyset(engine, scheme, b) as ks:
+        composed = KC._run_dev(engine, ks, KC._dev([u] + cols + [b["idx"], b["m"]]), n) & flags
         dsig, didx, dm = _to_dev(sig), _to_dev(b["idx"]), _to_dev(b["m"])
         for nn in NS:
             got = _run_wire_dev(engine, ks, dsig, didx, dm, nn)
@@ -205,11 +159,11 @@ def test_equals_composed_path(engine, scheme, k):
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_two_pow_20_matches_unkeyed_wire(engine, scheme):
     n, k = 1 << 20, 64
-    sk, gen, P0, P1 = TK._keys(engine, scheme, k, 4242)
+    sk, gen, P0, P1 = KC._keys(engine, scheme, k, 4242)
     rng = np.random.default_rng(99)
     idx = rng.integers(0, k, size=n).astype(np.uint32)
-    m = TK._scalars(rng, n, 0x3F)
-    r = TK._scalars(rng, n, 0x07)
+    m = KC._scalars(rng, n, 0x3F)
+    r = KC._scalars(rng, n, 0x07)
     Rp = None
     if scheme == "single":
         u, R = engine.sign_single(sk[idx], m, r)
@@ -249,7 +203,7 @@ def test_index_checks(engine, scheme):
     idx[bad[3]] = (idx[bad[3]] + 1) % 37  # another key's index
     want = b["want"].copy()
     want[bad] = 0
-    with TK._keyset(engine, scheme, b) as ks:
+    with KC._keyset(engine, scheme, b) as ks:
         got = _wire_dev(engine, ks, b["sig"], idx, b["m"])
         assert (got == want).all(), _diff(got, want)
         assert (ks.verify_wire(b["sig"], idx, b["m"]) == want).all()
@@ -291,7 +245,7 @@ def test_dev_semantics(engine):
     b = _wire_batch(engine, "single", 37, n)
     dsig, didx, dm = _to_dev(b["sig"]), _to_dev(b["idx"]), _to_dev(b["m"])
     vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    with TK._keyset(engine, "single", b) as ks:
+    with KC._keyset(engine, "single", b) as ks:
         need = engine.keyed_wire_workspace_bytes("single", n)
         ws = torch.empty(need, dtype=torch.uint8, device=DEV)
         # enqueued on a side stream behind a poison fill on that stream
@@ -358,11 +312,11 @@ def _host_batch(engine, scheme):
         _HOST.clear()
         nmax, k = max(D.edges("host/wire/%s" % scheme)), 37
         assert nmax <= D.HOST_MAX
-        sk, gen, P0, P1 = TK._keys(engine, scheme, k, 777)
+        sk, gen, P0, P1 = KC._keys(engine, scheme, k, 777)
         rng = np.random.default_rng(20261016)
         idx = rng.integers(0, k, size=nmax).astype(np.uint32)
-        m = TK._scalars(rng, nmax, 0x3F)
-        r = TK._scalars(rng, nmax, 0x07)
+        m = KC._scalars(rng, nmax, 0x3F)
+        r = KC._scalars(rng, nmax, 0x07)
         Rp = None
         if scheme == "single":
             u, R = engine.sign_single(sk[idx], m, r)
@@ -424,7 +378,7 @@ def test_two_host_calls_in_flight(engine, scheme):
 # ---- lifetime ---------------------------------------------------------------------------------------------
 def test_closed_set_raises(engine):
     b = _wire_batch(engine, "single", 37, 4099)
-    ks = TK._keyset(engine, "single", b)
+    ks = KC._keyset(engine, "single", b)
     assert (ks.verify_wire(b["sig"], b["idx"], b["m"]) == b["want"]).all()
     ks.close()
     with pytest.raises(ValueError):

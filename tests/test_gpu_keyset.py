@@ -15,6 +15,8 @@ import edge_sets as ES
 import harness as H
 import oracle_lib as O
 import pymodel as M
+import torsion_model as TM
+from keyed_cases import _batch, _dev, _diff, _items, _keys, _keyset, _oracle, _poison, _run_dev, _scalars
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,106 +25,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCHEMES = ("single", "double", "vargen")
 NS = (1, 63, 64, 65, 4099, (1 << 16) + 3)
 Q, R_ORDER = M.Q, M.R_ORDER
-
-
-def _scalars(rng, n, top_mask):
-    s = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
-    s[:, 31] &= top_mask
-    return s
-
-
-def _keys(engine, scheme, k, seed):
-    """(PK, second point or None) of k random keys: PK' for double, Gen for var-generator; and the secrets"""
-    rng = np.random.default_rng(seed)
-    sk = _scalars(rng, k, 0x07)  # < 2^251 < r
-    if scheme == "single":
-        return sk, None, engine.public_keys(sk), None
-    if scheme == "double":
-        return sk, None, engine.public_keys(sk, 0), engine.public_keys(sk, 1)
-    gen = engine.public_keys(_scalars(rng, k, 0x07))
-    return sk, gen, engine.public_keys(sk, Gen=gen), gen
-
-
-def _oracle(scheme, u, R, Rp, P0, P1, m):
-    if scheme == "single":
-        return O.verify_single(u, R, P0, m, nthreads=16)
-    if scheme == "double":
-        return O.verify_double(u, R, Rp, P0, P1, m, nthreads=16)
-    return O.verify_vargen(u, R, P0, P1, m, nthreads=16)
-
-
-_BATCHES = {}
-
-
-def _batch(engine, scheme, k, n, seed=0):
-    """n items signed under k keys (uniform indices), every 16th tampered (harness.tamper) -> dict with the key
-    arrays P0 / P1, the items u, R, Rp, idx, m and the oracle's verdicts on the gathered keys"""
-    key = (scheme, k, n, seed)
-    if key in _BATCHES:
-        return _BATCHES[key]
-    sk, gen, P0, P1 = _keys(engine, scheme, k, 1000 * k + 7 + seed)
-    rng = np.random.default_rng(k * 31 + n + seed)
-    idx = rng.integers(0, k, size=n).astype(np.uint32)
-    m = _scalars(rng, n, 0x3F)   # < 2^254 < q
-    r = _scalars(rng, n, 0x07)
-    Rp = None
-    if scheme == "single":
-        u, R = engine.sign_single(sk[idx], m, r)
-    elif scheme == "double":
-        u, R, Rp = engine.sign_double(sk[idx], m, r)
-    else:
-        u, R = engine.sign_vargen(sk[idx], gen[idx], m, r)
-    b = {"u": u, "R": R, "PK": P0[idx].copy(), "m": m}
-    H.tamper(b, kind_single=scheme == "single", period=16)
-    # a tampered PK row that is another registered key becomes that key's index; any other stays the row's key
-    where = {P0[j].tobytes(): j for j in range(k)}
-    changed = np.flatnonzero((b["PK"] != P0[idx]).any(axis=1))
-    for i in changed:
-        idx[i] = where.get(b["PK"][i].tobytes(), idx[i])
-    g1 = P1[idx] if P1 is not None else None
-    want = _oracle(scheme, b["u"], b["R"], Rp, P0[idx], g1, b["m"])
-    out = {"P0": P0, "P1": P1, "u": b["u"], "R": b["R"], "Rp": Rp, "idx": idx, "m": b["m"], "want": want}
-    if len(_BATCHES) > 4:
-        _BATCHES.pop(next(iter(_BATCHES)))
-    _BATCHES[key] = out
-    return out
-
-
-def _items(b, lo=0, hi=None):
-    """(u, R[, Rp], idx, m) host arrays of items [lo, hi)"""
-    s = slice(lo, hi)
-    pts = [b["R"][s]] + ([b["Rp"][s]] if b["Rp"] is not None else [])
-    return [b["u"][s]] + pts + [b["idx"][s], b["m"][s]]
-
-
-def _dev(arrs):
-    out = []
-    for a in arrs:
-        t = torch.from_numpy(np.ascontiguousarray(a).view(np.int32) if a.dtype == np.uint32 else np.ascontiguousarray(a))
-        out.append(t.to(DEV))
-    return out
-
-
-def _poison(n):
-    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
-
-
-def _run_dev(engine, ks, darrs, n, stream=None):
-    ok = _poison(n)
-    ws = torch.empty(max(engine.keyed_workspace_bytes(n), 1), dtype=torch.uint8, device=DEV)
-    ks.verify_dev(*[a[:n] for a in darrs], ok, ws, stream=stream)
-    torch.cuda.synchronize()
-    return ok.cpu().numpy()
-
-
-def _diff(got, want):
-    bad = np.flatnonzero(got != want)
-    return "%d verdicts differ, first at %s (got %s, want %s)" % (
-        len(bad), bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
-
-
-def _keyset(engine, scheme, b):
-    return engine.KeySet(scheme, b["P0"], b["P1"])
 
 
 # ---- oracle parity ----------------------------------------------------------------------------------------
@@ -203,16 +105,11 @@ def test_two_pow_20_matches_unkeyed(engine, scheme):
 
 
 # ---- table entries ----------------------------------------------------------------------------------------
-def _small_order_point():
-    import test_halfgcd as TH
-    return TH.order8_point()
-
-
 @pytest.mark.parametrize("point", (0, 1))
 def test_table_entries_are_true_multiples(engine, point):
     """entry [w][d] of a normal and a small-order (order 8) point equals d * 2^(8w) * P; -d its negation"""
     normal = H.to_int_point(engine.public_keys(_scalars(np.random.default_rng(5), 1, 0x07))[0])
-    small = _small_order_point()
+    small = TM.order8_point()
     pts = [normal, small]
     P0 = np.stack([np.frombuffer(M.point_bytes(p), np.uint8) for p in pts])
     # point 1 (double: PK'): the same two points in the other slot, a different first point

@@ -2,8 +2,8 @@
 the set dsv_keyset_create builds over the same keys — key_ok, table entries, every keyed verdict vector, all equal
 to the CPU oracle's —, the index keeps its invariants across appends (clusters that span calls, wrap-around,
 duplicates, invalid keys), a full set refuses and stays as it was, a captured graph keeps the k of its capture
-(the stale-k rule of the lookup kernel), and verify calls run beside appends.  Keys and items are generated the
-way tests/test_gpu_keyset.py does; every batch holds valid and invalid items."""
+(the stale-k rule of the lookup kernel), and verify calls run beside appends.  Keys and items come from
+tests/keyed_cases.py; every batch holds valid and invalid items."""
 import ctypes
 import threading
 
@@ -15,8 +15,7 @@ import harness as H
 import mont_cases as MC
 import oracle_lib as O
 import pymodel as M
-from test_gpu_keyset import _dev, _diff, _keys, _oracle, _poison, _scalars
-from test_gpu_keyset_lookup import _check_lookup, _expect, _le, _where
+from keyed_cases import _check_lookup, _dev, _diff, _expect, _keys, _le, _oracle, _poison, _scalars, _where
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -1,7 +1,7 @@
 """Key sets by key value on the GPU (dsv_keyset_lookup*, dsv_verify_keyed_lookup*): the lookup against a Python
 dict over the registered keys' bytes, duplicates and invalid keys, probes that wrap round the end of the slot
 table, collisions at size, closed-set verify against the oracle and against the keyed call at the dict's
-indices, and the _dev contract.  Keys and items are generated the way tests/test_gpu_keyset.py does."""
+indices, and the _dev contract.  Keys and items come from tests/keyed_cases.py."""
 import ctypes
 import os
 import subprocess
@@ -13,7 +13,8 @@ import torch
 
 import harness as H
 import pymodel as M
-from test_gpu_keyset import _dev, _diff, _keys, _oracle, _poison, _scalars
+from keyed_cases import (_check_lookup, _dev, _diff, _expect, _expect_rec, _key_records, _keys, _le, _poison, _scalars,
+                         _value_args, _value_batch, _where, _where_rec)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,49 +24,6 @@ SCHEMES = ("single", "double", "vargen")
 NONE = 0xFFFFFFFF
 Q = M.Q
 INVALID, NOT_INITIALIZED = -2, -1
-
-
-# ---- the model: a dict over the bytes of the valid registered keys, lowest index first ---------------------
-def _row(A, B, i):
-    return A[i].tobytes() + (B[i].tobytes() if B is not None else b"")
-
-
-def _where(P0, P1, key_ok):
-    d = {}
-    for j in range(len(P0)):
-        if key_ok[j]:
-            d.setdefault(_row(P0, P1, j), j)
-    return d
-
-
-def _expect(where, A, B):
-    return np.array([where.get(_row(A, B, i), NONE) for i in range(len(A))], dtype=np.uint32)
-
-
-def _lookup_dev(ks, A, B, stream=None):
-    """(idx uint32 [n], misses) through KeySet.lookup_dev, idx and the counter poisoned first"""
-    cols = _dev([A] + ([B] if B is not None else []))
-    out = torch.full((len(A),), 0x5A5A5A5A, dtype=torch.int32, device=DEV)
-    misses = torch.full((1,), 12345, dtype=torch.int32, device=DEV)
-    ks.lookup_dev(*cols, out, misses=misses, stream=stream)
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(np.uint32), int(misses.item())
-
-
-def _check_lookup(ks, where, A, B, what):
-    want = _expect(where, A, B)
-    nmiss = int((want == NONE).sum())
-    got, misses = _lookup_dev(ks, A, B)
-    assert (got == want).all(), (what, "dev", _diff(got, want))
-    assert misses == nmiss, (what, "dev", misses, nmiss)
-    got, misses = ks.lookup(*([A] + ([B] if B is not None else [])))
-    assert (got == want).all(), (what, "host", _diff(got, want))
-    assert misses == nmiss, (what, "host", misses, nmiss)
-    return want
-
-
-def _le(x):
-    return np.frombuffer(M.le32(x), np.uint8)
 
 
 # ---- 1. lookup parity with a dict --------------------------------------------------------------------------
@@ -239,43 +197,6 @@ def test_collisions_at_size(engine):
 
 
 # ---- 5. verify by value ------------------------------------------------------------------------------------
-_VALUE_BATCHES = {}
-
-
-def _value_batch(engine, scheme, k=33, n=4099):
-    """n items signed under k keys, every 16th tampered (harness.tamper: some key rows become other registered
-    keys, some leave the set) -> the key arrays, the items with their own key columns, the oracle's verdicts on
-    those key bytes, computed once per scheme"""
-    if scheme in _VALUE_BATCHES:
-        return _VALUE_BATCHES[scheme]
-    sk, gen, P0, P1 = _keys(engine, scheme, k, 1000 * k + 11)
-    rng = np.random.default_rng(k * 37 + n)
-    idx = rng.integers(0, k, size=n)
-    m = _scalars(rng, n, 0x3F)
-    r = _scalars(rng, n, 0x07)
-    Rp = None
-    if scheme == "single":
-        u, R = engine.sign_single(sk[idx], m, r)
-    elif scheme == "double":
-        u, R, Rp = engine.sign_double(sk[idx], m, r)
-    else:
-        u, R = engine.sign_vargen(sk[idx], gen[idx], m, r)
-    b = {"u": u, "R": R, "PK": P0[idx].copy(), "m": m}
-    H.tamper(b, kind_single=scheme == "single", period=16)
-    B = P1[idx].copy() if P1 is not None else None
-    oracle = _oracle(scheme, b["u"], b["R"], Rp, b["PK"], B, b["m"])
-    out = {"P0": P0, "P1": P1, "u": b["u"], "R": b["R"], "Rp": Rp, "A": b["PK"], "B": B, "m": b["m"],
-           "oracle": oracle}
-    _VALUE_BATCHES[scheme] = out
-    return out
-
-
-def _value_args(b, n):
-    pts = [b["R"][:n]] + ([b["Rp"][:n]] if b["Rp"] is not None else [])
-    keys = [b["A"][:n]] + ([b["B"][:n]] if b["B"] is not None else [])
-    return [b["u"][:n]] + pts + keys + [b["m"][:n]]
-
-
 @pytest.mark.parametrize("n", (1, 65, 4099))
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_verify_by_value(engine, scheme, n):
@@ -339,8 +260,6 @@ def _tiled(a, n):
 def test_host_lookups_across_a_chunk_boundary(engine, scheme):
     """dsv_keyset_lookup and dsv_keyset_lookup_wire on 2^18 + 5 host items tiled from 4099: the second chunk
     holds five items; the indices are the dict model's and `misses` is the sum over both chunks"""
-    from test_gpu_keyset_open_wire import _expect_rec, _key_records, _where_rec
-
     k, extra, base, n = 33, 8, 4099, HOST_CHUNK + 5
     _, _, K0, K1 = _keys(engine, scheme, k + extra, 4711)
     P0, X0 = np.ascontiguousarray(K0[:k]), K0[k:]

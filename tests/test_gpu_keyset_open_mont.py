@@ -14,12 +14,11 @@ import pytest
 import torch
 
 import dispatch_edges as D
-import edge_sets as ES
-import harness as H
 import mont_cases as MC
-import oracle_lib as O
 import pymodel as M
-import test_gpu_keyset as TK
+import torsion_model as TM
+from keyed_cases import (FRONT_N, NKEY, NS, NSIG, REG, SCHEMES, _diff, _limbs, _mixture, _open_mont_ws,
+                         _oracle_mont_cols, _plants, _poison, _pool, _pool_keyset, _scalars, _sign_items, _to_dev)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,23 +26,9 @@ POISON = 7
 NONE = 0xFFFFFFFF
 INVALID = -2
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCHEMES = ("single", "double", "vargen")
-# 2^15 + 3: the first size at which a lane shares its inversion among 8 items, with a ragged last lane
-NS = (1, 63, 64, 65, 4099, (1 << 15) + 3)
 KS = (0, 1, 64)
-NSIG = {"single": 1, "double": 2, "vargen": 1}
-NKEY = {"single": 1, "double": 2, "vargen": 2}
 Q, R_ORDER = M.Q, M.R_ORDER
 R_INV = pow(1 << 256, -1, Q)
-
-
-def _diff(got, want):
-    return TK._diff(np.asarray(got), np.asarray(want))
-
-
-def _limbs(points, rng):
-    """affine [n, 64] -> Montgomery limbs [n, 96] of the same points with a fresh random z each"""
-    return MC.to_limbs_py(H.projective(points, rng)[0], Q)
 
 
 def _limbs_z1(points):
@@ -61,88 +46,10 @@ def _normal_form(limbs):
     return out
 
 
-def _oracle(scheme, cols):
-    O.lib()  # (loaded on this thread, before the row blocks go to a pool)
-    fn = getattr(O, "verify_%s_mont" % scheme)
-    cols = [np.ascontiguousarray(c) for c in cols]
-    return np.asarray(fn(*cols) if len(cols[0]) < 64 else ES._par(fn, *cols)).astype(np.uint8)
-
-
-def _sign(engine, scheme, sk, gen, m, r):
-    if scheme == "single":
-        return engine.sign_single(sk, m, r) + (None,)
-    if scheme == "double":
-        return engine.sign_double(sk, m, r)
-    return engine.sign_vargen(sk, gen, m, r) + (None,)
-
-
-REG, UNREG = 64, 8
-_POOL, _MIX = {}, {}
-
-
-def _pool(engine, scheme):
-    """REG keys to register and UNREG valid keys nobody registers"""
-    if scheme not in _POOL:
-        _POOL[scheme] = TK._keys(engine, scheme, REG + UNREG, 9100 + len(scheme))
-    return _POOL[scheme]
-
-
-def _mixture(engine, scheme, k, n, seed=0):
-    """n items: about 3/4 under the first k registered keys (k = 0: none), each key presented with a fresh random
-    z, the rest under valid unregistered keys; a period-7 share tampered (harness.tamper: both kinds of key) ->
-    dict(cols: the limb columns u, R[, R'], PK[, PK' | Gen], m; affine: the keys' normal form per item; want: the
-    oracle's verdicts on the limbs)"""
-    key = (scheme, k, n, seed)
-    if key in _MIX:
-        return _MIX[key]
-    sk, gen, P0, P1 = _pool(engine, scheme)
-    rng = np.random.default_rng(77 * n + k + seed)
-    j = REG + rng.integers(0, UNREG, size=n)
-    if k:
-        reg = rng.integers(0, 4, size=n) != 0
-        j[reg] = rng.integers(0, k, size=int(reg.sum()))
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
-    b = {"u": u, "R": R, "PK": P0[j].copy(), "m": m}
-    H.tamper(b, kind_single=scheme == "single", period=7)
-    for f, mod in (("u", R_ORDER), ("m", Q)):  # the classes u + r / m + q have no limb form: the residue
-        for i in range(n):
-            v = M.from_le(b[f][i])
-            if v >= mod:
-                b[f][i] = np.frombuffer(M.le32(v % mod), np.uint8)
-    affine = [b["PK"]] + ([np.ascontiguousarray(P1[j])] if P1 is not None else [])
-    pts = [b["R"]] + ([Rp] if Rp is not None else [])
-    cols = [MC.to_limbs_py(b["u"], R_ORDER)] + [_limbs(p, rng) for p in pts + affine] + [MC.to_limbs_py(b["m"], Q)]
-    out = {"cols": cols, "affine": affine, "want": _oracle(scheme, cols), "j": j}
-    if len(_MIX) > 6:
-        _MIX.pop(next(iter(_MIX)))
-    _MIX[key] = out
-    return out
-
-
-def _keyset(engine, scheme, k, **kw):
-    _, _, P0, P1 = _pool(engine, scheme)
-    return engine.KeySet(scheme, np.ascontiguousarray(P0[:k]),
-                         np.ascontiguousarray(P1[:k]) if P1 is not None else None, **kw)
-
-
-def _to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _poison(n):
-    return torch.full((n,), POISON, dtype=torch.uint8, device=DEV)
-
-
-def _ws(engine, scheme, n):
-    return torch.full((max(engine.keyed_open_mont_workspace_bytes(scheme, n), 4),), 0xA5, dtype=torch.uint8,
-                      device=DEV)
-
-
 def _open_dev(engine, ks, cols, stream=None):
     """-> (verdicts, the workspace's index column, misses)"""
     n = len(cols[0])
-    ok, ws = _poison(n), _ws(engine, ks.scheme, n)
+    ok, ws = _poison(n), _open_mont_ws(engine, ks.scheme, n)
     misses = torch.full((1,), 999, dtype=torch.int32, device=DEV)
     ks.verify_open_mont_dev(*[_to_dev(c) for c in cols], ok, ws, misses=misses, stream=stream)
     torch.cuda.synchronize()
@@ -172,7 +79,7 @@ def test_open_mont_parity(engine, scheme, k):
     sample = slice(0, 40)
     assert all((_normal_form(c[sample]) == a[sample]).all()
                for c, a in zip(b["cols"][1 + NSIG[scheme]:-1], b["affine"]))
-    with _keyset(engine, scheme, k) as ks:
+    with _pool_keyset(engine, scheme, k) as ks:
         for n in NS:
             where = _check(engine, ks, [c[:n] for c in b["cols"]], [a[:n] for a in b["affine"]], b["want"][:n],
                            (scheme, k, n))
@@ -192,7 +99,7 @@ def test_open_mont_equals_the_unkeyed_typed_call(engine, scheme):
     ws = torch.empty(engine.mont_workspace_bytes(n), dtype=torch.uint8, device=DEV)
     getattr(engine, "verify_%s_mont_dev" % scheme)(*[_to_dev(c) for c in cols], ok, ws)
     torch.cuda.synchronize()
-    with _keyset(engine, scheme, 64) as ks:
+    with _pool_keyset(engine, scheme, 64) as ks:
         got = _open_dev(engine, ks, cols)[0]
     assert (got == ok.cpu().numpy()).all(), _diff(got, ok.cpu().numpy())
 
@@ -209,8 +116,8 @@ def test_open_mont_sixteen_items_per_lane(engine, scheme):
     dcols = [tile(c) for c in b["cols"]]
     ok, ref = _poison(n), _poison(n)
     misses = torch.full((1,), 999, dtype=torch.int32, device=DEV)
-    with _keyset(engine, scheme, 64) as ks:
-        ks.verify_open_mont_dev(*dcols, ok, _ws(engine, scheme, n), misses=misses)
+    with _pool_keyset(engine, scheme, 64) as ks:
+        ks.verify_open_mont_dev(*dcols, ok, _open_mont_ws(engine, scheme, n), misses=misses)
         where = _expect_idx(ks, [a[:block] for a in b["affine"]])
     ws = torch.empty(engine.mont_workspace_bytes(n), dtype=torch.uint8, device=DEV)
     getattr(engine, "verify_%s_mont_dev" % scheme)(*dcols, ref, ws)
@@ -234,8 +141,8 @@ def test_open_mont_one_key_in_every_representation(engine, scheme):
     reg = [_limbs(a, rng) for a in A]
     n = 96
     j = np.array([5, 3, 9] * (n // 3))
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
+    u, R, Rp = _sign_items(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
     u[::5, 0] ^= 4
     pts = [R] + ([Rp] if Rp is not None else [])
     keys = []
@@ -245,7 +152,7 @@ def test_open_mont_one_key_in_every_representation(engine, scheme):
         kl[1::6], kl[2::6], kl[5::6] = regl[j][1::6], regl[j][2::6], regl[j][5::6]  # the registered limbs
         keys.append(kl)
     cols = [MC.to_limbs_py(u, R_ORDER)] + [_limbs(p, rng) for p in pts] + keys + [MC.to_limbs_py(m, Q)]
-    want = _oracle(scheme, cols)
+    want = _oracle_mont_cols(scheme, cols)
     assert (want == (np.arange(n) % 5 != 0)).all()
     with engine.KeySet.from_mont_cols(scheme, reg) as ks:
         got, idx, nmiss = _open_dev(engine, ks, cols)
@@ -254,19 +161,6 @@ def test_open_mont_one_key_in_every_representation(engine, scheme):
 
 
 # ---- 3. limbs and z the Rust types cannot hold, in hits and in misses ----------------------------------------
-def _plants(scheme):
-    """(name, column, byte range, value) of every edge class"""
-    top, zero = np.full(32, 0xFF, np.uint8), np.zeros(32, np.uint8)
-    out = [("u >= r", 0, slice(0, 32), np.frombuffer(M.le32(R_ORDER + 5), np.uint8)),
-           ("m >= q", -1, slice(0, 32), np.frombuffer(M.le32(Q), np.uint8))]
-    for c in range(1, 1 + NSIG[scheme]):
-        out += [("nonce %d limbs >= q" % c, c, slice(32, 64), top), ("nonce %d z = 0" % c, c, slice(64, 96), zero)]
-    for c in range(1 + NSIG[scheme], 1 + NSIG[scheme] + NKEY[scheme]):
-        out += [("key %d limbs >= q" % c, c, slice(0, 32), top), ("key %d z = 0" % c, c, slice(64, 96), zero),
-                ("key %d z = q" % c, c, slice(64, 96), np.frombuffer(M.le32(Q), np.uint8))]
-    return out
-
-
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_open_mont_unholdable_limbs_give_zero(engine, scheme):
     """each class in turn, planted in a hit and in a miss that verify otherwise, twice at lane distance (the two
@@ -275,7 +169,7 @@ def test_open_mont_unholdable_limbs_give_zero(engine, scheme):
     lanes = -(-n // 8)
     b = _mixture(engine, scheme, 64, n)
     nk = NKEY[scheme]
-    with _keyset(engine, scheme, 64) as ks:
+    with _pool_keyset(engine, scheme, 64) as ks:
         where = _expect_idx(ks, b["affine"])
         good = b["want"][:lanes] & b["want"][lanes:2 * lanes]
         hit = np.flatnonzero(good & (where[:lanes] != NONE) & (where[lanes:2 * lanes] != NONE))
@@ -287,7 +181,7 @@ def test_open_mont_unholdable_limbs_give_zero(engine, scheme):
             cols[c][rows, span] = value
             want = b["want"].copy()
             sub = sorted(set(rows) | {x + 1 for x in rows} | {x - 1 for x in rows if x})
-            want[sub] = _oracle(scheme, [x[sub] for x in cols])   # (verdicts are per item)
+            want[sub] = _oracle_mont_cols(scheme, [x[sub] for x in cols])   # (verdicts are per item)
             expect = b["want"].copy()
             expect[rows] = 0
             assert (want == expect).all(), name
@@ -318,8 +212,8 @@ def test_open_mont_registered_but_not_a_hit(engine, scheme):
     reg[-1][13, 64:96] = 0                                       # z = 0
     j = rng.integers(0, k, size=n)
     j[:8] = (11, 13, 11, 13, 2, 4, 2, 4)
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
+    u, R, Rp = _sign_items(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
     pts = [R] + ([Rp] if Rp is not None else [])
     keys = [_limbs(a[j], rng) for a in A]
     affine = [a[j].copy() for a in A]
@@ -333,7 +227,7 @@ def test_open_mont_registered_but_not_a_hit(engine, scheme):
         affine[1][[4, 6]] = A[1][4]
         mixed = [4, 6]
     cols = [MC.to_limbs_py(u, R_ORDER)] + [_limbs(p, rng) for p in pts] + keys + [MC.to_limbs_py(m, Q)]
-    want = _oracle(scheme, cols)
+    want = _oracle_mont_cols(scheme, cols)
     assert (want[[0, 1, 2, 3] + mixed] == 0).all() and want[8:].all()
     with engine.KeySet.from_mont_cols(scheme, reg) as ks:
         ok = ks.key_ok()
@@ -353,21 +247,22 @@ def test_open_mont_small_order_keys_hit(engine, scheme):
     sk, gen, P0, P1 = _pool(engine, scheme)
     rng = np.random.default_rng(43)
     ident = np.frombuffer(M.le32(0) + M.le32(1), np.uint8)
-    small = np.frombuffer(M.point_bytes(TK._small_order_point()), np.uint8)
+    small = np.frombuffer(M.point_bytes(TM.order8_point()), np.uint8)
     k, n = 8, 64
     A = [np.ascontiguousarray(P[:k]).copy() for P in ([P0] + ([P1] if P1 is not None else []))]
     A[0][1], A[0][2] = ident, small
     j = rng.integers(0, k, size=n)
     j[:16] = [1, 2] * 8
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
+    u, R, Rp = _sign_items(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
     if scheme != "double":  # under the identity as PK, u*G == R verifies for R = u*G: sign with sk = 0
         z = np.zeros_like(sk[j[:16:2]])
-        u[:16:2], R[:16:2] = _sign(engine, scheme, z, gen[j[:16:2]] if gen is not None else None, m[:16:2], r[:16:2])[:2]
+        u[:16:2], R[:16:2] = _sign_items(engine, scheme, z, gen[j[:16:2]] if gen is not None else None, m[:16:2],
+                                         r[:16:2])[:2]
     pts = [R] + ([Rp] if Rp is not None else [])
     cols = [MC.to_limbs_py(u, R_ORDER)] + [_limbs(p, rng) for p in pts] + [_limbs(a[j], rng) for a in A] + \
         [MC.to_limbs_py(m, Q)]
-    want = _oracle(scheme, cols)
+    want = _oracle_mont_cols(scheme, cols)
     assert 0 < want.sum() < n
     with engine.KeySet(scheme, *A) as ks:
         assert (ks.key_ok() == 1).all()
@@ -391,10 +286,10 @@ def test_open_mont_dev_contract(engine, scheme):
     p = lambda t: vp(t.data_ptr())
     stream = vp(torch.cuda.current_stream().cuda_stream)
     need = engine.keyed_open_mont_workspace_bytes(scheme, n)
-    ws = _ws(engine, scheme, n)
+    ws = _open_mont_ws(engine, scheme, n)
     base = {"u": p(d[0]), "R": p(d[1]), "Rp": p(d[2]) if ns == 2 else null, "ka": p(d[1 + ns]),
             "kb": p(d[2 + ns]) if nk == 2 else null, "m": p(d[-1]), "ws": p(ws)}
-    ks = _keyset(engine, scheme, 64)
+    ks = _pool_keyset(engine, scheme, 64)
     try:
         def verify(h, nn, okt, wsb, **over):
             a = dict(base, **over)
@@ -444,7 +339,7 @@ def test_open_mont_capture_and_replay(engine):
     scheme, n, k = "double", 4099, 8
     sk, gen, P0, P1 = _pool(engine, scheme)
     rng = np.random.default_rng(6)
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
     base = rng.integers(0, k, size=n)
     batches = []
     for miss in (np.zeros(n, bool), rng.integers(0, 8, size=n) == 0, np.ones(n, bool)):
@@ -452,12 +347,12 @@ def test_open_mont_capture_and_replay(engine):
         u, R, Rp = engine.sign_double(sk[j], m, r)
         u[rng.integers(0, 16, size=n) == 0, 0] ^= 8
         cols = [MC.to_limbs_py(u, R_ORDER)] + [_limbs(x, rng) for x in (R, Rp, P0[j], P1[j])] + [MC.to_limbs_py(m, Q)]
-        want = _oracle(scheme, cols)
+        want = _oracle_mont_cols(scheme, cols)
         assert 0 < want.sum() < n
         batches.append((cols, want, int(miss.sum())))
-    with _keyset(engine, scheme, k) as ks:
+    with _pool_keyset(engine, scheme, k) as ks:
         d = [_to_dev(c) for c in batches[-1][0]]
-        ok, ws = _poison(n), _ws(engine, scheme, n)
+        ok, ws = _poison(n), _open_mont_ws(engine, scheme, n)
         misses = torch.full((1,), 999, dtype=torch.int32, device=DEV)
         side = torch.cuda.Stream(device=DEV)
         torch.cuda.synchronize()
@@ -491,19 +386,19 @@ def test_open_mont_captured_call_keeps_its_k_and_sees_replaced_keys(engine, sche
     j = rng.integers(0, 16, size=n)
     j[:16] = rng.permutation(16)
     j[16:24] = REG + 1                                            # the key that will replace key 3
-    m, r = TK._scalars(rng, n, 0x3F), TK._scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
+    m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
+    u, R, Rp = _sign_items(engine, scheme, sk[j], gen[j] if gen is not None else None, m, r)
     u[::8, 0] ^= 8
     pts = [R] + ([Rp] if Rp is not None else [])
     A = [P0] + ([P1] if P1 is not None else [])
     cols = [MC.to_limbs_py(u, R_ORDER)] + [_limbs(x, rng) for x in pts + [a[j] for a in A]] + [MC.to_limbs_py(m, Q)]
-    want = _oracle(scheme, cols)
+    want = _oracle_mont_cols(scheme, cols)
     assert (want == (np.arange(n) % 8 != 0)).all()
     newer = j >= k0
     sl = lambda P, lo, hi: np.ascontiguousarray(P[lo:hi]) if P is not None else None
     d = [_to_dev(c) for c in cols]
     with engine.KeySet.reserved(scheme, 16, sl(P0, 0, k0), sl(P1, 0, k0)) as ks:
-        ok, ws = _poison(n), _ws(engine, scheme, n)
+        ok, ws = _poison(n), _open_mont_ws(engine, scheme, n)
         misses = torch.full((1,), 999, dtype=torch.int32, device=DEV)
         side = torch.cuda.Stream(device=DEV)
         torch.cuda.synchronize()
@@ -539,9 +434,6 @@ def test_open_mont_captured_call_keeps_its_k_and_sees_replaced_keys(engine, sche
 
 
 # ---- 7. the two-launch front gives the same outputs ------------------------------------------------------------
-FRONT_N = 4099  # the block both processes build; tiled to NS[-1] for the lanes that share an inversion
-
-
 def test_open_mont_two_launch_front_in_a_subprocess(engine):
     """DSV_OPEN_MONT_FUSED=0 and =1 in processes of their own (side by side): the index column, valid, misses and
     ok of the two-launch front (k_normalize_uvz over all points, then k_index_lookup) equal the fused kernel's,
@@ -554,7 +446,7 @@ sys.path.insert(0, %r)
 sys.path.insert(0, %r)
 import torch
 from schnorr_amd import engine as E, _lib
-import test_gpu_keyset_open_mont as T
+import keyed_cases as T
 E.init(0)
 out = {}
 up = lambda x: (x + 255) // 256 * 256
@@ -572,10 +464,10 @@ for scheme in T.SCHEMES:
     for row, (name, c, span, value) in enumerate(T._plants(scheme)):
         big[c][20 + row, span] = value
     for k in (0, 64):
-        with T._keyset(E, scheme, k) as ks:
+        with T._pool_keyset(E, scheme, k) as ks:
             for n in (65, T.FRONT_N, T.NS[-1]):
                 cols = [c[:n] for c in big]
-                ok, ws = T._poison(n), T._ws(E, scheme, n)
+                ok, ws = T._poison(n), T._open_mont_ws(E, scheme, n)
                 misses = torch.full((1,), 999, dtype=torch.int32, device=T.DEV)
                 ks.verify_open_mont_dev(*[T._to_dev(c) for c in cols], ok, ws, misses=misses)
                 torch.cuda.synchronize()
@@ -594,7 +486,7 @@ for scheme in T.SCHEMES:
 np.savez(sys.argv[1], **out)
 # a dead set: its device was shut down under it
 L = _lib.load()
-ks = T._keyset(E, "single", 8)
+ks = T._pool_keyset(E, "single", 8)
 h = ctypes.c_void_p(ks._h.value)
 E.shutdown()
 okh = np.full(4, 7, np.uint8)
@@ -656,7 +548,7 @@ def _host_batch(engine, scheme):
         tile = lambda a: np.ascontiguousarray(np.tile(a[:HOST_BLOCK], (times,) + (1,) * (a.ndim - 1))[:nmax])
         sigs, pks, msgs, views = MC.as_records(scheme, [tile(c) for c in b["cols"]])
         assert views[1].strides[0] == sigs.dtype.itemsize > 96 and views[1 + NSIG[scheme]].strides[0] >= 160
-        ks = _keyset(engine, scheme, 64)
+        ks = _pool_keyset(engine, scheme, 64)
         miss = _expect_idx(ks, [a[:HOST_BLOCK] for a in b["affine"]]) == NONE
         _HOST[scheme] = {"views": views, "hold": (sigs, pks, msgs), "ks": ks, "miss": tile(miss),
                          "want": tile(b["want"])}

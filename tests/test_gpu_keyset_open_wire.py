@@ -1,8 +1,8 @@
 """The key cache for serialized records on the GPU (dsv_keyset_lookup_wire*, dsv_verify_*_keyed_open_wire*): the
 wire index of a key set and the open-set verify by compressed key.  The expected verdict is always the CPU
 oracle's on the records themselves, O.verify_<scheme>_wire(sig, pk, m) — registering a key never changes it — and
-`misses` is the count of a Python dict over O.compress of the keys with key_ok == 1.  Keys and items are generated
-the way tests/test_gpu_keyset.py, tests/test_gpu_keyset_lookup.py and tests/test_gpu_keyed_wire.py do."""
+`misses` is the count of a Python dict over O.compress of the keys with key_ok == 1.  Keys and items come from
+tests/keyed_cases.py."""
 import ctypes
 
 import numpy as np
@@ -14,9 +14,8 @@ import harness as H
 import mont_cases as MC
 import oracle_lib as O
 import pymodel as M
-from test_gpu_keyed_wire import _enc, _key_records, _non_squares, _oracle_wire, _sig, _to_dev
-from test_gpu_keyset import _diff, _keys, _poison, _scalars
-from test_gpu_keyset_lookup import _lookup_dev, _value_batch
+from keyed_cases import (_diff, _enc, _expect_rec, _key_records, _keys, _lookup_dev, _non_squares, _oracle_wire, _poison,
+                         _scalars, _sig, _to_dev, _value_batch, _where_rec)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -28,23 +27,10 @@ Q = M.Q
 
 
 # ---- the model: a dict over the canonical records of the valid registered keys, lowest index first ----------
-def _where_rec(P0, P1, key_ok):
-    rec = _key_records(P0, P1)
-    d = {}
-    for j in range(len(rec)):
-        if key_ok[j]:
-            d.setdefault(rec[j].tobytes(), j)
-    return d
-
-
 def _where_of_records(records, key_ok):
     """the model of a set built from key RECORDS: the canonical record of every decodable point"""
     pts = [O.decompress(np.ascontiguousarray(records[:, c:c + 32]))[0] for c in range(0, records.shape[1], 32)]
     return _where_rec(pts[0], pts[1] if len(pts) == 2 else None, key_ok)
-
-
-def _expect_rec(where, pk):
-    return np.array([where.get(pk[i].tobytes(), NONE) for i in range(len(pk))], dtype=np.uint32)
 
 
 def _lookup_wire_dev(ks, pk, stream=None):
@@ -94,7 +80,7 @@ def _check(engine, ks, sig, pk, m, want, nmiss, what):
     assert misses == nmiss, (what, "host", misses, nmiss)
 
 
-# ---- the items of tests/test_gpu_keyset_lookup.py, serialized; the oracle's wire verdicts, computed once -----
+# ---- the items of keyed_cases._value_batch, serialized; the oracle's wire verdicts, computed once -----
 _WIRE_VALUE = {}
 
 

@@ -3,7 +3,7 @@ the set dsv_keyset_create builds over the final key list — key_ok, table entri
 by-index verdicts against the CPU oracle —, both indices have the canonical layout of tests/keyset_index_model.py
 (clusters, wrap-around, duplicates, invalid keys), the open-set forms return the unkeyed verdicts before and after, a
 captured graph keeps its k, a full set never fills up, refused calls change nothing, and verify calls run beside
-replaces.  Keys and items are generated the way tests/test_gpu_keyset.py does; every batch holds valid and invalid
+replaces.  Keys and items come from tests/keyed_cases.py; every batch holds valid and invalid
 items.  Shapes: capacity 8 (the smallest index: 64 slots), 16, and 40 (128 slots)."""
 import ctypes
 import threading
@@ -15,8 +15,7 @@ import torch
 import keyset_index_model as IM
 import oracle_lib as O
 import pymodel as M
-from test_gpu_keyset import _dev, _diff, _keys, _oracle, _poison, _scalars
-from test_gpu_keyset_lookup import _le
+from keyed_cases import _dev, _diff, _keys, _le, _oracle, _poison, _scalars, _sign_items
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,22 +34,13 @@ def _cols(P0, P1, rows=slice(None)):
     return [_c(P0[rows])] + ([_c(P1[rows])] if P1 is not None else [])
 
 
-def _sign(engine, scheme, sk, gen, m, r):
-    """(u, R, Rp or None)"""
-    if scheme == "single":
-        return engine.sign_single(sk, m, r) + (None,)
-    if scheme == "double":
-        return engine.sign_double(sk, m, r)
-    return engine.sign_vargen(sk, gen, m, r) + (None,)
-
-
 def _items(engine, scheme, sk, gen, P0, P1, j, seed):
     """len(j) items, item i signed under key j[i] of the pool (sk, gen, P0, P1); every 8th has a bit of u flipped,
     every 8th + 3 a bit of m; A / B: the items' own key columns"""
     rng = np.random.default_rng(seed)
     n = len(j)
     m, r = _scalars(rng, n, 0x3F), _scalars(rng, n, 0x07)
-    u, R, Rp = _sign(engine, scheme, _c(sk[j]), _c(gen[j]) if gen is not None else None, m, r)
+    u, R, Rp = _sign_items(engine, scheme, _c(sk[j]), _c(gen[j]) if gen is not None else None, m, r)
     u[::8, 0] ^= 8
     m[3::8, 0] ^= 1
     return {"scheme": scheme, "u": u, "R": R, "Rp": Rp, "m": m, "A": _c(P0[j]), "B": _c(P1[j]) if P1 is not None else None,

@@ -283,8 +283,8 @@ _T8 = None
 def _order8():
     global _T8
     if _T8 is None:
-        import test_halfgcd as TH
-        _T8 = TH.order8_point()
+        import torsion_model as TM
+        _T8 = TM.order8_point()
     return _T8
 
 

@@ -279,9 +279,9 @@ def test_order8_torsion_components_valid_and_invalid(engine):
     """Keys and nonce points carrying an order-8 component: the signature is valid exactly when the
     torsion parts cancel (c*k1 = k2 mod 8).  Both GPU formulations (classic 250-bit chain and the
     half-size-scalar form, halfgcd.h) must reproduce the reference equation's verdicts."""
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
-    rnd = TH.rnd
+    import torsion_model as TM
+    t8 = TM.order8_point()
+    rnd = TM.rnd
     rows = {"u": [], "R": [], "PK": [], "m": []}
     want = []
     while sum(want) < 3 or len(want) < 48:
@@ -495,7 +495,7 @@ def test_reference_fixtures_on_gpu(engine):
     hash, decompression, and the GPU's own StdRng generator against the raw keystream.  Skipped while
     there is none."""
     import reference_fixtures as RF
-    from test_oracle import Backend, _check_reference_records
+    from reference_checks import Backend, _check_reference_records
     recs = RF.load()
     if not recs:
         pytest.skip("no tests/golden/reference_* fixture present: parity unpinned (DESIGN.md §2)")
@@ -509,7 +509,7 @@ def test_predicted_records_of_every_kind_on_gpu(engine):
     all three schemes (verdicts, wire verdicts, challenge bytes incl. the 5-input double hash),
     decompression edge cases and the StdRng stream."""
     import json, os
-    from test_oracle import Backend, _check_reference_records
+    from reference_checks import Backend, _check_reference_records
     P = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "predicted_reference.json")))
     seen = _check_reference_records(P["records"], Backend(engine, engine.decompress_points,
                                                           stdrng=lambda seed, n: engine.stdrng_sign_inputs(seed, n)))

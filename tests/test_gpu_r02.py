@@ -13,14 +13,10 @@ import pytest
 import harness as H
 import oracle_lib as O
 import pymodel as M
+from gpu_cases import _dev_col, _mixed_arrays
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def test_double_batch_at_config_size_with_oracle_sample(engine):
@@ -55,7 +51,7 @@ def test_fused_double_kernel_equals_two_single_equation_passes(engine):
     for i in range(7, n, 13):                       # break ONLY the plain half
         d["PK"][i] = d["PK"][(i + 1) % n]
     want = O.verify_double(d["u"], d["R"], d["Rp"], d["PK"], d["PKp"], d["m"], nthreads=8)
-    t = {k: _dev(v) for k, v in d.items() if k in ("u", "R", "Rp", "PK", "PKp", "m")}
+    t = {k: _dev_col(v) for k, v in d.items() if k in ("u", "R", "Rp", "PK", "PKp", "m")}
     c = torch.empty((n, 32), dtype=torch.uint8, device="cuda:0")
     valid = torch.empty(n, dtype=torch.uint8, device="cuda:0")
     ws = torch.empty(engine.workspace_bytes(n), dtype=torch.uint8, device="cuda:0")
@@ -104,7 +100,7 @@ def test_split_kinds_matches_numpy(engine, n):
         kinds[5] = 2                                # an invalid kind lands in neither list
         kinds[n - 3] = 255
     want_s, want_d = np.nonzero(kinds == 0)[0], np.nonzero(kinds == 1)[0]
-    k = _dev(kinds)
+    k = _dev_col(kinds)
     idx_s = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     idx_d = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     scratch = torch.empty(engine.split_scratch_bytes(n), dtype=torch.uint8, device="cuda:0")
@@ -117,26 +113,6 @@ def test_split_kinds_matches_numpy(engine, n):
     assert int((idx_s[len(want_s):] != -1).sum()) == 0   # nothing written past the counts
 
 
-def _mixed_arrays(n, seed):
-    rng = np.random.default_rng(seed)
-    kinds = rng.integers(0, 2, size=n, dtype=np.uint8)
-    si, di = np.nonzero(kinds == 0)[0], np.nonzero(kinds == 1)[0]
-    ds = O.keygen_sign_single(len(si), seed, nthreads=8)
-    dd = O.keygen_sign_double(len(di), seed + 1, nthreads=8)
-    H.tamper(ds, period=5)
-    H.tamper(dd, period=7)
-    cols = {k: np.zeros((n, w), np.uint8) for k, w in (("u", 32), ("R", 64), ("Rp", 64), ("PK", 64),
-                                                       ("PKp", 64), ("m", 32))}
-    for k in ("u", "R", "PK", "m"):
-        cols[k][si] = ds[k]
-    for k in cols:
-        cols[k][di] = dd[k]
-    want = np.zeros(n, np.uint8)
-    want[si] = O.verify_single(ds["u"], ds["R"], ds["PK"], ds["m"], nthreads=8)
-    want[di] = O.verify_double(dd["u"], dd["R"], dd["Rp"], dd["PK"], dd["PKp"], dd["m"], nthreads=8)
-    return kinds, cols, want, len(di)
-
-
 def test_mixed_batch_split_on_the_device(engine):
     """BASELINE.json configs[4] path on one GPU: arbitrary interleaving of single and double
     signatures in one structure of arrays, dsv_verify_mixed_dev (device-side split, row gathers,
@@ -146,16 +122,16 @@ def test_mixed_batch_split_on_the_device(engine):
     n = 5000 + 7
     kinds, cols, want, nd = _mixed_arrays(n, 11)
     assert 0 < want.sum() < n
-    t = {k: _dev(v) for k, v in cols.items()}
+    t = {k: _dev_col(v) for k, v in cols.items()}
     ok = torch.full((n,), 7, dtype=torch.uint8, device="cuda:0")
     ws = torch.empty(engine.mixed_workspace_bytes(n), dtype=torch.uint8, device="cuda:0")
-    engine.verify_mixed_dev(_dev(kinds), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd, ok, ws)
+    engine.verify_mixed_dev(_dev_col(kinds), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd, ok, ws)
     torch.cuda.synchronize()
     assert np.array_equal(ok.cpu().numpy(), want)
     # all single / all double
     for fill in (0, 1):
         k2 = np.full(n, fill, np.uint8)
-        engine.verify_mixed_dev(_dev(k2), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"],
+        engine.verify_mixed_dev(_dev_col(k2), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"],
                                 n * fill, ok, ws)
         torch.cuda.synchronize()
         w2 = np.where(kinds == fill, want, 0)
@@ -164,12 +140,12 @@ def test_mixed_batch_split_on_the_device(engine):
     k3 = kinds.copy()
     victim = int(np.nonzero((kinds == 0) & (want == 1))[0][0])
     k3[victim] = 9
-    engine.verify_mixed_dev(_dev(k3), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd, ok, ws)
+    engine.verify_mixed_dev(_dev_col(k3), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd, ok, ws)
     torch.cuda.synchronize()
     got = ok.cpu().numpy()
     assert got.sum() == 0                           # count of kind 0 no longer matches n - n_double
     # declared count off by one: no usable verdicts, no fault
-    engine.verify_mixed_dev(_dev(kinds), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd - 1, ok, ws)
+    engine.verify_mixed_dev(_dev_col(kinds), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], nd - 1, ok, ws)
     torch.cuda.synchronize()
     assert int(ok.sum()) == 0
 
@@ -223,8 +199,8 @@ def test_signing_rejects_non_canonical_scalars(engine):
     u = torch.zeros((n, 32), dtype=torch.uint8, device="cuda:0")
     R = torch.zeros((n, 64), dtype=torch.uint8, device="cuda:0")
     PK = torch.zeros((n, 64), dtype=torch.uint8, device="cuda:0")
-    engine.sign_single_dev(_dev(bad_sk), _dev(m), _dev(bad_r), u, R)
-    engine.public_keys_dev(_dev(bad_sk), 0, PK)
+    engine.sign_single_dev(_dev_col(bad_sk), _dev_col(m), _dev_col(bad_r), u, R)
+    engine.public_keys_dev(_dev_col(bad_sk), 0, PK)
     torch.cuda.synchronize()
     u, R, PK = u.cpu().numpy(), R.cpu().numpy(), PK.cpu().numpy()
     assert (u[3] == 0xFF).all() and (u[5] == 0xFF).all() and (R[5] == 0xFF).all() and (PK[3] == 0xFF).all()

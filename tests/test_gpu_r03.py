@@ -13,14 +13,10 @@ import pytest
 import harness as H
 import oracle_lib as O
 import pymodel as M
+from gpu_cases import _dev_col, _mixed_arrays
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _ext_case(scheme, n, seed):
@@ -74,7 +70,7 @@ def test_projective_entry_points_match_the_oracle(engine, scheme):
     assert np.array_equal(got_m, np.tile(want, reps))
     ok = torch.full((n,), 9, dtype=torch.uint8, device="cuda:0")
     ws = torch.full((engine.ext_workspace_bytes(n),), 0xFF, dtype=torch.uint8, device="cuda:0")
-    getattr(engine, "verify_%s_ext_dev" % scheme)(_dev(d["u"]), *[_dev(p) for p in pts], _dev(d["m"]), ok, ws)
+    getattr(engine, "verify_%s_ext_dev" % scheme)(_dev_col(d["u"]), *[_dev_col(p) for p in pts], _dev_col(d["m"]), ok, ws)
     torch.cuda.synchronize()
     assert np.array_equal(ok.cpu().numpy(), want)
 
@@ -97,7 +93,7 @@ def test_projective_large_batch_shares_one_inversion_among_eight_items(engine):
     tile = lambda a: np.tile(a, (reps, 1))[:n]
     ok = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
     ws = torch.empty(engine.ext_workspace_bytes(n), dtype=torch.uint8, device="cuda:0")
-    engine.verify_single_ext_dev(_dev(tile(d["u"])), _dev(tile(R_uvz)), _dev(tile(PK_uvz)), _dev(tile(d["m"])), ok, ws)
+    engine.verify_single_ext_dev(_dev_col(tile(d["u"])), _dev_col(tile(R_uvz)), _dev_col(tile(PK_uvz)), _dev_col(tile(d["m"])), ok, ws)
     torch.cuda.synchronize()
     assert np.array_equal(ok.cpu().numpy(), np.tile(want, reps)[:n])
     assert 0 < want.sum() < base
@@ -134,30 +130,10 @@ def test_wire_records_resident_in_device_memory(engine, scheme):
     assert 0 < want.sum() < n and want[7] == 0
     ok = torch.full((n,), 5, dtype=torch.uint8, device="cuda:0")
     ws = torch.full((engine.wire_workspace_bytes(n),), 0xFF, dtype=torch.uint8, device="cuda:0")
-    getattr(engine, "verify_%s_wire_dev" % scheme)(_dev(sig), _dev(pk), _dev(d["m"]), ok, ws)
+    getattr(engine, "verify_%s_wire_dev" % scheme)(_dev_col(sig), _dev_col(pk), _dev_col(d["m"]), ok, ws)
     torch.cuda.synchronize()
     assert np.array_equal(ok.cpu().numpy(), want)
     assert np.array_equal(getattr(engine, "verify_%s_wire" % scheme)(sig, pk, d["m"]), want)
-
-
-def _mixed_arrays(n, seed):
-    rng = np.random.default_rng(seed)
-    kinds = rng.integers(0, 2, size=n, dtype=np.uint8)
-    si, di = np.nonzero(kinds == 0)[0], np.nonzero(kinds == 1)[0]
-    ds = O.keygen_sign_single(len(si), seed, nthreads=8)
-    dd = O.keygen_sign_double(len(di), seed + 1, nthreads=8)
-    H.tamper(ds, period=5)
-    H.tamper(dd, period=7)
-    cols = {k: np.zeros((n, w), np.uint8) for k, w in (("u", 32), ("R", 64), ("Rp", 64), ("PK", 64),
-                                                       ("PKp", 64), ("m", 32))}
-    for k in ("u", "R", "PK", "m"):
-        cols[k][si] = ds[k]
-    for k in cols:
-        cols[k][di] = dd[k]
-    want = np.zeros(n, np.uint8)
-    want[si] = O.verify_single(ds["u"], ds["R"], ds["PK"], ds["m"], nthreads=8)
-    want[di] = O.verify_double(dd["u"], dd["R"], dd["Rp"], dd["PK"], dd["PKp"], dd["m"], nthreads=8)
-    return kinds, cols, want, len(di)
 
 
 def test_mixed_batch_out_of_contract_calls_on_a_poisoned_workspace(engine):
@@ -168,12 +144,12 @@ def test_mixed_batch_out_of_contract_calls_on_a_poisoned_workspace(engine):
     import torch
     n = 3000 + 5
     kinds, cols, want, nd = _mixed_arrays(n, 23)
-    t = {k: _dev(v) for k, v in cols.items()}
+    t = {k: _dev_col(v) for k, v in cols.items()}
 
     def run(kv, ndecl):
         ok = torch.full((n,), 7, dtype=torch.uint8, device="cuda:0")
         ws = torch.full((engine.mixed_workspace_bytes(n),), 0xFF, dtype=torch.uint8, device="cuda:0")
-        engine.verify_mixed_dev(_dev(kv), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], ndecl, ok, ws)
+        engine.verify_mixed_dev(_dev_col(kv), t["u"], t["R"], t["Rp"], t["PK"], t["PKp"], t["m"], ndecl, ok, ws)
         torch.cuda.synchronize()
         return ok.cpu().numpy()
 
@@ -189,7 +165,7 @@ def test_mixed_batch_out_of_contract_calls_on_a_poisoned_workspace(engine):
     idx = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     idx2 = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     scratch = torch.empty(engine.split_scratch_bytes(n), dtype=torch.uint8, device="cuda:0")
-    engine.split_kinds_dev(_dev(kinds), idx, idx2, scratch)
+    engine.split_kinds_dev(_dev_col(kinds), idx, idx2, scratch)
     cnt = engine.split_counts(scratch)
     dst = torch.zeros((n, 64), dtype=torch.uint8, device="cuda:0")
     engine.gather_rows_dev(t["R"], idx, n, dst, limit=cnt[0:1])       # count = n > what the split wrote
@@ -209,8 +185,8 @@ def test_mixed_sharded_verifier_refuses_wrong_counts(engine):
     from schnorr_amd.distributed import MixedShardedVerifier
     n = 2048
     kinds, cols, want, nd = _mixed_arrays(n, 29)
-    batch = {k: _dev(v) for k, v in cols.items()}
-    batch["kinds"] = _dev(kinds)
+    batch = {k: _dev_col(v) for k, v in cols.items()}
+    batch["kinds"] = _dev_col(kinds)
     good = MixedShardedVerifier(n, nd, 1, 0, "cuda:0", collective=False)
     out = good(batch, batch["kinds"]).cpu().numpy()
     assert np.array_equal(out, want) and good.local_counts() == (n - nd, nd)
@@ -249,7 +225,7 @@ def test_half_gcd_near_equal_remainders_do_not_spin(engine):
         ws = torch.empty(engine.workspace_bytes(n), dtype=torch.uint8, device="cuda:0")
         valid = torch.ones(n, dtype=torch.uint8, device="cuda:0")
         os.environ.pop("DSV_QUAD", None)
-        engine.verify_core_dev(_dev(uu), _dev(le(cs)), valid, _dev(PK), _dev(R), ok, ws)
+        engine.verify_core_dev(_dev_col(uu), _dev_col(le(cs)), valid, _dev_col(PK), _dev_col(R), ok, ws)
         torch.cuda.synchronize()
         assert ok.cpu().numpy().tolist() == [0 if tampered else 1] * n
     # the same scalars through the oracle's plain equation u*G + c*PK == R
@@ -363,9 +339,9 @@ def test_device_lattice_scalars_satisfy_the_congruences(engine):
 def test_vargen_order8_torsion_components_valid_and_invalid(engine):
     """Generators, keys and nonce points carrying an order-8 component through the three-scalar
     kernel: valid exactly when the torsion parts cancel — the reference equation's verdicts (oracle)."""
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
-    rnd = TH.rnd
+    import torsion_model as TM
+    t8 = TM.order8_point()
+    rnd = TM.rnd
     rows = {"u": [], "R": [], "PK": [], "Gen": [], "m": []}
     want = []
     while sum(want) < 3 or len(want) < 48:

@@ -13,15 +13,11 @@ import pytest
 import mont_cases as C
 import pymodel as M
 import oracle_lib as O
+from gpu_cases import _dev_col
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEEDS = {"single": 31, "double": 32, "vargen": 33}
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 @pytest.mark.parametrize("scheme", ["single", "double", "vargen"])
@@ -49,7 +45,7 @@ def test_montgomery_limb_entry_points_match_the_oracle(engine, scheme):
         del os.environ["DSV_MULTI_SHARDS"]
     ok = torch.full((n,), 9, dtype=torch.uint8, device="cuda:0")
     ws = torch.full((engine.mont_workspace_bytes(n),), 0xFF, dtype=torch.uint8, device="cuda:0")
-    getattr(engine, "verify_%s_mont_dev" % scheme)(*[_dev(c) for c in cols], ok, ws)
+    getattr(engine, "verify_%s_mont_dev" % scheme)(*[_dev_col(c) for c in cols], ok, ws)
     torch.cuda.synchronize()
     assert np.array_equal(ok.cpu().numpy(), want)
 

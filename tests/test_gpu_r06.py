@@ -13,34 +13,11 @@ import pytest
 import torch
 
 import harness as H
-import oracle_lib as O
+from gpu_cases import COLS, _oracle, _run, _signed
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COLS = {"single": ("u", "R", "PK", "m"), "double": ("u", "R", "Rp", "PK", "PKp", "m"),
-        "vargen": ("u", "R", "PK", "Gen", "m")}
-
-
-def _signed(n, seed, scheme="single"):
-    d = getattr(O, "keygen_sign_" + scheme)(n, seed, nthreads=8)
-    return {k: d[k] for k in COLS[scheme]}
-
-
-def _oracle(a, scheme):
-    return getattr(O, "verify_" + scheme)(*[a[k] for k in COLS[scheme]], nthreads=8)
-
-
-def _run(engine, a, scheme, window_bits=0, accepted_out=None):
-    n = len(a["u"])
-    t = [torch.from_numpy(np.ascontiguousarray(a[k])).to(DEV) for k in COLS[scheme]]
-    ok = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
-    ws = torch.empty(engine.rlc_workspace_bytes(n, window_bits), dtype=torch.uint8, device=DEV)
-    acc = getattr(engine, "verify_%s_rlc_dev" % scheme)(*t, ok, ws, window_bits=window_bits, accepted_out=accepted_out)
-    torch.cuda.synchronize()
-    return acc, ok.cpu().numpy()
-
-
 @pytest.fixture
 def forced_groups(engine):
     """sub-groups forced for the test, the automatic choice restored afterwards"""
@@ -92,13 +69,13 @@ def test_a_small_order_component_fails_only_its_own_sub_group(engine, forced_gro
 import sys
 sys.path.insert(0, "tests")
 import numpy as np, torch
-import oracle_lib as O, test_halfgcd as TH, test_gpu_rlc as T
+import oracle_lib as O, torsion_model as TM, gpu_cases as T
 from schnorr_amd import engine as E
 E.init(0)
 n = 4000
 d = O.keygen_sign_single(n, 611, nthreads=8)
 a = {k: d[k].copy() for k in ("u", "R", "PK", "m")}
-rows = T._torsion_rows(TH.order8_point(), TH.rnd, 1, True)
+rows = T._torsion_rows(TM.order8_point(), TM.rnd, 1, True)
 for k in rows:
     a[k][2500] = rows[k][0]
 want = O.verify_single(a["u"], a["R"], a["PK"], a["m"], nthreads=8)

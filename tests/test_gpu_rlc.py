@@ -14,38 +14,10 @@ import torch
 import harness as H
 import oracle_lib as O
 import pymodel as M
+from gpu_cases import COLS, _oracle, _run, _signed, _torsion_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-COLS = {"single": ("u", "R", "PK", "m"), "double": ("u", "R", "Rp", "PK", "PKp", "m"),
-        "vargen": ("u", "R", "PK", "Gen", "m")}
-
-
-def _scheme_of(a):
-    return "double" if "Rp" in a else ("vargen" if "Gen" in a else "single")
-
-
-def _run(engine, a, window_bits=0):
-    scheme = _scheme_of(a)
-    n = len(a["u"])
-    t = [torch.from_numpy(np.ascontiguousarray(a[k])).to(DEV) for k in COLS[scheme]]
-    ok = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
-    ws = torch.empty(engine.rlc_workspace_bytes(n, window_bits), dtype=torch.uint8, device=DEV)
-    accepted = getattr(engine, "verify_%s_rlc_dev" % scheme)(*t, ok, ws, window_bits=window_bits)
-    torch.cuda.synchronize()
-    return accepted, ok.cpu().numpy()
-
-
-def _oracle(a):
-    scheme = _scheme_of(a)
-    return getattr(O, "verify_" + scheme)(*[a[k] for k in COLS[scheme]], nthreads=8)
-
-
-def _signed(n, seed, scheme="single"):
-    d = getattr(O, "keygen_sign_" + scheme)(n, seed, nthreads=8)
-    return {k: d[k] for k in COLS[scheme]}
 
 
 @pytest.mark.parametrize("scheme", ["double", "vargen"])
@@ -56,7 +28,7 @@ def test_double_and_var_generator_schemes(engine, scheme):
     n = 1800
     d = _signed(n, 970 + len(scheme), scheme)
     for bits in (8, 12, 0):
-        accepted, ok = _run(engine, d, bits)
+        accepted, ok = _run(engine, d, window_bits=bits)
         assert accepted == (bits != 0) and ok.all(), bits      # (automatic bits: too small for an aggregate)
     points = [k for k in COLS[scheme] if k not in ("u", "m")]
     for j, field in enumerate(COLS[scheme]):
@@ -68,7 +40,7 @@ def test_double_and_var_generator_schemes(engine, scheme):
             a[field][victim] = d[field][victim + 1]
         want = _oracle(a)
         assert want.sum() == n - 1 and not want[victim], field
-        accepted, ok = _run(engine, a, 8)
+        accepted, ok = _run(engine, a, window_bits=8)
         assert not accepted and np.array_equal(ok, want), field
     a = {k: v.copy() for k, v in d.items()}
     H.tamper(a, period=9)
@@ -77,14 +49,14 @@ def test_double_and_var_generator_schemes(engine, scheme):
     accepted, ok = _run(engine, a)
     assert not accepted and np.array_equal(ok, want)
     # small-order component in ONE point of one item, for every point column: never decided by the aggregate
-    import test_halfgcd as TH
-    t8 = TH.order8_point()
+    import torsion_model as TM
+    t8 = TM.order8_point()
     for field in points:
         a = {k: v.copy() for k, v in d.items()}
         P = H.to_int_point(a[field][50])
         a[field][50] = np.frombuffer(M.point_bytes(M.padd(P, M.pmul(t8, 4))), np.uint8)
         want = _oracle(a)
-        accepted, ok = _run(engine, a, 8)
+        accepted, ok = _run(engine, a, window_bits=8)
         assert not accepted and np.array_equal(ok, want), field
 
 
@@ -98,7 +70,7 @@ def test_all_valid_batch_is_accepted_by_the_aggregate(engine, bits):
         # ... from there on it decides
         reps = -(-((1 << 17) + 5) // 1500)
         d = {k: np.tile(v, (reps, 1))[:(1 << 17) + 5] for k, v in d.items()}
-    accepted, ok = _run(engine, d, bits)
+    accepted, ok = _run(engine, d, window_bits=bits)
     assert accepted and ok.all()
 
 
@@ -114,7 +86,7 @@ def test_one_wrong_signature_sends_the_batch_to_the_per_signature_kernels(engine
             a[field][victim] = d[field][(victim + 1) % n]
         want = O.verify_single(a["u"], a["R"], a["PK"], a["m"], nthreads=8)
         assert want.sum() == n - 1 and not want[victim]
-        accepted, ok = _run(engine, a, bits)
+        accepted, ok = _run(engine, a, window_bits=bits)
         assert not accepted
         assert np.array_equal(ok, want)
 
@@ -141,28 +113,9 @@ def test_malformed_items_stay_out_of_the_sum(engine):
     d["m"][1100] = top
     want = O.verify_single(d["u"], d["R"], d["PK"], d["m"], nthreads=8)
     assert want.sum() == n - 4
-    accepted, ok = _run(engine, d, 8)
+    accepted, ok = _run(engine, d, window_bits=8)
     assert np.array_equal(ok, want)
     assert accepted
-
-
-def _torsion_rows(t8, rnd, count, cancel):
-    """signatures whose key and nonce point carry order-8 components; `cancel`: c*k1 == k2 (mod 8),
-    i.e. VALID under the reference's cofactorless equation"""
-    rows = {"u": [], "R": [], "PK": [], "m": []}
-    while len(rows["u"]) < count:
-        sk, m, rr = rnd.randrange(1, M.R_ORDER), rnd.randrange(M.Q), rnd.randrange(1, M.R_ORDER)
-        k1, k2 = rnd.randrange(1, 8), rnd.randrange(8)
-        pk = M.padd(M.pmul(M.GEN, sk), M.pmul(t8, k1))
-        R = M.padd(M.pmul(M.GEN, rr), M.pmul(t8, k2))
-        c = M.challenge(R, m)
-        if ((c * k1 - k2) % 8 == 0) != cancel:
-            continue
-        rows["u"].append(np.frombuffer(M.le32((rr - c * sk) % M.R_ORDER), np.uint8))
-        rows["R"].append(np.frombuffer(M.point_bytes(R), np.uint8))
-        rows["PK"].append(np.frombuffer(M.point_bytes(pk), np.uint8))
-        rows["m"].append(np.frombuffer(M.le32(m), np.uint8))
-    return {k: np.stack(v) for k, v in rows.items()}
 
 
 def test_small_order_components_are_never_decided_by_the_aggregate(engine):
@@ -170,8 +123,8 @@ def test_small_order_components_are_never_decided_by_the_aggregate(engine):
     exactly when the torsion parts cancel.  Whatever they do, a batch holding such a point must fall back
     — also when all its items are VALID (the aggregate's subgroup test is about the inputs, not the
     verdicts), and when two order-2 defects would cancel in a plain sum of the equations."""
-    import test_halfgcd as TH
-    t8, rnd = TH.order8_point(), TH.rnd
+    import torsion_model as TM
+    t8, rnd = TM.order8_point(), TM.rnd
     n = 900
     base = _signed(n, 940)
     for cancel, count in ((True, 1), (False, 1), (True, 3), (False, 2)):
@@ -182,7 +135,7 @@ def test_small_order_components_are_never_decided_by_the_aggregate(engine):
                 a[k][100 + 250 * j] = rows[k][j]
         want = O.verify_single(a["u"], a["R"], a["PK"], a["m"], nthreads=8)
         assert want.sum() == (n if cancel else n - count)
-        accepted, ok = _run(engine, a, 8)
+        accepted, ok = _run(engine, a, window_bits=8)
         assert not accepted, (cancel, count)
         assert np.array_equal(ok, want)
     # two items with the SAME order-2 defect: R + T2 signed as if it were R (T2 = (0, -1), so R + T2 =
@@ -201,7 +154,7 @@ def test_small_order_components_are_never_decided_by_the_aggregate(engine):
     want = O.verify_single(a["u"], a["R"], a["PK"], a["m"], nthreads=8)
     assert want.sum() == n - 2
     for _ in range(6):  # fresh weights every call
-        accepted, ok = _run(engine, a, 8)
+        accepted, ok = _run(engine, a, window_bits=8)
         assert not accepted and np.array_equal(ok, want)
 
 
@@ -214,7 +167,7 @@ def test_point_off_the_curve_takes_the_per_signature_path(engine):
     ws0 = torch.empty(engine.workspace_bytes(n), dtype=torch.uint8, device=DEV)
     engine.verify_single_dev(t["u"], t["R"], t["PK"], t["m"], ok0, ws0)
     torch.cuda.synchronize()
-    accepted, ok = _run(engine, d, 8)
+    accepted, ok = _run(engine, d, window_bits=8)
     assert not accepted
     assert np.array_equal(ok, ok0.cpu().numpy())
 
@@ -236,7 +189,7 @@ def test_argument_checks(engine):
     assert rc == -2
     accepted, got = _run(engine, d)  # tiny batch, default bits: the per-signature kernels
     assert not accepted and got.all()
-    accepted, got = _run(engine, d, 4)
+    accepted, got = _run(engine, d, window_bits=4)
     assert accepted and got.all()
     acc0 = ctypes.c_int(5)
     rc = L.dsv_verify_single_rlc_dev(None, None, None, None, ctypes.c_size_t(0), None, None, None, ctypes.c_int(0),

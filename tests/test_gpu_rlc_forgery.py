@@ -24,6 +24,7 @@ import dispatch_edges as D
 import forgery_sets as F
 import mont_cases as C
 import oracle_lib as O
+from gpu_cases import _dev_col
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -73,13 +74,9 @@ def forged(scheme, kind, pair):
     return _FORGED[key]
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _run_dev(engine, arm, scheme, a, bits, groups=0):
     n = len(a["u"])
-    t = [_dev(a[k]) for k in F.FIELDS[scheme]]
+    t = [_dev_col(a[k]) for k in F.FIELDS[scheme]]
     ok = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
     ws = torch.empty(engine.rlc_workspace_bytes(n, bits), dtype=torch.uint8, device=DEV)
     arm(groups)
@@ -170,7 +167,7 @@ def test_wire_form_rejects_cancelling_forgeries(engine, scheme):
     wire_oracle = getattr(O, "verify_%s_wire" % scheme)
 
     def run(arm, a):
-        t = [_dev(x) for x in _wire(scheme, a)]
+        t = [_dev_col(x) for x in _wire(scheme, a)]
         ok = torch.full((n,), 5, dtype=torch.uint8, device=DEV)
         ws = torch.empty(engine.wire_rlc_workspace_bytes(n, 0), dtype=torch.uint8, device=DEV)
         arm()
@@ -209,7 +206,7 @@ def test_mixed_batch_rejects_cancelling_forgeries(engine):
             if k in s:
                 t[0::2] = s[k]
             t[1::2] = d[k]
-            out[k] = _dev(t)
+            out[k] = _dev_col(t)
         return out
 
     kinds = (torch.arange(n, device=DEV) & 1).to(torch.uint8)
@@ -308,7 +305,7 @@ def test_keyed_form_rejects_cancelling_forgeries(engine, scheme, k, kind, same):
         ok = torch.full((N,), 7, dtype=torch.uint8, device=DEV)
         ws = torch.empty(engine.keyed_rlc_workspace_bytes(N, ks.k, 8), dtype=torch.uint8, device=DEV)
         arm()
-        acc = ks.verify_rlc_dev(*[_dev(c) for c in cols], ok, ws, window_bits=8)
+        acc = ks.verify_rlc_dev(*[_dev_col(c) for c in cols], ok, ws, window_bits=8)
         torch.cuda.synchronize()
         return acc, ok.cpu().numpy()
 

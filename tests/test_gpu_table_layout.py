@@ -20,7 +20,7 @@ import torch
 import harness as H
 import oracle_lib as O
 import pymodel as M
-import test_joint_windows as JW
+import joint_model as JW
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -5,41 +5,10 @@ tests/test_gpu_parity.py."""
 import random
 
 import pymodel as M
+import torsion_model as TM
 
 rnd = random.Random(2024)
 N = 8 * M.R_ORDER
-
-
-def _sqrt(n, p=M.Q):
-    q, s = p - 1, 0
-    while q % 2 == 0:
-        q //= 2
-        s += 1
-    z = 2
-    while pow(z, (p - 1) // 2, p) != p - 1:
-        z += 1
-    m, c, t, r = s, pow(z, q, p), pow(n, q, p), pow(n, (q + 1) // 2, p)
-    while t != 1:
-        i, tt = 0, t
-        while tt != 1:
-            tt = tt * tt % p
-            i += 1
-        b = pow(c, 1 << (m - i - 1), p)
-        m, c, t, r = i, b * b % p, t * b * b % p, r * b % p
-    return r
-
-
-def order8_point():
-    while True:
-        v = rnd.randrange(M.Q)
-        u2 = (v * v - 1) * pow(1 + M.D * v * v, -1, M.Q) % M.Q
-        if pow(u2, (M.Q - 1) // 2, M.Q) != 1:
-            continue
-        p = (_sqrt(u2), v)
-        assert M.on_curve(p)
-        t = M.pmul(p, M.R_ORDER)
-        if M.pmul(t, 4) != M.IDENTITY:
-            return t
 
 
 def test_half_scalars_congruence_parity_and_size():
@@ -57,7 +26,7 @@ def test_half_scalars_congruence_parity_and_size():
 
 
 def test_half_scalar_check_is_exact_with_torsion():
-    t8 = order8_point()
+    t8 = TM.order8_point(rnd)
     valid = 0
     for _ in range(12):
         sk, m, rr = rnd.randrange(1, M.R_ORDER), rnd.randrange(M.Q), rnd.randrange(1, M.R_ORDER)
@@ -93,7 +62,7 @@ def test_lattice3_congruences_parity_and_size():
 def test_lattice3_check_is_exact_with_torsion():
     """The three-scalar form gives the reference's verdict for generators, keys and nonce points with a
     small-order component: valid iff the torsion parts cancel (u*k0 + c*k1 = k2 mod 8)."""
-    t8 = order8_point()
+    t8 = TM.order8_point(rnd)
     valid = 0
     for _ in range(6):
         sk, m, rr, g = (rnd.randrange(1, M.R_ORDER), rnd.randrange(M.Q), rnd.randrange(1, M.R_ORDER),

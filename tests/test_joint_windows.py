@@ -1,39 +1,11 @@
 """The joint 2-bit window table of k_verify_fixed_half (schnorr_amd/csrc/common.h: joint_slot,
 recode_signed2, top_digit2): the digit-pair -> signed-slot map read from the source reproduces
 da*P + db*R for every pair, and the recoding is exact for both signs.  Integer model only (CPU)."""
-import os
 import random
 import re
 
 import pymodel as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "schnorr_amd", "csrc", "common.h")).read()
-
-# (coefficient of P, coefficient of R) held by each slot, as build_joint_table fills them
-SLOT = {1: (1, 0), 2: (0, 1), 3: (2, 0), 4: (0, 2), 5: (1, 1), 6: (1, -1), 7: (2, 1), 8: (2, -1),
-        9: (1, 2), 10: (-1, 2), 11: (2, 2)}
-A = int("55" * 32, 16)   # bias: digit = 2-bit field - 1, in [-1, 2]
-BIAS = 1
-
-
-def _constants():
-    slots = int(re.search(r"slots = (0x[0-9A-Fa-f]+)ULL", SRC).group(1), 16)
-    neg = int(re.search(r"\(\((0x[0-9A-Fa-f]+)u >> idx\) & 1u\)", SRC).group(1), 16)
-    return slots, neg
-
-
-def joint_slot(ra, rb):
-    slots, neg = _constants()
-    idx = ra * 4 + rb
-    s = (slots >> (4 * idx)) & 15
-    return -s if (neg >> idx) & 1 else s
-
-
-def recode_signed2(s):
-    y = A + s
-    assert 0 <= y < 1 << 256
-    return y
+from joint_model import A, BIAS, SLOT, SRC, joint_slot, recode_signed2
 
 
 def test_every_digit_pair_reads_the_right_combination():
@@ -113,9 +85,9 @@ def test_joint_chain_on_the_curve_equals_the_reference_equation():
     """the device chain on JubJub points (tests/pymodel.py group law): table slots = i*PK + j*R, chain
     = 4*acc + entry from the top window, plus (b*u)*G: identity exactly when u*G + c*PK == R — incl.
     a key with an order-8 component and tampered signatures."""
-    import test_halfgcd as TH
+    import torsion_model as TM
     rnd = random.Random(13)
-    t8 = TH.order8_point()
+    t8 = TM.order8_point()
     cases = 0
     for trial in range(12):
         sk, m, r = rnd.randrange(1, M.R_ORDER), rnd.randrange(M.Q), rnd.randrange(1, M.R_ORDER)

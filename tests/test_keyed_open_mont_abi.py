@@ -118,7 +118,7 @@ def test_front_kernel_register_budget():
     as they come out."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     stamp = _stamp()
     units = ("k_keyed_open_mont.hip", "k_misc.hip")

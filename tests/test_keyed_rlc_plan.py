@@ -197,7 +197,7 @@ def test_chunked_key_sums_reduce_like_the_whole():
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_keyed_rlc_kernels_stay_in_registers():
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_rlc.hip"), _stamp()))
     names = ["k_keyed_rlc_prepILi0E", "k_keyed_rlc_prepILi1E", "k_keyed_rlc_prepILi2E", "k_keyed_rlc_torsion",

@@ -89,7 +89,7 @@ print("ok")
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_decode_kernel_stays_in_registers():
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_wire.hip"), _stamp()))
     kernels = sorted(k for k in info if "k_keyed_wire_decode" in k)

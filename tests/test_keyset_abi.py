@@ -126,7 +126,7 @@ def test_key_recoding_needs_the_bound():
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_keyed_kernels_stay_in_registers():
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed.hip"), _stamp()))
     names = {"k_build_key_tables": 1, "k_verify_keyedILi0E": 1, "k_verify_keyedILi1E": 1, "k_verify_keyedILi2E": 1}

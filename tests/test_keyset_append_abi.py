@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_keyset_lookup_abi import POINTS, _up, cap_of
+from abi_model import POINTS, _up, cap_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POINT_BYTES = 594432
@@ -115,7 +115,7 @@ def test_append_and_lookup_kernels_stay_in_registers():
      and the append kernel, which now serves fresh sets too (first = 0), has kept to since: a fixed
     ceiling.  k_index_lookup<AffineKey<NP>> with the k guard: within the 42 - 68 VGPRs DESIGN.md §10.4 records for
     the kernel without it (one more scalar argument, one compare per slot)."""
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_lookup.hip"), _stamp()))
 

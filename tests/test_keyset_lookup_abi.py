@@ -9,22 +9,11 @@ import sys
 import numpy as np
 import pytest
 
+from abi_model import POINTS, _up, cap_of
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-POINTS = {"single": 1, "double": 2, "vargen": 2}
 CODE = {"single": 0, "double": 1, "vargen": 2}
 M32 = 0xFFFFFFFF
-
-
-def _up(x, a=256):
-    return (x + a - 1) // a * a
-
-
-def cap_of(k):
-    """the smallest power of two >= max(64, 2k)"""
-    cap = 64
-    while cap < 2 * k:
-        cap *= 2
-    return cap
 
 
 def model_hash(key_bytes):
@@ -149,7 +138,7 @@ print("ok")
                     subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0,
                     reason="hipcc not available")
 def test_lookup_kernels_stay_in_registers():
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_lookup.hip"), _stamp()))
     # the affine instantiations of the two index kernels (the fresh set's build is the append kernel at first = 0)

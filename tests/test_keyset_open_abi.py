@@ -88,7 +88,7 @@ def test_open_kernels_register_budget():
     k_verify_fixed_half of the same chain count, compiled by this run.  k_miss_list stays in registers."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     stamp = _stamp()
     with ThreadPoolExecutor(2) as ex:
@@ -117,7 +117,7 @@ def test_item_bodies_have_one_source():
     once, in a header."""
     import re
 
-    from test_isa_guard import CSRC
+    from isa_asm import CSRC
 
     files = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))}
     code = {f: re.sub(r"//[^\n]*", "", s) for f, s in files.items()}  # (comments may name what they like)

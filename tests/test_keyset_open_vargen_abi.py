@@ -57,7 +57,7 @@ def test_vargen_listed_kernel_register_budget():
     VGPRs than k_verify_var, compiled by this run (the bound is the mirrored kernel's figure, not a fixed one)."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     stamp = _stamp()
     with ThreadPoolExecutor(2) as ex:

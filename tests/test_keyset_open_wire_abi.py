@@ -175,7 +175,7 @@ def test_wire_kernels_register_budget():
     points per item."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     stamp = _stamp()
     units = ("k_keyed_open_wire.hip", "k_keyed_lookup.hip", "k_keyed_wire.hip")

@@ -79,7 +79,7 @@ print("ok")
 def test_commit_and_rebuild_kernels_stay_in_registers():
     """k_keyed_replace.hip: the commit, the planar copy and the ordered insertion — for one- and two-point keys, and
     both key forms of the insertion — use no scratch memory, spill no VGPR and take no AGPR"""
-    from test_isa_guard import CSRC, _asm, _kernel_info, _stamp
+    from isa_asm import CSRC, _asm, _kernel_info, _stamp
 
     info = _kernel_info(_asm(os.path.join(CSRC, "k_keyed_replace.hip"), _stamp()))
     kernels = {name: k for name, k in info.items() if "vgprs" in k}

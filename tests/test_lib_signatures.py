@@ -5,7 +5,7 @@ import os
 import re
 
 from schnorr_amd import _lib
-from test_abi import HEADER, declared_symbols
+from abi_model import HEADER, declared_symbols
 
 SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64}
 PROTOTYPE = re.compile(r"\b((?:const\s+)?\w+(?:\s*\*)?)\s*(dsv_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")

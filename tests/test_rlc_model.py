@@ -14,7 +14,7 @@ It pins the three facts the design rests on, independently of the GPU:
 import random
 
 import pymodel as M
-import test_halfgcd as TH
+import torsion_model as TM
 
 R = M.R_ORDER
 
@@ -96,13 +96,13 @@ def test_random_multiples_of_r_do_not_change_a_prime_order_point():
     P = M.pmul(M.GEN, rnd.randrange(1, R))
     e = rnd.randrange(R)
     assert M.pmul(P, e + 16 * R) == M.pmul(P, e)
-    t8 = TH.order8_point()
+    t8 = TM.order8_point()
     assert M.pmul(M.padd(P, t8), e + R) != M.pmul(M.padd(P, t8), e)      # ... and do for any other point
 
 
 def test_cancelling_order_two_defects_pass_the_plain_sum_but_not_the_subgroup_test():
     rnd = random.Random(13)
-    t2 = M.pmul(TH.order8_point(), 4)
+    t2 = M.pmul(TM.order8_point(), 4)
     assert t2 == (0, M.Q - 1)
     items = [_sign(rnd) for _ in range(3)] + [_sign(rnd, torsion_R=t2), _sign(rnd, torsion_R=t2)]
     for it in items[3:]:                                                   # each one alone is invalid
@@ -119,7 +119,7 @@ def test_a_valid_signature_with_cancelling_torsion_still_fails_the_subgroup_test
     """key and nonce point with order-8 components that cancel in the reference's equation (c k1 = k2 mod 8):
     the item is VALID, the batch all valid — and the aggregate must not decide it (the per-signature kernels do)"""
     rnd = random.Random(14)
-    t8 = TH.order8_point()
+    t8 = TM.order8_point()
     while True:
         k1, k2 = rnd.randrange(1, 8), rnd.randrange(8)
         it = _sign(rnd, torsion_R=M.pmul(t8, k2) if k2 else None, torsion_PK=M.pmul(t8, k1))

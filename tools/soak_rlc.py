@@ -35,7 +35,7 @@ import harness as H  # noqa: E402
 import mont_cases as C  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import pymodel as M  # noqa: E402
-import test_halfgcd as TH  # noqa: E402
+import torsion_model as TM  # noqa: E402
 from schnorr_amd import engine as E  # noqa: E402
 
 COLS = {"single": ("u", "R", "PK", "m"), "double": ("u", "R", "Rp", "PK", "PKp", "m"),
@@ -43,7 +43,7 @@ COLS = {"single": ("u", "R", "PK", "m"), "double": ("u", "R", "Rp", "PK", "PKp",
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 E.init(0)
-t8 = TH.order8_point()
+t8 = TM.order8_point()
 SIZES = [40, 700, 4097, (1 << 14) + 3, (1 << 15) - 1, 40000, (1 << 16) + 77, (1 << 17) + 1, (1 << 17) + (1 << 16) + 13, (1 << 18) + 5, (1 << 18) + (1 << 17) + 7]
 total = bad = 0
 t0 = time.time()
