@@ -991,6 +991,85 @@ int dsv_verify_keyed_open_mont_cols(const dsv_keyset *ks, const dsv_column *cols
                                     size_t *misses /* may be NULL */);
 int dsv_verify_keyed_open_mont_cols_submit(const dsv_keyset *ks, const dsv_column *cols /*[4|6|5]*/, size_t n,
                                            uint8_t *ok, dsv_job **job);
+/* ---- key cache census: per-key hit counts and the distinct missed keys ---------------
+ * What a cache needs in order to USE dsv_keyset_append* (admission) and dsv_keyset_replace* (eviction): which
+ * registered keys are cold, which unregistered keys are busy.  The census answers both for one batch, on the
+ * device, next to the verify call: the caller runs it over the key columns it hands to the open-set call, on the
+ * same stream.  It changes no verdict and no other call; the lookup it repeats is that of dsv_keyset_lookup*.
+ *   Keys        as for dsv_keyset_lookup_dev (key_a / key_b, 64 B affine per item), dsv_keyset_lookup_wire_dev
+ *               (records, 32 B per key point) and dsv_verify_keyed_open_mont_dev (key_a_uvz / key_b_uvz, 96 B of
+ *               Montgomery limbs u || v || z per item).
+ *   key_idx_out may be NULL; else u32[n], exactly what dsv_keyset_lookup* of the same form writes (typed form: what
+ *               the open typed call looks up — DSV_KEY_NONE for unusable key limbs).
+ *   hits        may be NULL; else u32[capacity of the set] — sized for the capacity, so that a captured graph
+ *               survives appends.  hits[j] is ADDED the number of items whose lookup result is j (the lowest index
+ *               of an equal valid key).  A call touches only entries below the k it was enqueued with and never
+ *               zeroes any: the caller owns the window (reset, decay).  The counts are uint32 and wrap.
+ *   Miss        every item that is not a hit — an unregistered key, but also a key that is registered but invalid,
+ *               another encoding of a registered key, a registered PK beside another key's second point.  All of
+ *               them appear in the report, so A POLICY MUST EXPECT TO BE OFFERED SUCH KEYS: registering one again
+ *               gives key_ok = 0 or changes nothing about the next lookup.
+ *   Report      entries [0, totals[0]) of miss_rep / miss_count (u32[n] each; entries from totals[0] on are not
+ *               written): one per DISTINCT missed key — compared by all its bytes — with miss_rep = the lowest
+ *               item index that carries it (its bytes are at that row of the caller's own key columns) and
+ *               miss_count = the number of items under it.  The _dev forms leave the order unspecified; the host
+ *               forms return it sorted by count descending, then by representative ascending.
+ *   totals      u32[4] (host forms: size_t[4]): [0] distinct missed keys, [1] missed items, [2] items with unusable
+ *               key limbs (typed form: a limb group >= q or z = 0; they count in [1], have no key bytes to report
+ *               and enter no report entry; the affine and record forms write 0), [3] reserved, written 0.  The sum
+ *               of miss_count is totals[1] - totals[2].
+ *   _dev forms  the checks of dsv_keyset_lookup_dev in their order and with their codes: a NULL handle before
+ *               dsv_init DSV_ERR_NOT_INITIALIZED; n > DSV_MAX_BATCH DSV_ERR_TOO_LARGE; a dead set
+ *               DSV_ERR_NOT_INITIALIZED; n = 0 DSV_OK with nothing enqueued; then, each DSV_ERR_INVALID_ARGUMENT
+ *               with nothing launched and nothing written: a NULL pointer (key_b of a two-point set included;
+ *               key_idx_out and hits may be NULL), key columns that are not 16-byte aligned, uint32 outputs that
+ *               are not 4-byte aligned, a workspace that is not 16-byte aligned or shorter than
+ *               dsv_keyset_census_workspace_bytes(n) (typed form: dsv_keyset_census_mont_workspace_bytes(scheme,
+ *               n)), totals not on the set's device.  Enqueue-only on `stream`, never synchronise, may be captured:
+ *               one straight chain of kernels — four one-lane stores that zero totals, the clearing of the call's
+ *               miss table, (typed form: the *_mont forms' normalisation over the key points alone,) the census,
+ *               the report; no memset node.  A call carries the k it was enqueued with (the stale-k rule of "key
+ *               sets that grow"); on an empty set (k = 0) every item is a miss and nothing is walked.  The result
+ *               is deterministic up to the order of the report.
+ *   Workspace   dsv_keyset_census_workspace_bytes(n) = the miss table: `cap` uint32 slots and `cap` uint32 counts,
+ *               cap = the smallest power of two >= max(64, 2n) (the slot count of a set of n keys, and the same home
+ *               slot: dsv_debug_keyset_home_slot(scheme, n, ...) / dsv_debug_keyset_wire_home_slot(scheme, n, ...)
+ *               predict where a missed key's walk starts), each rounded up to 256.  The typed form adds the
+ *               normalised key columns (64 B per item and key point), the validity bytes (1 B per item) and the
+ *               prefix products (points * (n + 32) * 36 B), each rounded up to 256; 0 for an unknown scheme.
+ *               Device memory; never smaller for a larger n; no GPU needed.
+ *   Host forms  take host arrays (typed form: cols[0] = PK, cols[1] = PK' / Gen objects, 96 B each, stride >= 96),
+ *               stage in chunks of 2^18 items on the set's device, run the census per chunk and merge the chunk
+ *               reports on the host by key bytes (typed form: by the normalised bytes), so the result is the whole
+ *               call's: a representative is the lowest item index of the CALL.  hits is added to as by the _dev
+ *               forms.  They block.
+ *   DSV_CENSUS_LDS_KEYS=n (read by dsv_init): sets with at most n keys (default 4096, at most 16384) count their
+ *               hits per workgroup in LDS, larger ones combine equal indices per wave; 0 sends every set down the
+ *               per-wave path.  Same outputs either way (A/B and cross-check, like DSV_QUAD).
+ *               dsv_debug_census_lds_keys(): the threshold as this process runs it. */
+size_t dsv_keyset_census_workspace_bytes(size_t n);
+size_t dsv_keyset_census_mont_workspace_bytes(int scheme, size_t n);
+int dsv_keyset_census_dev(const dsv_keyset *ks, const void *key_a, const void *key_b /* NULL for single */, size_t n,
+                          void *key_idx_out /* u32[n], may be NULL */,
+                          void *hits /* u32[capacity], ADDED to, may be NULL */, void *miss_rep /* u32[n] */,
+                          void *miss_count /* u32[n] */, void *totals /* u32[4] */, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int dsv_keyset_census_wire_dev(const dsv_keyset *ks, const void *pk_records, size_t n, void *key_idx_out, void *hits,
+                               void *miss_rep, void *miss_count, void *totals, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int dsv_keyset_census_mont_dev(const dsv_keyset *ks, const void *key_a_uvz,
+                               const void *key_b_uvz /* PK' | Gen, NULL for single */, size_t n, void *key_idx_out,
+                               void *hits, void *miss_rep, void *miss_count, void *totals, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int dsv_keyset_census(const dsv_keyset *ks, const uint8_t *key_a, const uint8_t *key_b, size_t n,
+                      uint32_t *key_idx_out, uint32_t *hits, uint32_t *miss_rep, uint32_t *miss_count,
+                      size_t totals[4]);
+int dsv_keyset_census_wire(const dsv_keyset *ks, const uint8_t *pk_records, size_t n, uint32_t *key_idx_out,
+                           uint32_t *hits, uint32_t *miss_rep, uint32_t *miss_count, size_t totals[4]);
+int dsv_keyset_census_mont_cols(const dsv_keyset *ks, const dsv_column *cols /*[1|2]*/, size_t n,
+                                uint32_t *key_idx_out, uint32_t *hits, uint32_t *miss_rep, uint32_t *miss_count,
+                                size_t totals[4]);
+int dsv_debug_census_lds_keys(void);
 /* ---- keyed fast accept: the batch aggregate over a registered key set ----------------
  * Same inputs and the same verdict vector as dsv_verify_*_keyed_dev — ok[] equals theirs bit for bit; what
  * differs is the time.  Per group of up to 2^22 items (cut into sub-groups like the unkeyed fast accept), with

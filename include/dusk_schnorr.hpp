@@ -868,6 +868,18 @@ inline BatchJob verify_batch_var_gen_submit(const std::vector<SignatureVarGen>& 
 // construction.  `KeySet keys(pks, capacity);` reserves room for `capacity` keys, and `keys.append(more)` then
 // registers further keys in place (dsv_keyset_append_mont_cols): it returns the index of the first of them, no
 // registered key moves, and batches submitted before the append returned keep the set they were submitted with.
+// What `keys.census(pks)` returns: what a cache's policy reads to decide whom to admit and whom to evict.
+struct KeyCensus {
+  struct Missed {
+    uint32_t first_item;  // the lowest index in the batch of an item under this key
+    uint32_t count;       // items under it
+  };
+  std::vector<uint32_t> hits;   // per registered key (capacity() entries): the items decided by its tables
+  std::vector<Missed> missed;   // the distinct keys that missed, by count descending, then first_item ascending
+  size_t missed_items = 0;      // items that took the unkeyed path, unusable ones included
+  size_t unusable_items = 0;    // items whose key has no normal form (z = 0, a coordinate the types cannot hold)
+};
+
 template <class Key>
 class BasicKeySet {
   using T = detail::SchemeTraits<Key>;
@@ -986,6 +998,27 @@ class BasicKeySet {
     detail::same_len(sigs.size(), pks.size(), msgs.size(), "KeySet::verify_batch_open_submit");
     return verify_batch_open_submit(sigs.data(), pks.data(), msgs.data(), sigs.size());
   }
+  // The census of a batch's keys against the set (dsv_keyset_census_mont_cols): per registered key the items that
+  // hit it, and the distinct keys that missed — keys are compared by their normal form, whatever their z — each with
+  // its number of items and its first item.  A missed key is not always one worth registering: an invalid key that
+  // is registered, or a registered PK beside another key's second point, is reported too.  Blocks.
+  KeyCensus census(const Key* pks, size_t n) const {
+    KeyCensus c;
+    c.hits.assign(capacity(), 0);
+    if (n == 0) return c;
+    detail::Columns cols{};
+    T::key_cols(pks, cols);
+    std::vector<uint32_t> rep(n), count(n);
+    size_t totals[4] = {0, 0, 0, 0};
+    detail::check(dsv_keyset_census_mont_cols(ks_, cols.c, n, nullptr, c.hits.data(), rep.data(), count.data(), totals),
+                  "dsv_keyset_census_mont_cols");
+    c.missed.resize(totals[0]);
+    for (size_t j = 0; j < totals[0]; j++) c.missed[j] = {rep[j], count[j]};
+    c.missed_items = totals[1];
+    c.unusable_items = totals[2];
+    return c;
+  }
+  KeyCensus census(const std::vector<Key>& pks) const { return census(pks.data(), pks.size()); }
 
  private:
   void drop() noexcept {

@@ -166,6 +166,34 @@ extern "C" {
     pub fn dsv_debug_keyset_slots(ks: *const c_void, form: c_int, out: *mut u32, room: usize,
                                   slots_out: *mut usize) -> c_int;
     pub fn dsv_debug_keyset_replace_exclusive_ns() -> u64;
+    // key cache census (include/dsv.h, "key cache census"): per registered key the items that hit it (hits:
+    // u32[capacity], ADDED to, may be null), and the distinct missed keys as (lowest item index, items) in
+    // miss_rep / miss_count (u32[n] each, entries [0, totals[0])); totals: u32[4] (host forms: usize[4]) = distinct
+    // missed keys, missed items, items with unusable key limbs, 0.  key_idx_out (may be null): the lookup's column.
+    // _dev forms: device pointers, enqueue-only, capturable; host forms block.  Raw exports.
+    pub fn dsv_keyset_census_workspace_bytes(n: usize) -> usize;
+    pub fn dsv_keyset_census_mont_workspace_bytes(scheme: c_int, n: usize) -> usize;
+    pub fn dsv_keyset_census_dev(ks: *const c_void, key_a: *const c_void, key_b: *const c_void, n: usize,
+                                 key_idx_out: *mut c_void, hits: *mut c_void, miss_rep: *mut c_void,
+                                 miss_count: *mut c_void, totals: *mut c_void, workspace: *mut c_void,
+                                 workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn dsv_keyset_census_wire_dev(ks: *const c_void, pk_records: *const c_void, n: usize,
+                                      key_idx_out: *mut c_void, hits: *mut c_void, miss_rep: *mut c_void,
+                                      miss_count: *mut c_void, totals: *mut c_void, workspace: *mut c_void,
+                                      workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn dsv_keyset_census_mont_dev(ks: *const c_void, key_a_uvz: *const c_void, key_b_uvz: *const c_void, n: usize,
+                                      key_idx_out: *mut c_void, hits: *mut c_void, miss_rep: *mut c_void,
+                                      miss_count: *mut c_void, totals: *mut c_void, workspace: *mut c_void,
+                                      workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn dsv_keyset_census(ks: *const c_void, key_a: *const u8, key_b: *const u8, n: usize, key_idx_out: *mut u32,
+                             hits: *mut u32, miss_rep: *mut u32, miss_count: *mut u32, totals: *mut usize) -> c_int;
+    pub fn dsv_keyset_census_wire(ks: *const c_void, pk_records: *const u8, n: usize, key_idx_out: *mut u32,
+                                  hits: *mut u32, miss_rep: *mut u32, miss_count: *mut u32,
+                                  totals: *mut usize) -> c_int;
+    pub fn dsv_keyset_census_mont_cols(ks: *const c_void, cols: *const Column, n: usize, key_idx_out: *mut u32,
+                                       hits: *mut u32, miss_rep: *mut u32, miss_count: *mut u32,
+                                       totals: *mut usize) -> c_int;
+    pub fn dsv_debug_census_lds_keys() -> c_int;
 }
 
 /// Engine failure (no GPU, HIP error).  Never a verdict.

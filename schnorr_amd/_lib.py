@@ -129,6 +129,16 @@ def _signatures():
         "dsv_verify_keyed_open_mont_dev")
     add("ippppppzpp", "dsv_verify_vargen_keyed_open")           # (ks, u, R, PK, Gen, m, n, ok, misses)
     add("ippppppzppzpp", "dsv_verify_vargen_keyed_open_dev")
+    # key cache census: per-key hit counts and the distinct missed keys
+    add("zz", "dsv_keyset_census_workspace_bytes")              # (n)
+    add("ziz", "dsv_keyset_census_mont_workspace_bytes")        # (scheme, n)
+    # (ks, key_a, key_b, n, idx, hits, rep, count, totals[, workspace, workspace_bytes, stream])
+    add("ipppzppppp", "dsv_keyset_census")
+    add("ipppzppppppzp", "dsv_keyset_census_dev", "dsv_keyset_census_mont_dev")
+    # (ks, records | cols, n, idx, hits, rep, count, totals[, workspace, workspace_bytes, stream])
+    add("ippzppppp", "dsv_keyset_census_wire", "dsv_keyset_census_mont_cols")
+    add("ippzppppppzp", "dsv_keyset_census_wire_dev")
+    add("i", "dsv_debug_census_lds_keys")
     return t
 
 

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdsv.so")
-UNITS = ["dsv_context.hip", "dsv_device.hip", "dsv_host.hip", "dsv_wire.hip", "dsv_rlc.hip", "dsv_inputs.hip", "k_hash.hip", "k_verify.hip", "k_quad.hip", "k_vargen.hip", "k_misc.hip", "k_rlc.hip", "dsv_keyset.hip", "k_keyed.hip", "dsv_keyed_rlc.hip", "k_keyed_rlc.hip", "dsv_keyed_wire.hip", "k_keyed_wire.hip", "dsv_keyed_mont.hip", "dsv_keyed_lookup.hip", "k_keyed_lookup.hip", "dsv_keyed_open.hip", "k_keyed_open.hip", "k_keyed_open_var.hip", "dsv_keyed_open_wire.hip", "k_keyed_open_wire.hip", "k_keyed_replace.hip", "dsv_keyed_open_mont.hip", "k_keyed_open_mont.hip"]
+UNITS = ["dsv_context.hip", "dsv_device.hip", "dsv_host.hip", "dsv_wire.hip", "dsv_rlc.hip", "dsv_inputs.hip", "k_hash.hip", "k_verify.hip", "k_quad.hip", "k_vargen.hip", "k_misc.hip", "k_rlc.hip", "dsv_keyset.hip", "k_keyed.hip", "dsv_keyed_rlc.hip", "k_keyed_rlc.hip", "dsv_keyed_wire.hip", "k_keyed_wire.hip", "dsv_keyed_mont.hip", "dsv_keyed_lookup.hip", "k_keyed_lookup.hip", "dsv_keyed_open.hip", "k_keyed_open.hip", "k_keyed_open_var.hip", "dsv_keyed_open_wire.hip", "k_keyed_open_wire.hip", "k_keyed_replace.hip", "dsv_keyed_open_mont.hip", "k_keyed_open_mont.hip", "dsv_keyed_census.hip", "k_keyed_census.hip"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra"]
 

@@ -406,6 +406,7 @@ int dsv_init(int device) {
   ctx.fuse_double = !(fused && strcmp(fused, "0") == 0);
   const char* omf = getenv("DSV_OPEN_MONT_FUSED");
   ctx.open_mont_fused = !(omf && strcmp(omf, "0") == 0);
+  census_configure();
   const char* pre = getenv("DSV_PIPE_PREP_STREAM");
   ctx.prep_stream = pre && strcmp(pre, "1") == 0;
   auto log2_env = [](const char* name, int lo, int hi, int dflt) {

@@ -225,6 +225,8 @@ int device_context(const void* ptr, Context*& out);
 void release_context(Context& ctx);
 // dsv_keyset.hip: free the device memory of the live key sets of `device` and mark them dead (dsv_shutdown_device)
 void keysets_release_device(int device);
+// dsv_keyed_census.hip: DSV_CENSUS_LDS_KEYS, read when a device is initialised (dsv_debug_census_lds_keys)
+void census_configure();
 
 // workspace layout for the *_dev verify entry points: c[n][32] | valid[n]
 // + the per-lane window tables of the verify kernels (fixed grid, see kMaxVerifyGrid)

@@ -108,7 +108,8 @@ void launch_index_reinsert(KeyForm form, int npoints, const uint8_t* affine_rows
 }  // namespace dsv
 
 #ifdef DSV_INDEX_KERNELS
-// what the kernel units of the indices share (k_keyed_lookup.hip, k_keyed_replace.hip, k_keyed_open_mont.hip)
+// what the kernel units of the indices share (k_keyed_lookup.hip, k_keyed_replace.hip, k_keyed_open_mont.hip,
+// k_keyed_census.hip)
 namespace dsv {
 namespace {
 
@@ -173,6 +174,13 @@ __device__ __forceinline__ uint32_t walk_index(const Words<W>& w, const uint8_t*
     slot = (slot + 1) & mask;
   }
   return found;
+}
+// The walk for a caller that may hold a set without an index (k = 0: no rows, no slots): nothing is read and every
+// key misses.  What the census runs per item (k_keyed_census.hip).
+template <int W>
+__device__ __forceinline__ uint32_t find_key(const Words<W>& w, const uint8_t* __restrict__ rows,
+                                             const uint32_t* __restrict__ slots, size_t mask, size_t k) {
+  return k ? walk_index<W>(w, rows, slots, mask, k) : kSlotEmpty;
 }
 
 // ---- the key forms: W = 16-byte words per row; source(P0, P1, j) = the row of the affine source key j (u || v,

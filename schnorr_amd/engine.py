@@ -933,6 +933,23 @@ def keyed_open_mont_workspace_bytes(scheme, n):
     return int(_lib.load().dsv_keyed_open_mont_workspace_bytes(_code(scheme), n))
 
 
+def keyset_census_workspace_bytes(n):
+    """dsv_keyset_census_workspace_bytes: device bytes of KeySet.census_dev's / census_wire_dev's workspace — the
+    call's miss table (no GPU needed)"""
+    return int(_lib.load().dsv_keyset_census_workspace_bytes(n))
+
+
+def keyset_census_mont_workspace_bytes(scheme, n):
+    """dsv_keyset_census_mont_workspace_bytes: device bytes of KeySet.census_mont_dev's workspace (no GPU needed)"""
+    return int(_lib.load().dsv_keyset_census_mont_workspace_bytes(_code(scheme), n))
+
+
+def census_lds_keys():
+    """dsv_debug_census_lds_keys: up to how many keys a set's hits are counted per workgroup in LDS, as this process
+    runs it (DSV_CENSUS_LDS_KEYS, read by init)"""
+    return int(_lib.load().dsv_debug_census_lds_keys())
+
+
 def keyset_wire_home_slot(scheme, capacity, record):
     """dsv_debug_keyset_wire_home_slot: where the probe for a key record (32 bytes per key point) starts in the
     wire index of a set of `capacity` keys (no GPU needed)"""
@@ -1066,6 +1083,8 @@ class KeySet:
         ks.k, ks.capacity                          # append_mont_cols([pk96]) for the other key forms
         ks.replace([3, 17], PK_two)                # eviction: new keys in the places of registered ones, in place;
         ks.replace_wire([5], record)               # k and every other key's index stay
+        c = ks.census(PK)                          # the policy's input: c["hits"][j] items per registered key, and
+        ks.census_dev(PK, idx, hits, rep, count, totals, workspace)   # the distinct missed keys as (rep, count)
     """
 
     def __init__(self, scheme, PK, PK2=None, _wire=None, _mont_cols=None, capacity=None):
@@ -1551,3 +1570,78 @@ class KeySet:
         keyed_open_mont_workspace_bytes(scheme, n) bytes; misses as for lookup_dev."""
         self._verify_by_value_dev("dsv_verify_keyed_open_mont_dev", args, "verify_open_mont_dev",
                                   lambda n: keyed_open_mont_workspace_bytes(self.scheme, n), misses, stream, width=96)
+
+    # ---- the census: per-key hit counts and the distinct missed keys (what a key cache's policy reads) ----------
+    def _census_host(self, symbol, ins, n):
+        """a host census -> dict(idx, hits, rep, count, misses, unusable): idx uint32 [n] as lookup writes it, hits
+        uint32 [capacity] (items per registered key, counted from zero), rep / count uint32 [distinct missed keys]
+        (the lowest item index of the key and its items; by count descending, then rep ascending), misses = missed
+        items, unusable = those of them without key bytes (typed form)"""
+        idx, hits = np.zeros(n, dtype=np.uint32), np.zeros(self.capacity, dtype=np.uint32)
+        rep, count = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        totals = (ctypes.c_size_t * 4)()
+        _lib.check(getattr(_lib.load(), symbol)(self._handle(), *ins, n, _p(idx), _p(hits), _p(rep), _p(count), totals))
+        d = int(totals[0])
+        return dict(idx=idx, hits=hits, rep=rep[:d].copy(), count=count[:d].copy(), misses=int(totals[1]),
+                    unusable=int(totals[2]))
+
+    def census(self, *keys):
+        """dsv_keyset_census: host arrays key_a [n, 64] (two-point sets: key_a, key_b) -> the census of the batch's
+        keys against the set (see _census_host); blocks"""
+        cols = [_arr(c, 64) for c in self._key_cols(keys, "census")]
+        return self._census_host("dsv_keyset_census", _slots(_p(c) for c in cols), _same_n(*cols))
+
+    def census_wire(self, pk):
+        """dsv_keyset_census_wire: census() over key records ([n, 32], two-point sets [n, 64])"""
+        rec = _arr(pk, self._rec_bytes())
+        return self._census_host("dsv_keyset_census_wire", [_p(rec)], rec.shape[0])
+
+    def census_mont_cols(self, cols):
+        """dsv_keyset_census_mont_cols: census() over key OBJECTS where they lie (cols as for from_mont_cols: views
+        [n, 96] of Montgomery limbs u || v || z with strided rows); keys are compared by their normalised bytes, an
+        item with unusable limbs counts in misses and unusable and has no report entry"""
+        n, arr, held = _keyed_columns(list(cols), [96] * _KEY_POINTS[self.scheme], "census_mont_cols")
+        res = self._census_host("dsv_keyset_census_mont_cols", [arr], n)
+        del held
+        return res
+
+    def _census_dev(self, symbol, key_ptrs, n, dev, outs, ws_need, stream):
+        """the tail of a _dev census, checked: (idx_out, hits, rep, count, totals, workspace) — idx_out int32 [n] or
+        None, hits a 32-bit tensor of >= capacity elements or None (ADDED to), rep / count 32-bit of >= n elements,
+        totals 32-bit of >= 4, workspace uint8 of >= ws_need bytes"""
+        if len(outs) != 6:
+            raise ValueError("a census takes the key columns, then idx_out, hits, rep, count, totals, workspace")
+        idx_out, hits, rep, count, totals, workspace = outs
+        _lib.check(getattr(_lib.load(), symbol)(
+            self._handle(), *key_ptrs, n, None if idx_out is None else _col32(idx_out, n, dev, "idx_out"),
+            None if hits is None else _idx(hits, self.capacity, dev, "hits"), _idx(rep, n, dev, "rep"),
+            _idx(count, n, dev, "count"), _idx(totals, 4, dev, "totals"),
+            _bytes_out(workspace, ws_need, dev, "workspace"), workspace.numel(), _stream_ptr(stream, dev)))
+
+    def census_dev(self, *args, stream=None):
+        """dsv_keyset_census_dev: CUDA tensors (key_a[, key_b], idx_out, hits, rep, count, totals, workspace) — see
+        _census_dev; workspace >= keyset_census_workspace_bytes(n) bytes.  Entries [0, totals[0]) of rep / count are
+        the report, in no particular order; totals = (distinct missed keys, missed items, unusable items, 0).
+        Enqueued on `stream` (default: torch's current stream of the batch's device) as one chain of launches; does
+        not synchronise and may be captured."""
+        cols = self._key_cols(args[:-6], "census_dev")
+        names = ["key_a", "key_b"][:len(cols)]
+        n, dev = _rows(*zip(cols, [64] * len(cols), names))
+        self._census_dev("dsv_keyset_census_dev", _slots(self._key_ptr(c, nm) for c, nm in zip(cols, names)), n, dev,
+                         args[-6:], keyset_census_workspace_bytes(n), stream)
+
+    def census_wire_dev(self, pk, *outs, stream=None):
+        """dsv_keyset_census_wire_dev: census_dev over key records pk [n, 32 | 64]"""
+        n, dev = _rows((pk, self._rec_bytes(), "pk"))
+        self._census_dev("dsv_keyset_census_wire_dev", [self._rec_ptr(pk, self._rec_bytes(), "pk")], n, dev, outs,
+                         keyset_census_workspace_bytes(n), stream)
+
+    def census_mont_dev(self, *args, stream=None):
+        """dsv_keyset_census_mont_dev: census_dev over key objects' limbs (PK [n, 96][, PKp | Gen]), 16-byte aligned;
+        workspace >= keyset_census_mont_workspace_bytes(scheme, n) bytes; totals[2] counts the items with unusable
+        limbs"""
+        cols = self._key_cols(args[:-6], "census_mont_dev")
+        names = ["key_a", "key_b"][:len(cols)]
+        n, dev = _rows(*zip(cols, [96] * len(cols), names))
+        self._census_dev("dsv_keyset_census_mont_dev", _slots(self._rec_ptr(c, 96, nm) for c, nm in zip(cols, names)),
+                         n, dev, args[-6:], keyset_census_mont_workspace_bytes(self.scheme, n), stream)
